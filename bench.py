@@ -3,17 +3,23 @@
 solves/s) on a SuiteSparse-class SPD matrix, numeric phase only, inputs resident in HBM.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one numeric factorization of the workload matrix (pattern analysed and
 uploaded once, outside the timed region -- the reference times only the executor call
-too: examples/choleskyTest01.cpp:209-229).  After the K factorization steps, K forward
-solves are timed the same way and reported as `solves_per_sec`.
+too: examples/choleskyTest01.cpp:209-229).  A plain run sets up, warms up, times the K
+factorization steps and prints the result line; --dump-outputs DIR also writes the factor
+of the last step (a fixed sample of it for the large workloads) for comparisons between builds.
+--full adds the other legs: after the K factorization steps, K forward solves are timed the
+same way and reported as `solves_per_sec` (backward solves beside them), the per-kernel
+profile (`roofline*`), the other configurations and the CPU baseline.
 
 N = 1 workload: the Flan_1565-class stand-in (BASELINE.json configs[2], the largest
 single-GPU configuration; the SuiteSparse file itself cannot be fetched offline): 3-D
 27-point stencil 116^3, geometric nested dissection, n = 1 560 896, 19.4 GB of lValues.
-The nd24k-class (configs[1]) and parabolic_fem-class (configs[3]: solves with 1 / 8 / 64
+With --full the nd24k-class (configs[1]) and parabolic_fem-class (configs[3]: solves with 1 / 8 / 64
 right-hand sides) inputs are measured after it and reported as extra objects, never as
 `value`.  N > 1: the same matrix, ONE factorization over the ranks (strong scaling, as north_star
 describes it): etree subtrees below a cut on one rank each, the pieces of the separators above it
@@ -296,6 +302,28 @@ def cpu_baseline_whole(name: str, threads: int):
             "gflops_F": sym.flops_colcount / med / 1e9, "dense_kernels": blas or "built-in loops"}
 
 
+DUMP_MAX_ENTRIES = 3_000_000   # --dump-outputs: 24 MB of values + 24 MB of positions at most
+DUMP_SEED = 20260101
+
+
+def dump_factor(out_dir, L, dev):
+    """--dump-outputs: the factor the timed steps computed (lValues, what a caller of parsy_factor_device receives) as
+    DIR/lvalues.npy, float64.  A factor of more than DUMP_MAX_ENTRIES entries is sampled: the same seeded positions for
+    the same workload in every run, sorted, written beside it as DIR/lvalues_index.npy (float64: exact below 2^53)."""
+    import torch
+    xsize = L.numel()
+    if xsize <= DUMP_MAX_ENTRIES:
+        idx = np.arange(xsize, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, xsize, size=DUMP_MAX_ENTRIES, dtype=np.int64))
+    vals = L.index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy()
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "lvalues.npy", vals.astype(np.float64))
+    np.save(out / "lvalues_index.npy", idx.astype(np.float64))
+    log(f"[bench] wrote {len(idx)} of {xsize} factor entries to {out}/lvalues.npy")
+
+
 # ---------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -313,6 +341,13 @@ def main():
     ap.add_argument("--no-solve", action="store_true", help="factorizations only (profiling runs)")
     ap.add_argument("--in-flight", type=int, default=1,
                     help="also time this many independent factorizations in flight (extra field; 1 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline factorizations: the forward / backward solves, --in-flight, the "
+                    "per-kernel profile (roofline), the other configurations and the CPU baseline (the --no-* and "
+                    "--profile-steps options shape these legs); without it a run times the factorizations only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the factor of the last step to DIR/lvalues.npy (float64; a "
+                    "fixed seeded sample of its entries when it is large) and their positions to DIR/lvalues_index.npy")
     args = ap.parse_args()
 
     import torch
@@ -485,6 +520,11 @@ def main():
     if status != 0:
         raise SystemExit(f"factorization failed: status {status} (> 0: non-positive pivot at that column; "
                          f"< 0: a hand-off wait inside a launch timed out)")
+    if args.dump_outputs:
+        if world > 1:   # every piece is final on its owner: collect the factor on rank 0 first
+            MG.gather_factor(L, pieces, D.owner, rank, dist, stage_on_host=(backend != "nccl"))
+        if rank == 0:
+            dump_factor(args.dump_outputs, L, dev)
 
     # ---- N > 1: who took part (evidence for the reader of the line: ranks seen by a collective, their devices,
     # what each rank's device spent on the last factorization, what each rank sent) -----
@@ -510,7 +550,7 @@ def main():
 
     # ---- two independent factorizations in flight (reported beside `value`, never as `value`) -----
     pipelined = None
-    if world == 1 and args.in_flight > 1 and int(sym.xsize) * 8 * args.in_flight < 64e9:
+    if args.full and world == 1 and args.in_flight > 1 and int(sym.xsize) * 8 * args.in_flight < 64e9:
         plans2 = [plan] + [api.Plan(sym, local_rank) for _ in range(args.in_flight - 1)]
         Ls2 = [L] + [torch.empty_like(L) for _ in range(args.in_flight - 1)]
         streams2 = [torch.cuda.Stream(device=dev) for _ in range(args.in_flight)]
@@ -536,7 +576,9 @@ def main():
     solve_plan = None
     BX = None
     sharded = None
-    if world == 1:
+    if not args.full:
+        pass   # a plain run: the factorizations only
+    elif world == 1:
         if not args.no_solve:
             solve_plan = plan
             dt_s, dt_b, solve_err, BX, back_err = measure_solves(solve_plan, sym, L, nrhs, args.warmup, args.steps)
@@ -607,7 +649,7 @@ def main():
 
     # ---- per-kernel timing (hipEvents on the launch stream, launches serialised) for the roofline ----
     prof = None
-    if rank == 0 and world == 1 and args.profile_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.profile_steps > 0:
         plan.profile(2)
         for _ in range(args.profile_steps):
             plan.factor_device(values.data_ptr(), L.data_ptr(), stream)
@@ -812,14 +854,14 @@ def main():
 
     # (the CPU baseline's second sample works on this factor: the extras below reuse the buffer)
     L_host = None
-    if world == 1 and not args.no_cpu_baseline and sym.nsuper > 1:
+    if args.full and world == 1 and not args.no_cpu_baseline and sym.nsuper > 1:
         try:
             L_host = L.cpu().numpy()
         except Exception as e:
             log(f"no host copy of the factor for the top-separator sample: {e!r}")
     # ---- extra objects: the other single-GPU configurations of BASELINE.json (never `value`) ----
     del plan, solve_plan, BX
-    if world == 1 and not args.no_extras and args.workload == "flan":
+    if args.full and world == 1 and not args.no_extras and args.workload == "flan":
         L_big = L
         try:
             extras = {}
@@ -890,7 +932,7 @@ def main():
         except Exception as e:  # extras never cost the headline
             out["other_configs"] = {"failed": repr(e)}
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             share, share_src = granted_cpus()
             out["cpu_baseline"] = cpu_baseline(sym, share)

@@ -5,7 +5,7 @@ oracle/Makefile into oracle/_ref/libparsy_ref.so (see oracle/ref_harness.cpp for
 which reference functions that is), on inputs produced by this repo's deterministic
 generators.  The fixtures are data (inputs + expected outputs); no reference source text.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [inspector dense lbc larger ereach]   (no name: all of them)
 """
 import sys
 from pathlib import Path
@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
 import oracle as O  # noqa: E402
-from parsy_bench_amd import matrices as M  # noqa: E402
+from parsy_bench_amd import inspector as I, matrices as M  # noqa: E402
 
 OUT = Path(__file__).resolve().parent
 R = O.ref()
@@ -130,7 +130,46 @@ def lbc_ex15_cases():
     print("lbc_ex15:", len(out) // 4, "settings")
 
 
+# the fields of ref_analyze that tests/test_inspector_golden.py compares
+LARGER_FIELDS = ("Perm", "Parent", "ColCount", "super", "col2Sup", "sParent", "s", "A1p", "A1i", "A2p", "A2i", "p",
+                 "i_ptr", "A2x", "wfLevelPtr", "wfLevelSet", "prunePtr", "pruneSet")
+
+
+def larger_cases():
+    """The reference's inspector on the mid3d workload (20^3 27-point grid, the repo's own generator and ordering):
+    the larger problem of test_live_reference_on_a_larger_problem.  Inputs are not stored: the generator makes them."""
+    A, perm = M.workload("mid3d")
+    g = ref_analyze(A, perm)
+    np.savez_compressed(OUT / "reference_mid3d.npz", **{k: g[k] for k in LARGER_FIELDS})
+    print("reference_mid3d", g["scalars"])
+
+
+def ereach_cases():
+    """The reference's ereach_sn (the supernodes that update supernode t) for every t of tiny2d / small3d / mid3d, on
+    the product's inspector output for them: <name>_ptr (nsuper + 1) and <name>_set (the lists, concatenated)."""
+    out = {}
+    for name in ("tiny2d", "small3d", "mid3d"):
+        A, perm = M.workload(name)
+        sym = I.analyze(A, perm)
+        ns = sym.nsuper
+        a1p, a1i = np.ascontiguousarray(sym.A1p, np.int32), np.ascontiguousarray(sym.A1i, np.int32)
+        c2s, par = np.ascontiguousarray(sym.col2Sup, np.int32), np.ascontiguousarray(sym.sParent, np.int32)
+        ptr, lists = [0], []
+        for t in range(ns):
+            xr = np.zeros(2 * ns, np.int32)
+            top = R.ref_ereach_sn(ns, P(a1p), P(a1i), int(sym.super[t]), int(sym.super[t + 1]), P(c2s), P(par),
+                                  P(xr), P(xr[ns:]))
+            lists.append(xr[top:ns].copy())
+            ptr.append(ptr[-1] + ns - top)
+        out[f"{name}_ptr"] = np.array(ptr, np.int32)
+        out[f"{name}_set"] = np.concatenate(lists).astype(np.int32)
+    np.savez_compressed(OUT / "ereach_sn.npz", **out)
+    print("ereach_sn:", {k: v.shape for k, v in out.items()})
+
+
+CASES = {"inspector": inspector_cases, "dense": dense_kernel_cases, "lbc": lbc_ex15_cases, "larger": larger_cases,
+         "ereach": ereach_cases}
+
 if __name__ == "__main__":
-    inspector_cases()
-    dense_kernel_cases()
-    lbc_ex15_cases()
+    for name in sys.argv[1:] or CASES:
+        CASES[name]()

@@ -183,3 +183,52 @@ def test_matrixmarket_input_of_the_bench(tmp_path):
     bad.write_text(f"{A0.n}\n" + "\n".join(["0"] * A0.n) + "\n")
     with pytest.raises(ValueError):
         M.read_ordering(str(bad), A0.n)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_dump_samples_a_large_factor(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on a factor larger than DUMP_MAX_ENTRIES: a sorted sample of distinct positions, the
+    same in every run, and the factor's values at them."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 1000)
+    L = torch.arange(100000, dtype=torch.float64) * 0.5
+    for d in ("a", "b"):
+        bench.dump_factor(tmp_path / d, L, torch.device("cpu"))
+    idx, lv = np.load(tmp_path / "a" / "lvalues_index.npy"), np.load(tmp_path / "a" / "lvalues.npy")
+    assert idx.dtype == np.float64 and lv.dtype == np.float64
+    assert 900 < len(idx) <= 1000 and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < L.numel()
+    assert np.array_equal(lv, idx * 0.5)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "lvalues_index.npy"))
+    assert np.array_equal(lv, np.load(tmp_path / "b" / "lvalues.npy"))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path, oracle):
+    """A plain bench.py run times --steps factorizations and nothing else; --dump-outputs writes the factor of the last
+    step, which is the oracle's factor."""
+    import json
+    import numpy as np
+    from conftest import problem
+    from parsy_bench_amd import inspector as I
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "small3d", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "factorizations/s" and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert line["solves_per_sec"] is None and not {"roofline", "other_configs", "cpu_baseline"} & set(line)
+    A, perm, sym = problem("small3d")
+    lv, idx = np.load(out / "lvalues.npy"), np.load(out / "lvalues_index.npy")
+    assert lv.dtype == np.float64 and np.array_equal(idx, np.arange(sym.xsize))
+    ok, lo, _ = oracle.cholesky_05(sym, sym.A2x, I.trivial_hlevel(sym))
+    assert ok and float(np.abs(lv - lo).max() / np.abs(lo).max()) <= 1e-11

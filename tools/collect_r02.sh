@@ -14,10 +14,10 @@ O=$R/gpurun_out/r02
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 H=$(python3 -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.kernel_source_hash())")
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r02_stats -o st -- python3 $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/stats_bench.json 2> $O/stats_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r02_stats -o st -- python3 $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/stats_bench.json 2> $O/stats_bench.err
 cp /tmp/r02_stats/st_kernel_stats.csv $O/${W}_kernel_stats.csv
 # the same command with every launch on one stream (as in bench.py's profiled steps: roofline.avg_launch_ms)
-PARSY_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r02_stats_s -o st -- python3 $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/stats_bench_serialized.json 2> $O/stats_bench_serialized.err
+PARSY_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r02_stats_s -o st -- python3 $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/stats_bench_serialized.json 2> $O/stats_bench_serialized.err
 cp /tmp/r02_stats_s/st_kernel_stats.csv $O/${W}_kernel_stats_serialized.csv
 pmc() {  # group name, program..., -- counters
     g=$1; shift
