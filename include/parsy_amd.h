@@ -334,6 +334,16 @@ const char* parsy_last_error(void);
 /* Number of visible HIP devices (0 when none / runtime unusable). */
 int parsy_device_count(void);
 
+/* ---- Diagnostics: kernel witness ------------------------------------------------------------------------
+ * One host-side counter per solve kernel instantiation that the library can enqueue (process-wide, every plan and
+ * device), incremented when a launch of it is enqueued.  Tests use it to prove which kernels a solve ran.
+ * Entries 0 .. parsy_debug_kernel_count() - 1; the name is the kernel's, template arguments included (for example
+ * "k_solve_small_mrhs<64,true>"; NULL out of range). */
+int parsy_debug_kernel_count(void);
+const char* parsy_debug_kernel_name(int k);
+unsigned long long parsy_debug_kernel_launches(int k);
+void parsy_debug_kernel_reset(void);
+
 /* ------------------------------------------------------------------------ */
 /* 3. Inspector (host)                                                       */
 /* ------------------------------------------------------------------------ */

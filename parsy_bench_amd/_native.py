@@ -84,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "parsy_dist_get", "parsy_dist_level_messages", "parsy_dist_message", "parsy_dist_check",
     "parsy_mg_create", "parsy_mg_destroy", "parsy_mg_set_values", "parsy_mg_factor", "parsy_mg_rank_ms",
     "parsy_mg_gather_host", "parsy_mg_dist", "parsy_mg_plan", "parsy_mg_profile", "parsy_plan_profile_levels",
+    "parsy_debug_kernel_count", "parsy_debug_kernel_name", "parsy_debug_kernel_launches", "parsy_debug_kernel_reset",
 ]
 
 
@@ -103,6 +104,12 @@ def _declare(lib):
     vp = C.c_void_p
     lib.parsy_last_error.restype = C.c_char_p
     lib.parsy_device_count.restype = C.c_int
+    lib.parsy_debug_kernel_count.restype = C.c_int
+    lib.parsy_debug_kernel_name.restype = C.c_char_p
+    lib.parsy_debug_kernel_name.argtypes = [C.c_int]
+    lib.parsy_debug_kernel_launches.restype = C.c_ulonglong
+    lib.parsy_debug_kernel_launches.argtypes = [C.c_int]
+    lib.parsy_debug_kernel_reset.restype = None
     lib.parsy_analyze.restype = vp
     lib.parsy_analyze.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
     lib.parsy_symbolic_free.argtypes = [vp]

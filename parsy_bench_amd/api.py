@@ -25,6 +25,18 @@ def device_count() -> int:
     return int(N.lib().parsy_device_count())
 
 
+def kernel_launches() -> dict:
+    """Kernel witness: launches enqueued per solve kernel instantiation since the last reset (process-wide),
+    name -> count, every entry of the library's table (zero included)."""
+    lib = N.lib()
+    return {lib.parsy_debug_kernel_name(k).decode(): int(lib.parsy_debug_kernel_launches(k))
+            for k in range(lib.parsy_debug_kernel_count())}
+
+
+def reset_kernel_launches() -> None:
+    N.lib().parsy_debug_kernel_reset()
+
+
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -260,7 +260,7 @@ static void profile_mark(parsy_plan* pl, int kind, hipStream_t stream, size_t& c
 // hand sides (trsv_sub_kernels.hip; PARSY_SUB_MRHS_MIN, 0: never)
 // (the kernels address x by a 32-bit byte offset from a wave-uniform base: 16 rows or right-hand sides of either stride)
 static bool sub_tiers_usable(const parsy_plan* pl, int nrhs, int ldx) {
-    const int m = solve_sub_mrhs_min();
+    const int m = pl->dp.gates.sub_mrhs_min;
     return pl->dp.sub_ntiers > 0 && m > 0 && nrhs >= m && ldx < (1 << 24) && nrhs < (1 << 20);
 }
 
@@ -335,7 +335,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                     launch_solve_small(pl->dp, l.first, l.count, l.jb, l.fused == 2, Lc, x, nrhs, ldx, pl->solve_ldq, stream);
                 break;
             case kLaunchSolvePanel:
-                if (l.fused && nrhs >= solve_mrhs_min() && !pl->old_mrhs_chain)
+                if (l.fused && nrhs >= pl->dp.gates.chain_mrhs_min && !pl->old_mrhs_chain)
                     launch_solve_blocks_mrhs(pl->dp, l.lds_bytes, l.wait_level, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx,
                                              pl->solve_ldq, l.jb, pl->solve_wait_bias, stream);
                 else if (l.fused)
@@ -488,6 +488,7 @@ int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int
         return -1;
     }
     pl->levels_open = false;
+    pl->dp.gates = read_solve_gates();
     const int64_t need = (int64_t)ldx * nrhs;
     double *y = nullptr, *y_next = nullptr;
     int *st = nullptr, *st_next = nullptr;
@@ -584,6 +585,7 @@ int plan_solve_levels(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, 
     const int passes = backward ? (nrhs + 3) / 4 : (nrhs + 7) / 8;
     const int64_t need = (int64_t)ldx * nrhs;
     if (first) {
+        pl->dp.gates = read_solve_gates();   // (once per solve: its later steps keep them)
         if (solve_begin(pl, passes, stream) != 0) return -1;
         {
             const char* e = std::getenv("PARSY_OLD_MRHS_CHAIN");
@@ -763,6 +765,8 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
         return -1;
     }
     pl->levels_open = false;   // (a solve in steps of levels that was never finished is abandoned)
+    pl->dp.gates = read_solve_gates();
+    const SolveGates& G = pl->dp.gates;
     double *y = nullptr, *y_next = nullptr;
     int *st = nullptr, *st_next = nullptr;
     int one_rc = solve_takes_one_launch(pl, nrhs, false) ? one_begin(pl, false, nrhs, stream, y, y_next, st, st_next) : 1;
@@ -787,9 +791,15 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
         const char* e = std::getenv("PARSY_OLD_MRHS_CHAIN");
         pl->old_mrhs_chain = e && e[0] == '1';
     }
-    // (several right-hand sides on the armed-buffer chain launches: one prologue launch, below)
-    const bool arm_wide = nrhs >= solve_mrhs_min() && !pl->old_mrhs_chain && pl->S.n_solve_wide > 0 &&
-                          !pl->S.solve_wide_list.empty() && pl->S.solve_fix_list.empty();
+    // The prologue follows the chain launches the solve will take (run_range: kLaunchSolvePanel), chosen here once:
+    //   mrhs_chain -- k_solve_blocks_mrhs on the armed buffer (from G.chain_mrhs_min right-hand sides on: one as well under
+    //                 PARSY_MRHS_MIN=1): k_solve_arm_wide zeroes the status word and the tickets and arms the wide columns
+    //                 (where it can: no fixup list), else the memsets of solve_begin and the whole buffer armed;
+    //   one right-hand side otherwise -- k_solve_chain_w: memsets, whole buffer armed;
+    //   otherwise -- the flag protocol (k_solve_chain / k_solve_chain_mrhs): memsets, nothing armed.
+    const bool mrhs_chain = nrhs >= G.chain_mrhs_min && !pl->old_mrhs_chain;
+    const bool arm_wide = mrhs_chain && pl->S.n_solve_wide > 0 && !pl->S.solve_wide_list.empty() &&
+                          pl->S.solve_fix_list.empty();
     if (solve_begin(pl, passes, stream, !arm_wide) != 0) return -1;
     // (many right-hand sides: k_solve_blocks_mrhs on the armed buffer; PARSY_OLD_MRHS_CHAIN=1: the flag protocol of rounds 1-2)
     {
@@ -804,7 +814,7 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
     // (measured, 64 right-hand sides: Flan-class 23.1 -> 20.4 ms, nd24k-class 1.31 -> 1.19 ms; parabolic_fem-class 1.72 ->
     // 1.75 ms -- its factor has 67 entries per row and the two transposes, 0.3 ms, cost what the kernels gain: the layout
     // is taken from 200 entries of L per row on)
-    const bool use_xt = xt_min > 0 && nrhs >= xt_min && nrhs >= solve_small_mrhs_min() && nrhs >= solve_mrhs_min() &&
+    const bool use_xt = xt_min > 0 && nrhs >= xt_min && nrhs >= G.mrhs_min && nrhs >= G.chain_mrhs_min &&
                         !pl->old_mrhs_chain && pl->S.solve_fix_list.empty() &&
                         (pl->S.xsize >= (int64_t)150 * pl->S.n || (xt_env && *xt_env));
     const int ldq = use_xt ? (nrhs + 15) & ~15 : 0;
@@ -830,11 +840,10 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
     PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
     // the chain launches hand x over through xscratch itself (one right-hand side: k_solve_chain_w; many:
     // k_solve_blocks_mrhs): every entry holds the armed pattern when the solve starts
-    if (nrhs == 1 && pl->S.n_solve_wide > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch, ldx, stream));
-    else if (arm_wide)
+    if (arm_wide)
         launch_solve_arm_wide(pl->dp, (int)pl->S.solve_wide_list.size() / 2, pl->xscratch, nrhs, ldx, ldq,
                               std::max(pl->S.n_solve_chain_launches, 1), stream);
-    else if (nrhs >= solve_mrhs_min() && !pl->old_mrhs_chain && pl->S.n_solve_wide > 0)
+    else if ((mrhs_chain || nrhs == 1) && pl->S.n_solve_wide > 0)
         PARSY_HIP(solve_arm_handoff(pl->xscratch, need, stream));
     launch_diag_inverse(pl->dp, (int)pl->S.solve_wide_list.size() / 2, d_L, pl->dinv, stream);
     pl->solve_ldq = ldq;

@@ -11,6 +11,70 @@ namespace parsy {
 
 constexpr int kPassLanes = 8;    // passes over the right-hand sides of a solve that run side by side
 
+// The thresholds that choose between the solves' kernel variants.  The defaults are the tuned values; the variables
+// (diagnostics, tests: every variant can be forced) are read ONCE at the start of every forward / backward solve call
+// (read_solve_gates, into the plan's DevicePattern, where the launch functions take them from) -- not per process, so a
+// test can change them between solves, and not per launch (a solve makes hundreds of launches).
+struct SolveGates {
+    int mrhs_min = 6;             // PARSY_MRHS_MIN=k (sets this and the next): narrow supernodes take k_solve_small_mrhs from here on
+    int chain_mrhs_min = 2;       // ... the wide supernodes' chain k_solve_blocks_mrhs (armed hand-off buffer)
+    int bmrhs_min = 16;           // PARSY_BMRHS_MIN: the backward solve's many-right-hand-side kernels
+    bool bmrhs_wide_only = true;  // PARSY_BMRHS_WIDE_ONLY=0: k_bsolve_block_mrhs on launches of few blocks too
+    int bchain_min_blocks = 128;  // PARSY_BCHAIN_MIN_BLOCKS: chain launches take k_bsolve_chain_mrhs from this many block columns on
+    int small_halves_min = 512;   // PARSY_SMALL_MRHS_HALVES_MIN: k_solve_small_mrhs<64> sweeps in halves from this many supernodes on
+    int sub_mrhs_min = 6;         // PARSY_SUB_MRHS_MIN: the subtree launches take the many-right-hand-side form (0: never)
+};
+SolveGates read_solve_gates();
+
+// Kernel witness (diagnostics, tests): one host-side counter per solve kernel instantiation that a launch function can
+// enqueue, bumped next to its hipLaunchKernelGGL (a relaxed atomic add on the host: nothing on the GPU).  Exported
+// through parsy_debug_kernel_* so that a test can prove which kernels a solve ran.
+#define PARSY_WITNESS_KERNELS(X)                                                                                     \
+    X(SolveTiny, "k_solve_tiny<16>")                                                                                 \
+    X(SolveSmall, "k_solve_small")                                                                                   \
+    X(SolveSmallMrhs16, "k_solve_small_mrhs<16>")                                                                    \
+    X(SolveSmallMrhs32, "k_solve_small_mrhs<32>")                                                                    \
+    X(SolveSmallMrhs64, "k_solve_small_mrhs<64>")                                                                    \
+    X(SolveSmallMrhs64Halves, "k_solve_small_mrhs<64,true>")                                                         \
+    X(SolvePanel, "k_solve_panel")                                                                                   \
+    X(DiagInverse, "k_diag_inverse")                                                                                 \
+    X(SolveChain8, "k_solve_chain<8>")                                                                               \
+    X(SolveChainW2, "k_solve_chain_w<2>")                                                                            \
+    X(SolveChainW4, "k_solve_chain_w<4>")                                                                            \
+    X(SolveChainMrhs, "k_solve_chain_mrhs")                                                                          \
+    X(SolveBlocksMrhsNarrow, "k_solve_blocks_mrhs<true>")                                                            \
+    X(SolveBlocksMrhs, "k_solve_blocks_mrhs<false>")                                                                 \
+    X(TransposeX, "k_transpose_x")                                                                                   \
+    X(SolveArmWide, "k_solve_arm_wide")                                                                              \
+    X(SolveOne1, "k_solve_one<1>")                                                                                   \
+    X(SolveOne4, "k_solve_one<4>")                                                                                   \
+    X(SolveOne8, "k_solve_one<8>")                                                                                   \
+    X(BsolveOne1, "k_bsolve_one<1>")                                                                                 \
+    X(BsolveOne4, "k_bsolve_one<4>")                                                                                 \
+    X(BsolveOne8, "k_bsolve_one<8>")                                                                                 \
+    X(BsolveBlock1, "k_bsolve_block<1>")                                                                             \
+    X(BsolveBlock4, "k_bsolve_block<4>")                                                                             \
+    X(BsolveBlockMrhs1, "k_bsolve_block_mrhs<1>")                                                                    \
+    X(BsolveBlockMrhs4, "k_bsolve_block_mrhs<4>")                                                                    \
+    X(BsolveChainMrhs, "k_bsolve_chain_mrhs")                                                                        \
+    X(BsolveTiny16, "k_bsolve_tiny<16>")                                                                             \
+    X(BsolveTiny32, "k_bsolve_tiny<32>")                                                                             \
+    X(BsolveTinyMrhs, "k_bsolve_tiny_mrhs")                                                                          \
+    X(BsolveBelow, "k_bsolve_below")                                                                                 \
+    X(BsolveChainW, "k_bsolve_chain_w")                                                                              \
+    X(SolveFixup, "k_solve_fixup")                                                                                   \
+    X(RhsOnes, "k_rhs_ones")                                                                                         \
+    X(CopySegments, "k_copy_segments")                                                                               \
+    X(SolveSubMrhs, "k_solve_sub_mrhs")                                                                              \
+    X(BsolveSubMrhs, "k_bsolve_sub_mrhs")
+enum WitnessKernel : int {
+#define PARSY_WITNESS_ENUM(id, name) kW##id,
+    PARSY_WITNESS_KERNELS(PARSY_WITNESS_ENUM)
+#undef PARSY_WITNESS_ENUM
+    kWitnessCount
+};
+void witness_launch(WitnessKernel k);
+
 struct DevicePattern {           // device copies of Schedule arrays
     const SnDesc* sn = nullptr;           // the supernodes (solve kernels)
     const SnDesc* csn = nullptr;          // Cholesky view (pieces of the very wide ones): Cholesky kernels
@@ -65,6 +129,7 @@ struct DevicePattern {           // device copies of Schedule arrays
         int nblocks = 0;
         int64_t nslots = 1;
     } one_f, one_b;
+    SolveGates gates;   // of the running solve (read_solve_gates at its start)
 };
 
 // lValues[a_dst[q]] = values[q]
@@ -103,9 +168,6 @@ void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doubl
 void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const double* L, double* x, int nrhs, int ldx,
                             hipStream_t stream);
 int solve_sub_prepare(int max_slots);   // once per plan: LDS beyond 64 KB per workgroup needs the kernels' attribute (-1: refused)
-int solve_sub_mrhs_min();   // right-hand sides from which those kernels take the subtree launches (PARSY_SUB_MRHS_MIN; 0: never)
-int solve_mrhs_min();
-int solve_small_mrhs_min();
 hipError_t solve_arm_handoff(double* xscratch, int64_t n, hipStream_t stream);
 // several right-hand sides: status word + ticket counters zeroed and the hand-off buffer armed at the wide supernodes' columns
 void launch_solve_arm_wide(const DevicePattern& P, int npairs, double* xscratch, int nrhs, int ldx, int ldq, int ntickets,

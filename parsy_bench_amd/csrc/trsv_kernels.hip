@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 #include "kernels.hpp"
@@ -318,25 +319,9 @@ static constexpr int kRhsM = 64;        // right-hand sides per pass
 //   * for the narrow supernodes (k_solve_small_mrhs) from 6 right-hand sides on,
 //   * for the wide supernodes' chain (k_solve_blocks_mrhs) from 2 on
 // (parabolic_fem-class input, MI355X, forward solve: 4 right-hand sides 1.02 -> 0.85 ms, 8: 1.41 -> 0.89 ms; Flan-class,
-// 8: 18.2 -> 11.6 ms).  PARSY_MRHS_MIN=k sets both thresholds to k (diagnostics, tests).
-static int mrhs_env() {
-    static const int v = [] {
-        const char* e = std::getenv("PARSY_MRHS_MIN");
-        return e && *e ? std::atoi(e) : 0;
-    }();
-    return v;
-}
-static int mrhs_min() { return mrhs_env() > 0 ? mrhs_env() : 6; }         // narrow supernodes
-static int chain_mrhs_min() { return mrhs_env() > 0 ? mrhs_env() : 2; }   // wide supernodes' chain
-static int bmrhs_min() {                // ... of the backward solve (PARSY_BMRHS_MIN)
-    static const int v = [] {
-        const char* e = std::getenv("PARSY_BMRHS_MIN");
-        return e && *e ? std::atoi(e) : 16;
-    }();
-    return v;
-}
+// 8: 18.2 -> 11.6 ms).  PARSY_MRHS_MIN=k sets both thresholds to k (diagnostics, tests).  These and the other gates of the
+// solves' variants: SolveGates (kernels.hpp), read at the start of every solve.
 static constexpr int kLdXs = kRhsM + 4; // row stride of xs in LDS
-static constexpr int kSmallMrhsHalvesMin = 512;   // k_solve_small_mrhs<64>: launches of at least this many supernodes sweep in halves
 
 template <int WMAX, bool HALVES = false>  // WMAX: widest supernode of the launch, rounded up to 16 / 32 / 64: sizes LDS and loops
 __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __restrict__ sn,
@@ -519,26 +504,33 @@ void launch_solve_small(const DevicePattern& P, int first, int count, int wmax, 
     // subtree launch: `first` counts (begin, end) pairs of solve_small_ranges, which index the whole list
     const int32_t* list = subtrees ? P.solve_small_list : P.solve_small_list + first;
     const int32_t* ranges = subtrees ? P.solve_small_ranges + 2 * first : nullptr;
-    if (nrhs < mrhs_min() && wmax <= kTinyWidth) {   // one wave per supernode (or per subtree of them)
+    const int mrhs_min = P.gates.mrhs_min;
+    if (nrhs < mrhs_min && wmax <= kTinyWidth) {   // one wave per supernode (or per subtree of them)
+        witness_launch(kWSolveTiny);
         hipLaunchKernelGGL(k_solve_tiny<kTinyWidth>, dim3(count, std::min(kPassLanes, nrhs)), dim3(64), 0, stream, P.sn,
                            list, ranges, P.rows, L, x, nrhs, ldx);
         return;
     }
-    if (nrhs >= mrhs_min()) {
-        if (wmax <= 16)
+    if (nrhs >= mrhs_min) {
+        if (wmax <= 16) {
+            witness_launch(kWSolveSmallMrhs16);
             hipLaunchKernelGGL(k_solve_small_mrhs<16>, dim3(count), dim3(kThreads), 0, stream, P.sn, list, ranges,
                                P.rows, L, x, nrhs, ldx, ldq);
-        else if (wmax <= 32)
+        } else if (wmax <= 32) {
+            witness_launch(kWSolveSmallMrhs32);
             hipLaunchKernelGGL(k_solve_small_mrhs<32>, dim3(count), dim3(kThreads), 0, stream, P.sn, list, ranges,
                                P.rows, L, x, nrhs, ldx, ldq);
-        else
-            if (count >= kSmallMrhsHalvesMin || nrhs <= 32)   // (at most 32 right-hand sides: one sweep either way, fewer registers)
-                hipLaunchKernelGGL((k_solve_small_mrhs<64, true>), dim3(count), dim3(kThreads), 0, stream, P.sn, list, ranges, P.rows, L, x,
-                                   nrhs, ldx, ldq);
-            else
+        } else if (count >= P.gates.small_halves_min || nrhs <= 32) {   // (at most 32 right-hand sides: one sweep either way, fewer registers)
+            witness_launch(kWSolveSmallMrhs64Halves);
+            hipLaunchKernelGGL((k_solve_small_mrhs<64, true>), dim3(count), dim3(kThreads), 0, stream, P.sn, list, ranges, P.rows, L, x,
+                               nrhs, ldx, ldq);
+        } else {
+            witness_launch(kWSolveSmallMrhs64);
             hipLaunchKernelGGL(k_solve_small_mrhs<64>, dim3(count), dim3(kThreads), 0, stream, P.sn, list, ranges,
                                P.rows, L, x, nrhs, ldx, ldq);
+        }
     } else {
+        witness_launch(kWSolveSmall);
         hipLaunchKernelGGL(k_solve_small, dim3(count, std::min(kPassLanes, (nrhs + kRhs - 1) / kRhs)),
                            dim3(kThreads), 0, stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx);
     }
@@ -623,6 +615,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_panel(const SnDesc* __restri
 void launch_solve_panel(const DevicePattern& P, int first, int count, const double* L, double* x,
                         double* xscratch, int nrhs, int ldx, hipStream_t stream) {
     if (count <= 0) return;
+    witness_launch(kWSolvePanel);
     hipLaunchKernelGGL(k_solve_panel, dim3(count), dim3(kThreads), 0, stream, P.sn,
                        P.solve_panels + first, P.rows, L, x, xscratch, nrhs, ldx);
 }
@@ -742,6 +735,7 @@ __global__ __launch_bounds__(64) void k_diag_inverse(const SnDesc* __restrict__ 
 
 void launch_diag_inverse(const DevicePattern& P, int count, const double* L, double* dinv, hipStream_t stream) {
     if (count <= 0) return;
+    witness_launch(kWDiagInverse);
     hipLaunchKernelGGL(k_diag_inverse, dim3(count), dim3(64), 0, stream, P.sn, P.solve_wide_list, L, dinv);
 }
 
@@ -1130,7 +1124,6 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
 // product too (t through LDS into operand layout); the rows below the supernode's columns are scattered at the end
 // with atomics, as in the one-vector kernel.
 static constexpr int kMrhsWideBlocks = 128;   // backward launches of at least this many blocks take 64 right-hand sides per pass
-static constexpr int kBChainMinBlocks = 128;  // ... chain launches: k_bsolve_chain_mrhs from this many block columns on
 static constexpr int kLdXm = kRhsM + 16;  // row stride of the staged x_jb / t_jb (doubles): conflict-free operand reads
 static constexpr int kSolveRowsM = kSolveRowsMrhs;   // rows of a chunk task of k_solve_blocks_mrhs (schedule.hpp)
 
@@ -1824,12 +1817,15 @@ void launch_solve_blocks_mrhs(const DevicePattern& P, int first, int count, cons
                               hipStream_t stream) {
     if (count <= 0) return;
     const int lanes_m = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
-    if (nrhs <= 16)
+    if (nrhs <= 16) {
+        witness_launch(kWSolveBlocksMrhsNarrow);
         hipLaunchKernelGGL(k_solve_blocks_mrhs<true>, dim3(count * lanes_m), dim3(kThreads), 0, stream, P.sn, P.solve_mtasks + first,
                            P.rows, L, dinv, x, xscratch, nrhs, ldx, ldq, P.sinfo, P.stickets + ticket, wait_bias, count);
-    else
+    } else {
+        witness_launch(kWSolveBlocksMrhs);
         hipLaunchKernelGGL(k_solve_blocks_mrhs<false>, dim3(count * lanes_m), dim3(kThreads), 0, stream, P.sn, P.solve_mtasks + first,
                            P.rows, L, dinv, x, xscratch, nrhs, ldx, ldq, P.sinfo, P.stickets + ticket, wait_bias, count);
+    }
 }
 
 // X between its two layouts: right-hand-side-major a[q * lda + row] <-> row-major b[row * ldb + q] (64 x 64 tiles
@@ -1867,13 +1863,36 @@ __global__ __launch_bounds__(kThreads) void k_transpose_x(double* __restrict__ a
 }
 void launch_transpose_x(double* x, int64_t ldx, double* xt, int64_t ldq, int n, int nrhs, bool to_rows, hipStream_t stream) {
     if (n <= 0 || nrhs <= 0) return;
+    witness_launch(kWTransposeX);
     hipLaunchKernelGGL(k_transpose_x, dim3((n + 63) / 64, (nrhs + 63) / 64), dim3(kThreads), 0, stream, x, ldx, xt, ldq, n,
                        nrhs, to_rows ? 1 : 0);
 }
 
-// the many-right-hand-side kernels start at this many right-hand sides (the executor arms the hand-off buffer for them)
-int solve_mrhs_min() { return chain_mrhs_min(); }
-int solve_small_mrhs_min() { return mrhs_min(); }
+SolveGates read_solve_gates() {
+    SolveGates g;
+    auto num = [](const char* name, int& v) {
+        const char* e = std::getenv(name);
+        if (e && *e) v = std::atoi(e);
+    };
+    int m = 0;
+    num("PARSY_MRHS_MIN", m);
+    if (m > 0) g.mrhs_min = g.chain_mrhs_min = m;
+    num("PARSY_BMRHS_MIN", g.bmrhs_min);
+    const char* w = std::getenv("PARSY_BMRHS_WIDE_ONLY");
+    g.bmrhs_wide_only = !(w && w[0] == '0');
+    num("PARSY_BCHAIN_MIN_BLOCKS", g.bchain_min_blocks);
+    num("PARSY_SMALL_MRHS_HALVES_MIN", g.small_halves_min);
+    num("PARSY_SUB_MRHS_MIN", g.sub_mrhs_min);
+    return g;
+}
+
+static std::atomic<unsigned long long> g_witness[kWitnessCount];
+static const char* const kWitnessNames[kWitnessCount] = {
+#define PARSY_WITNESS_NAME(id, name) name,
+    PARSY_WITNESS_KERNELS(PARSY_WITNESS_NAME)
+#undef PARSY_WITNESS_NAME
+};
+void witness_launch(WitnessKernel k) { g_witness[k].fetch_add(1, std::memory_order_relaxed); }
 
 // One right-hand side: the chain launches hand x over through xscratch itself (k_solve_chain_w); every entry must
 // hold the armed pattern when the solve starts.
@@ -1917,6 +1936,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_arm_wide(const SnDesc* __res
 void launch_solve_arm_wide(const DevicePattern& P, int npairs, double* xscratch, int nrhs, int ldx, int ldq, int ntickets,
                            hipStream_t stream) {
     const bool tr = ldq > 0;
+    witness_launch(kWSolveArmWide);
     hipLaunchKernelGGL(k_solve_arm_wide, dim3(std::max(npairs, 1)), dim3(kThreads), 0, stream, P.sn, P.solve_wide_list, npairs,
                        xscratch, nrhs, (int64_t)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), P.sinfo, P.stickets, ntickets);
 }
@@ -1925,8 +1945,9 @@ void launch_solve_chain(const DevicePattern& P, int first, int count, const doub
                         double* x, double* xscratch, int nrhs, int ldx, int epoch0, int ticket, int wait_bias,
                         hipStream_t stream) {
     if (count <= 0) return;
-    if (nrhs >= chain_mrhs_min()) {
+    if (nrhs >= P.gates.chain_mrhs_min) {
         const int lanes_m = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
+        witness_launch(kWSolveChainMrhs);
         hipLaunchKernelGGL(k_solve_chain_mrhs, dim3(count * lanes_m), dim3(kThreads), 0, stream, P.sn,
                            P.solve_panels + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, P.flags, epoch0, P.sinfo,
                            P.stickets + ticket, wait_bias, count, P.flag_stride);
@@ -1935,18 +1956,24 @@ void launch_solve_chain(const DevicePattern& P, int first, int count, const doub
     const int nq = nrhs == 1 ? 1 : kRhs;
     const int lanes = std::min(kPassLanes, (nrhs + nq - 1) / nq);
     if (nrhs == 1) {   // (xscratch was armed by the caller: solve_arm_handoff)
-        if (count <= kChainFewChunks)
+        if (count <= kChainFewChunks) {
+            witness_launch(kWSolveChainW2);
             hipLaunchKernelGGL(k_solve_chain_w<2>, dim3(2 * count), dim3(kChainThreads), 0, stream, P.sn,
                                P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
                                wait_bias);
-        else
+        } else {
+            witness_launch(kWSolveChainW4);
             hipLaunchKernelGGL(k_solve_chain_w<4>, dim3(count), dim3(kChainThreads), 0, stream, P.sn,
                                P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
                                wait_bias);
-    } else
+        }
+    } else {
+        static_assert(kRhs == 8, "witness entry k_solve_chain<8>");
+        witness_launch(kWSolveChain8);
         hipLaunchKernelGGL(k_solve_chain<kRhs>, dim3(count * lanes), dim3(kThreads), 0, stream, P.sn,
                            P.solve_panels + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, P.flags, epoch0,
                            P.sinfo, P.stickets + ticket, wait_bias, count, P.flag_stride);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2544,9 +2571,9 @@ void launch_solve_one(const DevicePattern& P, const double* L, double* x, int nr
 #define PARSY_ONE_LAUNCH(NQ)                                                                                               \
     hipLaunchKernelGGL(k_solve_one<NQ>, dim3(O.nblocks), dim3(kThreads), 0, stream, O.sn, O.slot0, O.pull_ptr, O.pull_slot, \
                        O.pull_pos, L, x, nrhs, ldx, O.nslots, y, y_next, state, state_next, wait_bias, cap)
-    if (nrhs == 1) PARSY_ONE_LAUNCH(1);
-    else if (nrhs <= 4) PARSY_ONE_LAUNCH(4);
-    else PARSY_ONE_LAUNCH(8);
+    if (nrhs == 1) { witness_launch(kWSolveOne1); PARSY_ONE_LAUNCH(1); }
+    else if (nrhs <= 4) { witness_launch(kWSolveOne4); PARSY_ONE_LAUNCH(4); }
+    else { witness_launch(kWSolveOne8); PARSY_ONE_LAUNCH(8); }
 #undef PARSY_ONE_LAUNCH
 }
 
@@ -2838,9 +2865,9 @@ void launch_bsolve_one(const DevicePattern& P, int n, const double* L, double* x
 #define PARSY_ONE_LAUNCH(NQ)                                                                                              \
     hipLaunchKernelGGL(k_bsolve_one<NQ>, dim3(O.nblocks), dim3(kThreads), 0, stream, O.sn, P.rows, O.wleft, L, x, nrhs,    \
                        ldx, n, O.nblocks, y, y_next, state, state_next, wait_bias, cap)
-    if (nrhs == 1) PARSY_ONE_LAUNCH(1);
-    else if (nrhs <= 4) PARSY_ONE_LAUNCH(4);
-    else PARSY_ONE_LAUNCH(8);
+    if (nrhs == 1) { witness_launch(kWBsolveOne1); PARSY_ONE_LAUNCH(1); }
+    else if (nrhs <= 4) { witness_launch(kWBsolveOne4); PARSY_ONE_LAUNCH(4); }
+    else { witness_launch(kWBsolveOne8); PARSY_ONE_LAUNCH(8); }
 #undef PARSY_ONE_LAUNCH
 }
 
@@ -3812,6 +3839,7 @@ __global__ __launch_bounds__(kThreads) void k_bsolve_below(const SnDesc* __restr
 
 void launch_bsolve_below(const DevicePattern& P, int first, int count, const double* L, const double* x, hipStream_t stream) {
     if (count <= 0) return;
+    witness_launch(kWBsolveBelow);
     hipLaunchKernelGGL(k_bsolve_below, dim3(count), dim3(kThreads), 0, stream, P.sn, P.bsolve_below + first, P.rows, L, x,
                        P.bpart);
 }
@@ -4030,6 +4058,7 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_bsolve_chain_w(const SnDes
 void launch_bsolve_chain_w(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
                            double* x, double* xscratch, int ticket, int wait_bias, hipStream_t stream) {
     if (count <= 0) return;
+    witness_launch(kWBsolveChainW);
     hipLaunchKernelGGL(k_bsolve_chain_w, dim3(count), dim3(kChainThreads), 0, stream, P.sn, P.bsolve_pairs + first,
                        P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias, P.bpart);
 }
@@ -4043,63 +4072,69 @@ void launch_bsolve_block(const DevicePattern& P, int first, int count, const dou
     const int chain = mode == 1;
     const PanelDesc* pds = mode == 2 ? P.bsolve_blocks : P.bsolve_blocks + first;
     const int32_t* ranges = mode == 2 ? P.bsolve_ranges + 2 * first : nullptr;
-    if (tiny == 1 && nrhs >= bmrhs_min()) {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
+    const SolveGates& G = P.gates;
+    if (tiny == 1 && nrhs >= G.bmrhs_min) {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
         const dim3 grid(count, std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM));
+        witness_launch(kWBsolveTinyMrhs);
         hipLaunchKernelGGL(k_bsolve_tiny_mrhs, grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L, x, nrhs, ldx);
         return;
     }
-    if (tiny && nrhs < bmrhs_min()) {   // width class kTinyWidth (1) or kTinyWidth2 (2), a subtree launch or a level's launch: one wave each
+    if (tiny && nrhs < G.bmrhs_min) {   // width class kTinyWidth (1) or kTinyWidth2 (2), a subtree launch or a level's launch: one wave each
         const dim3 grid(count, std::min(kPassLanes, nrhs));
-        if (tiny == 1)
+        static_assert(kTinyWidth == 16 && kTinyWidth2 == 32, "witness entries k_bsolve_tiny<16>, <32>");
+        if (tiny == 1) {
+            witness_launch(kWBsolveTiny16);
             hipLaunchKernelGGL(k_bsolve_tiny<kTinyWidth>, grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L, x, nrhs,
                                ldx);
-        else
+        } else {
+            witness_launch(kWBsolveTiny32);
             hipLaunchKernelGGL(k_bsolve_tiny<kTinyWidth2>, grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L, x, nrhs,
                                ldx);
+        }
         return;
     }
     // launches of few blocks (the top of the tree, small inputs: a chain of hand-offs, not a stream of L) keep the
     // light kernel -- 4 right-hand sides per workgroup, up to 8 workgroups per block side by side (nd24k-class, 16
     // right-hand sides: 1.02 ms against 2.06 with the kernel below everywhere)
-    static const bool wide_only = [] {
-        const char* e = std::getenv("PARSY_BMRHS_WIDE_ONLY");
-        return !(e && e[0] == '0');
-    }();
-    // (round 5) chain launches of more than 16 right-hand sides: k_bsolve_chain_mrhs from kBChainMinBlocks block columns on
-    // (PARSY_BCHAIN_MIN_BLOCKS), 64 right-hand sides per pass
-    static const int bchain_min = [] {
-        const char* e = std::getenv("PARSY_BCHAIN_MIN_BLOCKS");
-        return e && *e ? std::atoi(e) : kBChainMinBlocks;
-    }();
-    if (chain && nrhs > 16 && nrhs >= bmrhs_min() && count >= bchain_min) {
+    // (G.bmrhs_wide_only; PARSY_BMRHS_WIDE_ONLY=0: the kernel below everywhere)
+    // (round 5) chain launches of more than 16 right-hand sides: k_bsolve_chain_mrhs from G.bchain_min_blocks (128) block
+    // columns on (PARSY_BCHAIN_MIN_BLOCKS), 64 right-hand sides per pass
+    if (chain && nrhs > 16 && nrhs >= G.bmrhs_min && count >= G.bchain_min_blocks) {
         const int mlanes = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
+        witness_launch(kWBsolveChainMrhs);
         hipLaunchKernelGGL(k_bsolve_chain_mrhs, dim3(count * mlanes), dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x, xscratch, nrhs,
                            ldx, P.sinfo, P.stickets + ticket, wait_bias, count, dinv);
         return;
     }
-    if (nrhs >= bmrhs_min() && (!wide_only || count >= kMrhsWideBlocks)) {   // 64 right-hand sides per pass over L, products on the matrix cores
+    if (nrhs >= G.bmrhs_min && (!G.bmrhs_wide_only || count >= kMrhsWideBlocks)) {   // 64 right-hand sides per pass over L, products on the matrix cores
         // launches of few blocks (the top of the tree, small inputs) take 16 right-hand sides per pass in up to 8
         // workgroups per block side by side; the others 64 per pass (L read once per 64)
         const bool wide = count >= kMrhsWideBlocks && nrhs > 16;
         const int per = wide ? kRhsM : 16;
         const int mlanes = std::min(kPassLanes, (nrhs + per - 1) / per);
         const dim3 mgrid = chain ? dim3(count * mlanes) : dim3(count, mlanes);
-        if (wide)
+        if (wide) {
+            witness_launch(kWBsolveBlockMrhs4);
             hipLaunchKernelGGL(k_bsolve_block_mrhs<4>, mgrid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x, xscratch,
                                nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
-        else
+        } else {
+            witness_launch(kWBsolveBlockMrhs1);
             hipLaunchKernelGGL(k_bsolve_block_mrhs<1>, mgrid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x, xscratch,
                                nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+        }
         return;
     }
     const int lanes = nrhs == 1 ? 1 : std::min(kPassLanes, (nrhs + 3) / 4);
     const dim3 grid = chain ? dim3(count * lanes) : dim3(count, lanes);
-    if (nrhs == 1)
+    if (nrhs == 1) {
+        witness_launch(kWBsolveBlock1);
         hipLaunchKernelGGL(k_bsolve_block<1>, grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x, xscratch,
                            nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
-    else
+    } else {
+        witness_launch(kWBsolveBlock4);
         hipLaunchKernelGGL(k_bsolve_block<4>, grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x, xscratch,
                            nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+    }
 }
 
 // SOLVE_FIXUP: solved blocks of the wide supernodes go from scratch into x.
@@ -4117,6 +4152,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_fixup(const SnDesc* __restri
 void launch_solve_fixup(const DevicePattern& P, int first, int count, double* x,
                         const double* xscratch, int nrhs, int ldx, hipStream_t stream) {
     if (count <= 0) return;
+    witness_launch(kWSolveFixup);
     hipLaunchKernelGGL(k_solve_fixup, dim3(count, min(nrhs, 64)), dim3(kThreads), 0, stream, P.sn,
                        P.solve_fix_list + first, x, xscratch, nrhs, ldx);
 }
@@ -4149,6 +4185,7 @@ void launch_rhs_ones(const DevicePattern& P, int nsuper, int max_rows, const dou
                      hipStream_t stream) {
     if (nsuper <= 0) return;
     const int ny = std::max(1, std::min(16, (max_rows + kThreads - 1) / kThreads));
+    witness_launch(kWRhsOnes);
     hipLaunchKernelGGL(k_rhs_ones, dim3(nsuper, ny), dim3(kThreads), 0, stream, P.sn, P.rows, L, b);
 }
 
@@ -4171,7 +4208,20 @@ void launch_copy_segments(double* dst, const double* src, const int64_t* dst_off
                           const int32_t* len, int64_t nseg, hipStream_t stream) {
     if (nseg <= 0) return;
     const unsigned grid = (unsigned)std::min<int64_t>(nseg, 1 << 20);
+    witness_launch(kWCopySegments);
     hipLaunchKernelGGL(k_copy_segments, dim3(grid), dim3(64), 0, stream, dst, src, dst_off, src_off, len, nseg);
 }
 
 }  // namespace parsy
+
+// Kernel witness (include/parsy_amd.h, diagnostics)
+extern "C" int parsy_debug_kernel_count(void) { return parsy::kWitnessCount; }
+extern "C" const char* parsy_debug_kernel_name(int k) {
+    return k >= 0 && k < parsy::kWitnessCount ? parsy::kWitnessNames[k] : nullptr;
+}
+extern "C" unsigned long long parsy_debug_kernel_launches(int k) {
+    return k >= 0 && k < parsy::kWitnessCount ? parsy::g_witness[k].load(std::memory_order_relaxed) : 0ull;
+}
+extern "C" void parsy_debug_kernel_reset(void) {
+    for (auto& c : parsy::g_witness) c.store(0, std::memory_order_relaxed);
+}

@@ -475,11 +475,6 @@ __global__ __launch_bounds__(256) void k_bsolve_sub_mrhs(const SubMember* __rest
     }
 }
 
-int solve_sub_mrhs_min() {   // (read per solve: the tests switch between the two forms of the subtree launch)
-    const char* e = std::getenv("PARSY_SUB_MRHS_MIN");
-    return e && *e ? std::atoi(e) : 6;
-}
-
 static int sub_abl() {
     const char* e = std::getenv("PARSY_SUB_ABL");
     return e && *e ? std::atoi(e) : 0;
@@ -506,6 +501,7 @@ void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doubl
     size_t lds;
     sub_grid(T, nrhs, ngroups, grid, block, per_wave, lds);
     const bool tr = ldq > 0;
+    witness_launch(kWSolveSubMrhs);
     hipLaunchKernelGGL(k_solve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
                        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs,
                        (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, sub_abl());
@@ -518,6 +514,7 @@ void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doub
     dim3 grid, block;
     size_t lds;
     sub_grid(T, nrhs, ngroups, grid, block, per_wave, lds);
+    witness_launch(kWBsolveSubMrhs);
     hipLaunchKernelGGL(k_bsolve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
                        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs, 1u,
                        (int64_t)ldx, sub_abl());

@@ -18,6 +18,11 @@ RESID_TOL = 1e-10
 SOLVE_TOL = 1e-10
 
 
+def _launched(seen):
+    """The kernels a witness dict saw (for assertion messages)."""
+    return {k: v for k, v in seen.items() if v}
+
+
 def _factor_both(api, oracle, name):
     from parsy_bench_amd import inspector as I
     A, perm, sym = problem(name)
@@ -167,15 +172,22 @@ def test_product_gate_with_row_major_x_forced(api, oracle, monkeypatch, name, nr
 @pytest.mark.parametrize("nrhs", [3, 19])
 def test_solve_flag_protocol_chain_matches_oracle(api, oracle, monkeypatch, nrhs):
     """PARSY_OLD_MRHS_CHAIN=1: the chain launches of rounds 1-2 (flags + staged copies per block column; 8 right-hand
-    sides per pass below 16) stay available as a fallback and stay correct."""
+    sides per pass below 16) stay available as a fallback and stay correct.  The witness proves which ran: below
+    PARSY_MRHS_MIN=16 k_solve_chain<8>, from there on k_solve_chain_mrhs, never the armed-buffer chain."""
     monkeypatch.setenv("PARSY_OLD_MRHS_CHAIN", "1")
     monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
     monkeypatch.setenv("PARSY_MRHS_MIN", "16")
     A, sym, plan, lv, lo = _factor_both(api, oracle, "lap30")
     rng = np.random.default_rng(2)
     B = rng.standard_normal((sym.n, nrhs))
+    api.reset_kernel_launches()
     X, _ = plan.solve(lo, B)
     assert plan.solve_status() == 0
+    seen = api.kernel_launches()
+    assert seen["k_solve_chain<8>" if nrhs < 16 else "k_solve_chain_mrhs"] > 0, _launched(seen)
+    assert seen["k_solve_blocks_mrhs<true>"] == seen["k_solve_blocks_mrhs<false>"] == seen["k_solve_arm_wide"] == 0
+    if nrhs < 16:   # (the narrow supernodes: the 8-per-pass kernels below the threshold as well)
+        assert seen["k_solve_small"] > 0 and not any(seen[f"k_solve_small_mrhs<{w}>"] for w in (16, 32, 64)), _launched(seen)
     for q in range(nrhs):
         xo = oracle.blocked_lsolve(sym, lo, B[:, q], "serial")
         assert np.abs(X[:, q] - xo).max() <= SOLVE_TOL * max(1.0, np.abs(xo).max())
@@ -986,12 +998,16 @@ def test_solve_timeout_is_reported_not_returned_as_success(api, oracle, monkeypa
     api.dropin_reset()
 
 
-@pytest.mark.parametrize("nrhs", [8, 40])
+@pytest.mark.parametrize("nrhs", [8, 40, 64])
 def test_many_rhs_solve_timeout_is_reported(api, oracle, monkeypatch, nrhs):
     """The same with many right-hand sides: the block-column tasks of k_solve_blocks_mrhs (8: the waves share one group's
     rows and leave together behind a barrier; 40: a wave per group) and the backward chain kernels run into their bounded
-    waits, the solve reports -1 instead of hanging or returning a wrong x, and the next solve is clean."""
+    waits, the solve reports -1 instead of hanging or returning a wrong x, and the next solve is clean.  64: the backward
+    chain launches are k_bsolve_chain_mrhs (PARSY_BCHAIN_MIN_BLOCKS=1), and the witness shows that it is the one that timed out."""
     monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
+    chain_mrhs = nrhs == 64
+    if chain_mrhs:
+        monkeypatch.setenv("PARSY_BCHAIN_MIN_BLOCKS", "1")
     A, perm, sym = problem("lap30")
     plan = api.Plan(sym, 0)
     lv, _ = plan.factor(sym.A2x)
@@ -1004,14 +1020,22 @@ def test_many_rhs_solve_timeout_is_reported(api, oracle, monkeypatch, nrhs):
     with pytest.raises(RuntimeError, match="timed out"):
         plan.solve(lv, B)
     assert plan.solve_status() == -1
+    api.reset_kernel_launches()
     with pytest.raises(RuntimeError, match="timed out"):
         plan.solve2(lv, B, forward=False)
+    assert plan.solve_status() == -1
+    if chain_mrhs:
+        seen = api.kernel_launches()
+        assert seen["k_bsolve_chain_mrhs"] > 0, _launched(seen)
     monkeypatch.delenv("PARSY_DEBUG_SOLVE_STALL")
     X2, _ = plan.solve(lv, B)
-    assert plan.solve_status() == 0 and np.array_equal(X2, X) or np.abs(X2 - X).max() <= 1e-12 * max(1.0, np.abs(X).max())
+    assert plan.solve_status() == 0
+    assert np.array_equal(X2, X) or np.abs(X2 - X).max() <= 1e-12 * max(1.0, np.abs(X).max())
+    api.reset_kernel_launches()
     Xb, _ = plan.solve2(lv, B, forward=False)
     assert plan.solve_status() == 0
-    for q in (0, nrhs - 1):
+    assert api.kernel_launches()["k_bsolve_chain_mrhs"] > 0 or not chain_mrhs
+    for q in range(nrhs):
         xb = oracle.blocked_ltsolve(sym, lv, B[:, q])
         assert np.abs(Xb[:, q] - xb).max() <= SOLVE_TOL * max(1.0, np.abs(xb).max())
 
@@ -1292,3 +1316,258 @@ def test_subtree_launches_report_a_bad_pivot(api, oracle, monkeypatch):
     lv, _ = plan.factor(vals)
     ok, lo, bad = oracle.cholesky_05(sym, vals, I.trivial_hlevel(sym))
     assert not ok and plan.status() == col + 1
+
+
+# ---------------------------------------------------------------------------
+# every gated variant of the solves reached and proven (the kernel witness: api.kernel_launches() counts the launches
+# enqueued per kernel instantiation; the gates are read at the start of every solve, so a test sets them per solve)
+# ---------------------------------------------------------------------------
+def _plan_and_factor(api, name):
+    A, perm, sym = problem(name)
+    plan = api.Plan(sym, 0)
+    lv, _ = plan.factor(sym.A2x)
+    assert plan.status() == 0
+    return sym, plan, lv
+
+
+def _oracle_cols(oracle, sym, lv, B, forward):
+    return np.stack([oracle.blocked_lsolve(sym, lv, B[:, q], "serial") if forward else oracle.blocked_ltsolve(sym, lv, B[:, q])
+                     for q in range(B.shape[1])], axis=1)
+
+
+def _check_cols(X, ref, what):
+    for q in range(ref.shape[1]):
+        assert np.abs(X[:, q] - ref[:, q]).max() <= SOLVE_TOL * max(1.0, np.abs(ref[:, q]).max()), f"{what}: column {q}"
+
+
+def _same(X, X0, what):
+    assert np.abs(X - X0).max() <= 1e-12 * max(1.0, np.abs(X0).max()), what
+
+
+# middle values of PARSY_BCHAIN_MIN_BLOCKS: some of the backward chain launches of the input have at least this many block
+# columns (k_bsolve_chain_mrhs), the others fewer (with PARSY_BMRHS_WIDE_ONLY=0: k_bsolve_block_mrhs) -- both in one solve
+_BCHAIN_MID = {"lap30": "16", "mid3d": "9", "nd24k": "50"}
+
+
+@pytest.mark.parametrize("name,nrhs", [(name, nrhs) for name in ("lap30", "mid3d", "nd24k")
+                                       for nrhs in (17, 19, 33, 64, 65, 70, 130)] + [("mid3d", 520)])
+def test_backward_chain_many_rhs_matches_oracle(api, oracle, monkeypatch, name, nrhs):
+    """k_bsolve_chain_mrhs (backward chain launches of more than 16 right-hand sides, 64 per pass, by default from 128 block
+    columns on -- more than any of these inputs has) forced on every chain launch (PARSY_BCHAIN_MIN_BLOCKS=1) and on some of
+    them beside k_bsolve_block_mrhs on the others: right-hand-side counts around 16, 32, 64, 128 and above 8 passes of 64
+    (520: the pass loop), every column against the checker and equal to the default kernels' result to 1e-12."""
+    monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
+    sym, plan, lv = _plan_and_factor(api, name)
+    B = np.random.default_rng(100 + nrhs).standard_normal((sym.n, nrhs))
+    ref = _oracle_cols(oracle, sym, lv, B, False)
+    api.reset_kernel_launches()
+    X0, _ = plan.solve2(lv, B, forward=False)
+    assert plan.solve_status() == 0
+    assert api.kernel_launches()["k_bsolve_chain_mrhs"] == 0   # (the default gate: no launch of these inputs is that wide)
+    _check_cols(X0, ref, f"{name} default gates")
+    for env, want in (({"PARSY_BCHAIN_MIN_BLOCKS": "1"}, ("k_bsolve_chain_mrhs",)),
+                      ({"PARSY_BCHAIN_MIN_BLOCKS": _BCHAIN_MID[name], "PARSY_BMRHS_WIDE_ONLY": "0"},
+                       ("k_bsolve_chain_mrhs", "k_bsolve_block_mrhs<1>"))):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        api.reset_kernel_launches()
+        X, _ = plan.solve2(lv, B, forward=False)
+        assert plan.solve_status() == 0
+        seen = api.kernel_launches()
+        assert all(seen[k] > 0 for k in want), (env, _launched(seen))
+        _check_cols(X, ref, f"{name} {env}")
+        _same(X, X0, f"{name} {env} against the default gates")
+        for k in env:
+            monkeypatch.delenv(k)
+
+
+def test_backward_chain_many_rhs_default_gate(api, oracle, monkeypatch):
+    """With no variable set the parabolic_fem-class plan's widest backward chain launch (128 block columns) takes
+    k_bsolve_chain_mrhs at 64 right-hand sides: every column against the checker."""
+    for k in ("PARSY_SOLVE_ONE", "PARSY_BCHAIN_MIN_BLOCKS", "PARSY_BMRHS_MIN", "PARSY_BMRHS_WIDE_ONLY", "PARSY_MRHS_MIN"):
+        monkeypatch.delenv(k, raising=False)
+    sym, plan, lv = _plan_and_factor(api, "parabolic_fem")
+    B = np.random.default_rng(64).standard_normal((sym.n, 64))
+    api.reset_kernel_launches()
+    X, _ = plan.solve2(lv, B, forward=False)
+    assert plan.solve_status() == 0
+    seen = api.kernel_launches()
+    assert seen["k_bsolve_chain_mrhs"] > 0, _launched(seen)
+    _check_cols(X, _oracle_cols(oracle, sym, lv, B, False), "parabolic_fem backward, 64")
+
+
+@pytest.mark.parametrize("name", ["lap30", "nd24k"])
+@pytest.mark.parametrize("xt", ["0", "6"])
+@pytest.mark.parametrize("nrhs", [33, 40, 48, 64, 70, 100, 128])
+def test_forward_small_mrhs_in_halves_matches_oracle(api, oracle, monkeypatch, name, xt, nrhs):
+    """k_solve_small_mrhs<64, true> sweeps the right-hand sides of a pass in two halves (by default for launches of at least
+    512 supernodes, which these inputs do not have): forced with PARSY_SMALL_MRHS_HALVES_MIN=1 on their launches of
+    supernodes 33-64 wide, both layouts of X, against the oracle and the one-sweep kernel's result."""
+    monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
+    monkeypatch.setenv("PARSY_XT_MIN", xt)
+    sym, plan, lv = _plan_and_factor(api, name)
+    B = np.random.default_rng(200 + nrhs).standard_normal((sym.n, nrhs))
+    api.reset_kernel_launches()
+    X0, _ = plan.solve(lv, B)
+    assert plan.solve_status() == 0
+    seen = api.kernel_launches()
+    assert seen["k_solve_small_mrhs<64>"] > 0 and seen["k_solve_small_mrhs<64,true>"] == 0, _launched(seen)
+    assert (seen["k_transpose_x"] > 0) == (xt == "6")
+    monkeypatch.setenv("PARSY_SMALL_MRHS_HALVES_MIN", "1")
+    api.reset_kernel_launches()
+    X, _ = plan.solve(lv, B)
+    assert plan.solve_status() == 0
+    seen = api.kernel_launches()
+    assert seen["k_solve_small_mrhs<64,true>"] > 0 and seen["k_solve_small_mrhs<64>"] == 0, _launched(seen)
+    _check_cols(X, _oracle_cols(oracle, sym, lv, B, True), f"{name} halves")
+    _same(X, X0, f"{name}: halves against one sweep")
+
+
+_SENTINEL = 1234.5678125   # (finite: the armed pattern is a NaN)
+
+
+@pytest.mark.parametrize("one", ["default", "0"])
+@pytest.mark.parametrize("nrhs", [1, 3, 8, 16, 19, 64, 70])
+def test_padded_leading_dimension(api, oracle, monkeypatch, one, nrhs):
+    """X with ldx = n + 37 on device buffers through parsy_solve_device, parsy_backsolve_device and parsy_solve_levels_device
+    (both directions): the rows n .. ldx - 1 of every column and a tail past the last column hold a sentinel that must come
+    back bit for bit; the values match the oracle."""
+    import torch
+    if one == "0":
+        monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
+    else:
+        monkeypatch.delenv("PARSY_SOLVE_ONE", raising=False)
+    sym, plan, lv = _plan_and_factor(api, "lap30")
+    n, ldx, tail = sym.n, sym.n + 37, 53
+    dev = torch.device("cuda", 0)
+    Ld = torch.from_numpy(lv).to(dev)
+    B = np.random.default_rng(300 + nrhs).standard_normal((n, nrhs))
+    ref = {fwd: _oracle_cols(oracle, sym, lv, B, fwd) for fwd in (True, False)}
+    nl = int(plan.solve_levels().max()) + 1
+    for how in ("solve_device", "backsolve_device", "levels_forward", "levels_backward"):
+        fwd = how in ("solve_device", "levels_forward")
+        buf = np.full(ldx * nrhs + tail, _SENTINEL)
+        buf[:ldx * nrhs].reshape(nrhs, ldx)[:, :n] = B.T
+        Xd = torch.from_numpy(buf.copy()).to(dev)
+        if how == "solve_device":
+            plan.solve_device(Ld.data_ptr(), Xd.data_ptr(), nrhs, ldx)
+        elif how == "backsolve_device":
+            plan.backsolve_device(Ld.data_ptr(), Xd.data_ptr(), nrhs, ldx)
+        else:
+            order = [(l, l + 1) for l in range(nl)]
+            if not fwd:
+                order = order[::-1]
+            for i, (a, b) in enumerate(order):
+                plan.solve_levels_device(Ld.data_ptr(), Xd.data_ptr(), nrhs, ldx, 0, a, b, i == 0, i == len(order) - 1, not fwd)
+        torch.cuda.synchronize()
+        assert plan.solve_status() == 0, how
+        out = Xd.cpu().numpy()
+        body = out[:ldx * nrhs].reshape(nrhs, ldx)
+        assert np.array_equal(body[:, n:].view(np.uint64), np.full((nrhs, ldx - n), _SENTINEL).view(np.uint64)), \
+            f"{how}: the padding rows of X were written"
+        assert np.array_equal(out[ldx * nrhs:].view(np.uint64), np.full(tail, _SENTINEL).view(np.uint64)), \
+            f"{how}: written past the last column"
+        _check_cols(body[:, :n].T, ref[fwd], how)
+
+
+@pytest.mark.parametrize("name", ["lap30", "nd24k"])
+def test_one_rhs_under_mrhs_min_1(api, oracle, monkeypatch, name):
+    """PARSY_MRHS_MIN=1: one right-hand side takes the many-right-hand-side kernels of the forward solve (k_solve_small_mrhs,
+    k_solve_blocks_mrhs on the armed buffer), so its prologue must be theirs: k_solve_arm_wide zeroes the status word and
+    the chain tickets that an earlier solve left behind.  Repeated solves of both directions against the oracle."""
+    monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
+    sym, plan, lv = _plan_and_factor(api, name)
+    B = np.random.default_rng(400).standard_normal((sym.n, 1))
+    ref = {fwd: _oracle_cols(oracle, sym, lv, B, fwd) for fwd in (True, False)}
+    X, _ = plan.solve(lv, B)   # (the default kernels first: their tickets are left behind)
+    assert plan.solve_status() == 0
+    _check_cols(X, ref[True], f"{name}: default gates")
+    monkeypatch.setenv("PARSY_MRHS_MIN", "1")
+    for rep in range(2):
+        api.reset_kernel_launches()
+        X, _ = plan.solve(lv, B)
+        assert plan.solve_status() == 0
+        seen = api.kernel_launches()
+        assert seen["k_solve_arm_wide"] == 1 and seen["k_solve_blocks_mrhs<true>"] > 0, _launched(seen)
+        assert seen["k_solve_small_mrhs<64,true>"] > 0, _launched(seen)
+        assert seen["k_solve_chain_w<2>"] == seen["k_solve_chain_w<4>"] == seen["k_solve_tiny<16>"] == seen["k_solve_small"] == 0
+        _check_cols(X, ref[True], f"{name}: forward, PARSY_MRHS_MIN=1, solve {rep}")
+        Xb, _ = plan.solve2(lv, B, forward=False)
+        assert plan.solve_status() == 0
+        _check_cols(Xb, ref[False], f"{name}: backward, PARSY_MRHS_MIN=1, solve {rep}")
+
+
+# The coverage matrix: (input, variables, right-hand sides, forward) -> the kernels that cell must launch.  Together the
+# cells launch every entry of the witness table but _NOT_COVERED.
+_COVERAGE = [
+    ("lap30", {"PARSY_SOLVE_ONE": "0"}, 1, True, ["k_solve_tiny<16>", "k_solve_small", "k_solve_chain_w<2>", "k_diag_inverse"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0"}, 1, False, ["k_bsolve_chain_w", "k_bsolve_below", "k_bsolve_block<1>", "k_bsolve_tiny<16>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0"}, 8, True, ["k_solve_small_mrhs<16>", "k_solve_small_mrhs<64,true>",
+                                                   "k_solve_blocks_mrhs<true>", "k_solve_arm_wide"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0"}, 3, False, ["k_bsolve_block<4>", "k_solve_arm_wide"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_XT_MIN": "6"}, 64, True, ["k_solve_small_mrhs<64>", "k_solve_blocks_mrhs<false>",
+                                                                        "k_transpose_x"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_BCHAIN_MIN_BLOCKS": "16", "PARSY_BMRHS_WIDE_ONLY": "0"}, 19, False,
+     ["k_bsolve_chain_mrhs", "k_bsolve_block_mrhs<1>", "k_bsolve_tiny_mrhs"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_SMALL_MRHS_HALVES_MIN": "1"}, 70, True, ["k_solve_small_mrhs<64,true>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_OLD_MRHS_CHAIN": "1", "PARSY_MRHS_MIN": "16"}, 3, True, ["k_solve_chain<8>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_OLD_MRHS_CHAIN": "1"}, 19, True, ["k_solve_chain_mrhs"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 1, True, ["k_solve_one<1>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 3, True, ["k_solve_one<4>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 8, True, ["k_solve_one<8>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 1, False, ["k_bsolve_one<1>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 3, False, ["k_bsolve_one<4>"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "2"}, 8, False, ["k_bsolve_one<8>"]),
+    ("mid3d", {"PARSY_SOLVE_ONE": "0"}, 8, True, ["k_solve_small_mrhs<32>"]),
+    ("mid3d", {"PARSY_SOLVE_ONE": "0"}, 3, False, ["k_bsolve_tiny<32>"]),
+    ("mid3d", {"PARSY_SOLVE_ONE": "0", "PARSY_FORCE_UNFUSED": "1"}, 3, True, ["k_solve_panel", "k_solve_fixup"]),
+    ("nd24k", {"PARSY_SOLVE_ONE": "0"}, 19, True, ["k_solve_sub_mrhs"]),
+    ("nd24k", {"PARSY_SOLVE_ONE": "0"}, 19, False, ["k_bsolve_sub_mrhs"]),
+    ("nd24k", {"PARSY_SOLVE_ONE": "0", "PARSY_SUB_MRHS_MIN": "0"}, 19, False, ["k_bsolve_block_mrhs<4>"]),
+]
+_NOT_COVERED = {
+    "k_solve_chain_w<4>": "one right-hand side through a forward chain launch of more than 384 chunks: Flan-class plans only",
+    "k_copy_segments": "the multi-device exchange's copy, not a solve: bitwise in test_copy_segments_device_packs_and_unpacks",
+}
+_PLAN_VARIABLES = ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED")   # (read when the plan is made; the others per solve)
+
+
+def test_every_solve_kernel_is_reached(api, oracle, monkeypatch):
+    """Every cell of _COVERAGE against the oracle / the checker (every column) and its witness; the union of the cells'
+    launches covers the witness table but the listed exclusions.  PARSY_OLD_MRHS_CHAIN=1 reaches the flag-protocol kernels;
+    parsy_rhs_ones_device is k_rhs_ones (against the oracle's rhs_init_blocked)."""
+    import torch
+    union = {}
+    plans = {}
+    for name, env, nrhs, fwd, want in _COVERAGE:
+        for k in ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED", "PARSY_XT_MIN", "PARSY_BCHAIN_MIN_BLOCKS", "PARSY_BMRHS_WIDE_ONLY",
+                  "PARSY_SMALL_MRHS_HALVES_MIN", "PARSY_OLD_MRHS_CHAIN", "PARSY_MRHS_MIN", "PARSY_SUB_MRHS_MIN"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        key = (name, tuple(sorted((k, v) for k, v in env.items() if k in _PLAN_VARIABLES)))
+        if key not in plans:
+            plans[key] = _plan_and_factor(api, name)
+        sym, plan, lv = plans[key]
+        B = np.random.default_rng(500 + nrhs).standard_normal((sym.n, nrhs))
+        api.reset_kernel_launches()
+        X, _ = plan.solve(lv, B) if fwd else plan.solve2(lv, B, forward=False)
+        assert plan.solve_status() == 0
+        seen = api.kernel_launches()
+        cell = (name, env, nrhs, "forward" if fwd else "backward")
+        assert all(seen[k] > 0 for k in want), (cell, _launched(seen))
+        _check_cols(X, _oracle_cols(oracle, sym, lv, B, fwd), str(cell))
+        for k, v in seen.items():
+            union[k] = union.get(k, 0) + v
+    sym, plan, lv = plans[("lap30", (("PARSY_SOLVE_ONE", "0"),))]
+    api.reset_kernel_launches()
+    dev = torch.device("cuda", 0)
+    Ld, bd = torch.from_numpy(lv).to(dev), torch.zeros(sym.n, dtype=torch.float64, device=dev)
+    plan.rhs_ones_device(Ld.data_ptr(), bd.data_ptr())
+    torch.cuda.synchronize()
+    bo = oracle.rhs_init_blocked(sym, lv)
+    assert np.abs(bd.cpu().numpy() - bo).max() <= 1e-12 * max(1.0, np.abs(bo).max())
+    union["k_rhs_ones"] = union.get("k_rhs_ones", 0) + api.kernel_launches()["k_rhs_ones"]
+    assert set(_NOT_COVERED) <= set(union), "an exclusion names no entry of the witness table"
+    missing = sorted(k for k, v in union.items() if v == 0 and k not in _NOT_COVERED)
+    assert not missing, f"solve kernels no cell reached: {missing}"
