@@ -300,6 +300,33 @@ int parsy_copy_segments_device(double* d_dst, const double* d_src, const int64_t
 int parsy_solve2_host(parsy_plan* plan, const double* lValues, double* x, int nrhs, int ldx,
                       int forward, double* seconds);
 
+/* ---- A x = b in the caller's ordering: residuals, backward errors, iterative refinement ---------------
+ * The plan holds P A P' (A2 order, lower triangle); these calls take and return vectors in the caller's ordering
+ * and refine with LAPACK dporfs's loop, column by column: r = Pb - A z, berr = max_i |r_i| / (|A||z| + |Pb|)_i
+ * (with dporfs's safe1 / safe2 guards), then z += (L L')^-1 r while berr > 2^-53, berr halved at least, and fewer
+ * than max_steps steps were taken.  The residual is FP64 and bitwise reproducible.  The values may differ from the
+ * values that were factored (a stale factor of nearby values): refinement then stops on the halving test.  Refused:
+ * host-only and solve-only plans, plans under parsy_plan_set_active / _set_active_pieces, an open factorization or
+ * level-stepped solve, nrhs < 1, a leading dimension < n, NULL pointers.  Return 0, or < 0 with parsy_last_error. */
+/* The ordering of the caller's A: perm[new] = old, n entries (host, copied; refused unless a permutation of 0..n-1);
+ * NULL = identity (the default: plans from parsy_plan_create already hold the permuted system). */
+int parsy_plan_set_perm(parsy_plan* plan, const int* perm);
+/* R = B - A X and the componentwise backward error of every column (device pointers, d_values in A2 order as
+ * parsy_factor_device takes them).  d_r may be NULL; berr (host, nrhs) may be NULL; a non-NULL berr synchronises
+ * `stream`. */
+int parsy_residual_device(parsy_plan* plan, const double* d_values, const double* d_x, int ldx, const double* d_b,
+                          int ldb, double* d_r, int ldr, int nrhs, double* berr, void* stream);
+/* X = A^-1 B with up to max_steps refinement steps.  d_x may equal d_b when ldx == ldb.  steps / berr: host, nrhs
+ * entries each, may be NULL; berr is the backward error of the returned X.  With max_steps > 0 the call synchronises
+ * `stream` once per step (and fails, X untouched, when a solve's hand-off wait timed out); with max_steps == 0 and
+ * both NULL it is fully asynchronous (check parsy_solve_status). */
+int parsy_solve_spd_device(parsy_plan* plan, const double* d_values, const double* d_lValues, const double* d_b,
+                           int ldb, double* d_x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr,
+                           void* stream);
+/* Host-buffer convenience (H2D, the call above, D2H); seconds = device time of the call above. */
+int parsy_solve_spd_host(parsy_plan* plan, const double* values, const double* lValues, const double* b, int ldb,
+                         double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds);
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

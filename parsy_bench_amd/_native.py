@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "parsy_mg_create", "parsy_mg_destroy", "parsy_mg_set_values", "parsy_mg_factor", "parsy_mg_rank_ms",
     "parsy_mg_gather_host", "parsy_mg_dist", "parsy_mg_plan", "parsy_mg_profile", "parsy_plan_profile_levels",
     "parsy_debug_kernel_count", "parsy_debug_kernel_name", "parsy_debug_kernel_launches", "parsy_debug_kernel_reset",
+    "parsy_plan_set_perm", "parsy_residual_device", "parsy_solve_spd_device", "parsy_solve_spd_host",
 ]
 
 
@@ -168,6 +169,10 @@ def _declare(lib):
     lib.parsy_mg_dist.argtypes = [vp]
     lib.parsy_mg_plan.restype = vp
     lib.parsy_mg_plan.argtypes = [vp, C.c_int]
+    lib.parsy_plan_set_perm.argtypes = [vp, vp]
+    lib.parsy_residual_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.parsy_solve_spd_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_solve_spd_host.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -234,6 +234,57 @@ class Plan:
         x[self.sym.Perm] = z
         return x, sec
 
+    # A x = b in the caller's ordering: residuals, backward errors, iterative refinement (dporfs) -----------
+    def set_perm(self, perm) -> None:
+        """The caller's ordering (perm[new] = old, n entries) for residual_device / solve_spd_device; None: identity."""
+        p = None if perm is None else _i32(perm)
+        if p is not None and p.size != self.sym.n:
+            raise ValueError(f"set_perm: perm has {p.size} entries, the plan has n = {self.sym.n}")
+        if N.lib().parsy_plan_set_perm(self._h, N.ptr(p)) != 0:
+            raise RuntimeError(N.last_error())
+
+    def residual_device(self, d_values: int, d_x: int, ldx: int, d_b: int, ldb: int, nrhs: int, d_r: int = 0,
+                        ldr: int = 0, stream: int = 0) -> np.ndarray:
+        """R = B - A X (d_r: 0 for none) and the componentwise backward error of every column (returned)."""
+        berr = np.zeros(nrhs, dtype=np.float64)
+        if N.lib().parsy_residual_device(self._h, d_values, d_x, ldx, d_b, ldb, d_r or None, ldr, nrhs,
+                                         N.ptr(berr), stream) != 0:
+            raise RuntimeError("parsy_residual_device failed: " + N.last_error())
+        return berr
+
+    def solve_spd_device(self, d_values: int, d_lValues: int, d_b: int, ldb: int, d_x: int, ldx: int, nrhs: int,
+                         max_steps: int = 5, stream: int = 0):
+        """X = A^-1 B with up to max_steps refinement steps; returns (steps int32[nrhs], berr float64[nrhs])."""
+        steps = np.zeros(nrhs, dtype=np.int32)
+        berr = np.zeros(nrhs, dtype=np.float64)
+        if N.lib().parsy_solve_spd_device(self._h, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps,
+                                          N.ptr(steps), N.ptr(berr), stream) != 0:
+            raise RuntimeError("parsy_solve_spd_device failed: " + N.last_error())
+        return steps, berr
+
+    def solve_refined(self, values, lValues, b, max_steps: int = 5):
+        """x with A x = b for the ORIGINAL matrix (caller's ordering, like solve_spd), refined on the device against
+        `values` (A2 order; they may differ from the values lValues was factored from).  On first use the plan takes
+        sym.Perm as its ordering.  Returns (x, {"steps", "berr", "seconds"})."""
+        if not getattr(self, "_perm_set", False):
+            self.set_perm(self.sym.Perm)
+            self._perm_set = True
+        b = np.asarray(b, dtype=np.float64)
+        one = b.ndim == 1
+        B = np.asfortranarray(b.reshape(self.sym.n, -1))
+        nrhs = B.shape[1]
+        X = np.zeros((self.sym.n, nrhs), order="F")
+        vals, lv = _f64(values), _f64(lValues)
+        steps = np.zeros(nrhs, dtype=np.int32)
+        berr = np.zeros(nrhs, dtype=np.float64)
+        sec = C.c_double(0)
+        if N.lib().parsy_solve_spd_host(self._h, N.ptr(vals), N.ptr(lv), B.ctypes.data_as(C.c_void_p), self.sym.n,
+                                        X.ctypes.data_as(C.c_void_p), self.sym.n, nrhs, max_steps, N.ptr(steps),
+                                        N.ptr(berr), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_solve_spd_host failed: " + N.last_error())
+        x = X[:, 0].copy() if one else np.ascontiguousarray(X)
+        return x, {"steps": steps, "berr": berr, "seconds": sec.value}
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

@@ -18,6 +18,7 @@
 #include "dist.hpp"
 #include "executor.hpp"
 #include "inspector.hpp"
+#include "refine.hpp"
 
 using parsy::set_last_error;
 
@@ -887,6 +888,88 @@ int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs
     sec += parsy_last_solve_ms(pl) * 1e-3;
     if (seconds) *seconds = sec;
     CAPI_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost), -1);
+    return 0;
+}
+
+int parsy_plan_set_perm(parsy_plan* pl, const int* perm) {
+    if (!pl) {
+        set_last_error("parsy_plan_set_perm: null plan");
+        return -1;
+    }
+    return parsy::plan_set_perm(pl, perm);
+}
+
+int parsy_residual_device(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
+                          double* d_r, int ldr, int nrhs, double* berr, void* stream) {
+    if (!pl || !d_values || !d_x || !d_b) {
+        set_last_error("parsy_residual_device: null argument");
+        return -1;
+    }
+    return parsy::plan_residual(pl, d_values, d_x, ldx, d_b, ldb, d_r, ldr, nrhs, berr, (hipStream_t)stream);
+}
+
+int parsy_solve_spd_device(parsy_plan* pl, const double* d_values, const double* d_lValues, const double* d_b, int ldb,
+                           double* d_x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, void* stream) {
+    if (!pl || !d_values || !d_lValues || !d_b || !d_x) {
+        set_last_error("parsy_solve_spd_device: null argument");
+        return -1;
+    }
+    return parsy::plan_solve_refined(pl, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps, steps, berr,
+                                     (hipStream_t)stream);
+}
+
+int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lValues, const double* b, int ldb,
+                         double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds) {
+    if (!pl || !values || !lValues || !b || !x) {
+        set_last_error("parsy_solve_spd_host: null argument");
+        return -1;
+    }
+    if (pl->device < 0) {
+        set_last_error("parsy_solve_spd_host: plan was built without a device (device < 0)");
+        return -1;
+    }
+    const parsy::Schedule& S = pl->S;
+    if (nrhs < 1 || ldb < S.n || ldx < S.n) {
+        set_last_error("parsy_solve_spd_host: need nrhs >= 1 and leading dimensions >= n");
+        return -1;
+    }
+    CAPI_HIP(hipSetDevice(pl->device), -1);
+    if (!pl->h_values_dev) CAPI_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8), -1);
+    if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
+    const int64_t need = std::max<int64_t>((int64_t)S.n * nrhs, 1);
+    if (pl->h_x_len < need) {
+        if (pl->h_x_dev) (void)hipFree(pl->h_x_dev);
+        pl->h_x_dev = nullptr;
+        CAPI_HIP(hipMalloc((void**)&pl->h_x_dev, (size_t)need * 8), -1);
+        pl->h_x_len = need;
+    }
+    const size_t row = (size_t)S.n * 8;
+    CAPI_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice), -1);
+    CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
+    if (S.n > 0) CAPI_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice), -1);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    CAPI_HIP(hipEventCreate(&e0), -1);
+    if (hipEventCreate(&e1) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        set_last_error("parsy_solve_spd_host: hipEventCreate failed");
+        return -1;
+    }
+    (void)hipEventRecord(e0, nullptr);
+    int rc = parsy::plan_solve_refined(pl, pl->h_values_dev, pl->h_L_dev, pl->h_x_dev, S.n, pl->h_x_dev, S.n, nrhs,
+                                       max_steps, steps, berr, nullptr);
+    float ms = 0;
+    if (rc == 0 && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                    hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
+        set_last_error("parsy_solve_spd_host: timing the call failed");
+        rc = -1;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc != 0) return -1;
+    // (max_steps == 0 without steps / berr: nothing synchronised inside the call, so the solves' status is read here)
+    if (parsy_solve_status(pl) != 0) return -1;
+    if (seconds) *seconds = ms * 1e-3;
+    if (S.n > 0) CAPI_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost), -1);
     return 0;
 }
 

@@ -8,6 +8,7 @@
 
 #include "errors.hpp"
 #include "plan_fwd.hpp"
+#include "refine.hpp"
 
 namespace parsy {
 
@@ -235,6 +236,7 @@ void plan_free(parsy_plan* pl) {
         if (pl->h_copy) (void)hipStreamDestroy(pl->h_copy);
         for (hipEvent_t e : pl->h_band_ev) (void)hipEventDestroy(e);
     }
+    refine_free(pl);
     delete pl;
 }
 

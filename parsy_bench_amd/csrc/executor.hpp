@@ -10,6 +10,10 @@
 #include "kernels.hpp"
 #include "schedule.hpp"
 
+namespace parsy {
+struct RefineState;
+}
+
 struct parsy_plan {
     parsy::Schedule S;
     int device = -1;          // < 0: host schedule only
@@ -86,6 +90,7 @@ struct parsy_plan {
     double kind_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int kind_launches[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int profiled_runs = 0;
+    parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
 };
 
 namespace parsy {
