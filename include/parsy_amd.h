@@ -327,6 +327,38 @@ int parsy_solve_spd_device(parsy_plan* plan, const double* d_values, const doubl
 int parsy_solve_spd_host(parsy_plan* plan, const double* values, const double* lValues, const double* b, int ldb,
                          double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds);
 
+/* ---- Selected inversion: entries of A^-1 on the pattern of L, and log det A -------------------------------------
+ * Z = (P A P')^-1 on the stored pattern of L by the Takahashi recurrences, level by level from the root of the tree of
+ * the block columns (at most 64 columns of a supernode each).  Two kernel paths: a tiled one (FP64 MFMA, one workgroup
+ * per 64-row tile of a block column's rows below it) and a small one (one workgroup per block column) for block columns
+ * with fewer than PARSY_SELINV_TILED_MIN rows below them (read at every call).  No float atomics: Z, the diagonal and the
+ * log-determinant are bitwise reproducible.  The device calls refuse host-only and solve-only plans, plans under
+ * parsy_plan_set_active / _set_active_pieces, an open factorization or level-stepped solve and NULL pointers, with
+ * parsy_last_error set and the outputs untouched.  A plan that never calls them allocates nothing for them; the first
+ * call allocates the gather map and the scratch and adds them to the plan's device_bytes. */
+typedef struct parsy_selinv_info {
+    int32_t levels;               /* depth of the block-column tree = level steps per call */
+    int32_t block_columns;        /* sum over supernodes of ceil(w / 64) */
+    int32_t tiled_block_columns;  /* of those, on the tiled path under the current threshold */
+    int32_t launches;             /* kernel launches per parsy_selinv_device call */
+    double  flops;                /* sum_b 2 |R_b|^2 w_b + 4 |R_b| w_b^2 (the products Z Y, L T, Y' Z) */
+    int64_t device_bytes;         /* map + scratch held once built (0 before the first device call) */
+} parsy_selinv_info;
+int parsy_selinv_get_info(parsy_plan* plan, parsy_selinv_info* info);   /* host-only plans too */
+/* Violations of the schedule (every block column scheduled once, below its parent; every gather position holds the
+ * row it stands for); parsy_last_error describes the first.  Host-only plans too. */
+long long parsy_selinv_check(const parsy_plan* plan);
+/* Z = (P A P')^-1 on the pattern of L, in lValues' layout (xsize doubles, overwritten; the strict upper part of every
+ * diagonal block is 0).  d_z must not overlap d_lValues.  Asynchronous on stream after the first call. */
+int parsy_selinv_device(parsy_plan* plan, const double* d_lValues, double* d_z, void* stream);
+/* d_diag[perm[i]] = Z(i, i): diag(A^-1) in the caller's ordering (parsy_plan_set_perm; identity by default). */
+int parsy_inverse_diag_device(parsy_plan* plan, const double* d_z, double* d_diag, void* stream);
+/* Host buffers: H2D, the two calls above, D2H; diag may be NULL; seconds = device time. */
+int parsy_selinv_host(parsy_plan* plan, const double* lValues, double* z, double* diag, double* seconds);
+/* log det A = 2 sum log L_jj into *logdet (host; synchronises stream).  Returns 0; k > 0: the first (1-based, plan
+ * ordering) column whose diagonal entry is not positive and finite, *logdet = NaN; < 0: error. */
+int parsy_logdet_device(parsy_plan* plan, const double* d_lValues, double* logdet, void* stream);
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

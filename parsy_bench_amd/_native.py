@@ -86,7 +86,19 @@ EXPORTED_SYMBOLS = [
     "parsy_mg_gather_host", "parsy_mg_dist", "parsy_mg_plan", "parsy_mg_profile", "parsy_plan_profile_levels",
     "parsy_debug_kernel_count", "parsy_debug_kernel_name", "parsy_debug_kernel_launches", "parsy_debug_kernel_reset",
     "parsy_plan_set_perm", "parsy_residual_device", "parsy_solve_spd_device", "parsy_solve_spd_host",
+    "parsy_selinv_get_info", "parsy_selinv_check", "parsy_selinv_device", "parsy_inverse_diag_device",
+    "parsy_selinv_host", "parsy_logdet_device",
 ]
+
+
+class SelinvInfo(C.Structure):
+    _fields_ = [
+        ("levels", C.c_int32), ("block_columns", C.c_int32), ("tiled_block_columns", C.c_int32),
+        ("launches", C.c_int32), ("flops", C.c_double), ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DistInfo(C.Structure):
@@ -173,6 +185,13 @@ def _declare(lib):
     lib.parsy_residual_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.parsy_solve_spd_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.parsy_solve_spd_host.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_selinv_get_info.argtypes = [vp, vp]
+    lib.parsy_selinv_check.restype = C.c_longlong
+    lib.parsy_selinv_check.argtypes = [vp]
+    lib.parsy_selinv_device.argtypes = [vp, vp, vp, vp]
+    lib.parsy_inverse_diag_device.argtypes = [vp, vp, vp, vp]
+    lib.parsy_selinv_host.argtypes = [vp, vp, vp, vp, vp]
+    lib.parsy_logdet_device.argtypes = [vp, vp, vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

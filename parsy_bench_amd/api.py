@@ -285,6 +285,47 @@ class Plan:
         x = X[:, 0].copy() if one else np.ascontiguousarray(X)
         return x, {"steps": steps, "berr": berr, "seconds": sec.value}
 
+    # selected inversion: entries of A^-1 on the pattern of L, and log det A ------------------------------------
+    @property
+    def selinv_info(self) -> dict:
+        """levels, block_columns, tiled_block_columns (under the current PARSY_SELINV_TILED_MIN), launches, flops,
+        device_bytes (0 before the first device call)."""
+        si = N.SelinvInfo()
+        if N.lib().parsy_selinv_get_info(self._h, C.byref(si)) != 0:
+            raise RuntimeError("parsy_selinv_get_info failed: " + N.last_error())
+        return si.as_dict()
+
+    def selinv_check(self) -> int:
+        """Violations of the selected inversion's schedule (0: none; N.last_error() names the first)."""
+        return int(N.lib().parsy_selinv_check(self._h))
+
+    def selinv(self, lValues):
+        """Z = (P A P')^-1 on the pattern of L (lValues' layout) and diag(A^-1) in the plan's ordering
+        (parsy_plan_set_perm); returns (Z, diag, device_seconds)."""
+        lv = _f64(lValues)
+        z = np.empty(int(self.sym.xsize), dtype=np.float64)
+        diag = np.empty(self.sym.n, dtype=np.float64)
+        sec = C.c_double(0)
+        if N.lib().parsy_selinv_host(self._h, N.ptr(lv), N.ptr(z), N.ptr(diag), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_selinv_host failed: " + N.last_error())
+        return z, diag, sec.value
+
+    def selinv_device(self, d_lValues: int, d_z: int, stream: int = 0) -> None:
+        if N.lib().parsy_selinv_device(self._h, d_lValues, d_z, stream) != 0:
+            raise RuntimeError("parsy_selinv_device failed: " + N.last_error())
+
+    def inverse_diag_device(self, d_z: int, d_diag: int, stream: int = 0) -> None:
+        if N.lib().parsy_inverse_diag_device(self._h, d_z, d_diag, stream) != 0:
+            raise RuntimeError("parsy_inverse_diag_device failed: " + N.last_error())
+
+    def logdet_device(self, d_lValues: int, stream: int = 0):
+        """(log det A, column): column 0, or the first 1-based column whose pivot is not positive and finite (NaN)."""
+        out = C.c_double(0)
+        rc = N.lib().parsy_logdet_device(self._h, d_lValues, C.byref(out), stream)
+        if rc < 0:
+            raise RuntimeError("parsy_logdet_device failed: " + N.last_error())
+        return out.value, int(rc)
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

@@ -9,6 +9,7 @@
 #include "errors.hpp"
 #include "plan_fwd.hpp"
 #include "refine.hpp"
+#include "selinv.hpp"
 
 namespace parsy {
 
@@ -237,6 +238,7 @@ void plan_free(parsy_plan* pl) {
         for (hipEvent_t e : pl->h_band_ev) (void)hipEventDestroy(e);
     }
     refine_free(pl);
+    selinv_free(pl);
     delete pl;
 }
 

@@ -12,6 +12,7 @@
 
 namespace parsy {
 struct RefineState;
+struct SelinvState;
 }
 
 struct parsy_plan {
@@ -91,6 +92,7 @@ struct parsy_plan {
     int kind_launches[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     int profiled_runs = 0;
     parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
+    parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
 };
 
 namespace parsy {

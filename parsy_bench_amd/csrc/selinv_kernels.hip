@@ -1,0 +1,721 @@
+// Selected inversion on the device (selinv.hpp): Z = (P A P')^-1 on the pattern of L, level by level from the root,
+// diag(A^-1) in the caller's ordering and log det A.
+//
+// Per level, two kernel paths (split by |R_b|, PARSY_SELINV_TILED_MIN):
+//   TILED  k_selinv_tinv  one wave per block column: T = L_bb^-1 into a 64 x 64 scratch slot;
+//          k_selinv_y     one workgroup per 64-row tile of R_b: Y_t = L(R_b tile t, b) T (MFMA) into a slot;
+//          k_selinv_z     one workgroup per 64-row tile of R_b: Z(tile t, b) = -sum_k Z(tile t, chunk k) Y_k, the operand
+//                         chunks gathered through the map (symmetric: the lower triangle of Z only), FP64 MFMA; then the
+//                         partial Y_t' Z(tile t, b) into a slot;
+//          k_selinv_zbb   one workgroup per block column: Z(b, b) = T'T - (partials summed in tile order), zeros above.
+//   SMALL  k_selinv_small one workgroup per block column, in LDS, over 32-row chunks of R_b with the products
+//          reassociated so that no full Y is held: W = Z(chunk, R_b) L(R_b, b), Z(chunk, b) = -W T, G += L(chunk, b)'
+//          Z(chunk, b); at the end Z(b, b) = T'(T - G).
+// Every output entry has one writer and every sum a fixed order, with no atomics: Z is bitwise reproducible.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/parsy_amd.h"
+#include "errors.hpp"
+#include "executor.hpp"
+#include "refine.hpp"
+#include "selinv.hpp"
+
+namespace parsy {
+
+struct SelinvState {
+    bool map_ready = false;
+    SelinvSchedule X;
+    SelinvSplit sp;
+    int64_t *d_cb = nullptr, *d_mo = nullptr;
+    int32_t* d_gmap = nullptr;
+    SelinvBc* d_bcs = nullptr;
+    int32_t* d_tasks = nullptr;
+    int64_t task_cap = 0;            // (descriptor, tile) pairs d_tasks holds
+    double* d_scr = nullptr;         // level scratch: T, Y and partial slots (64 x 64 doubles each)
+    int64_t scr_slots = 0;
+    int64_t map_bytes = 0, scr_bytes = 0;
+    bool used = false;               // a call has enqueued work that reads the descriptors / scratch
+    // log-determinant and diagonal: per column the offset of its diagonal entry, the reduction's partials and result
+    int64_t* d_doff = nullptr;
+    double* d_lpart = nullptr;       // kLogParts sums, kLogParts first bad columns (as doubles), then the result pair
+    int64_t diag_bytes = 0;
+    // buffers of parsy_selinv_host
+    double *h_z = nullptr, *h_diag = nullptr;
+};
+
+namespace {
+
+constexpr int kSThreads = 256;
+constexpr int kLd = kTile + 1;          // LDS leading dimension of a 64-row block
+constexpr int kSlot = kTile * kTile;    // doubles of a scratch slot
+constexpr int kChunk = 32;              // rows of R_b per step of the small path
+constexpr int kLdC = kChunk + 1;
+constexpr int kLogParts = 256;          // workgroups of the log-determinant's first pass
+typedef double dbl4 __attribute__((ext_vector_type(4)));
+
+// ---- T = L_bb^-1 in LDS, one wave (the blocked inversion of the solves' k_diag_inverse) ---------------------------
+// 16x16 MFMA product acc += X Y of blocks of the LDS matrix (column-major, ld kLd); lane (l15, kq) holds column l15,
+// rows kq + 4 v of the result (v_mfma_f64_16x16x4_f64: A lane = (row l15, k kq), B lane = (k kq, column l15)).
+__device__ __forceinline__ dbl4 mm16(dbl4 acc, const double* __restrict__ X, const double* __restrict__ Y, int l15, int kq) {
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[(4 * st + kq) * kLd + l15], Y[l15 * kLd + 4 * st + kq], acc, 0, 0, 0);
+    return acc;
+}
+__device__ __forceinline__ void put16(double* __restrict__ Z, dbl4 acc, double sign, int l15, int kq) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) Z[l15 * kLd + kq + 4 * v] = sign * acc[v];
+}
+
+// M (64 x kLd doubles of LDS) := inv(L_bb), lower triangle, zeros above, an identity past wb.  Lanes 0..63 of one wave.
+__device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int r, int j0, int wb) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
+    {
+        double v[kTile];
+        const double* __restrict__ src = G + (int64_t)j0 * r + j0 + min(lane, wb - 1);
+#pragma unroll
+        for (int cc = 0; cc < kTile; ++cc) v[cc] = src[(int64_t)min(cc, wb - 1) * r];
+#pragma unroll
+        for (int cc = 0; cc < kTile; ++cc)
+            M[cc * kLd + lane] = (cc < wb && lane < wb && lane >= cc) ? v[cc] : (lane == cc ? 1.0 : 0.0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    auto blk = [&](int bi, int bj) { return M + (16 * bj) * kLd + 16 * bi; };
+    {
+        double* __restrict__ B = blk(kq, kq);
+        double y[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) y[k] = 0.0;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            double sacc = (rr == l15) ? -1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < rr; ++k) sacc = fma(B[k * kLd + rr], y[k], sacc);
+            y[rr] = (rr >= l15) ? -sacc / B[rr * kLd + rr] : 0.0;
+        }
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) B[l15 * kLd + rr] = y[rr];
+    }
+    __builtin_amdgcn_wave_barrier();
+    const dbl4 zero = {0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 4; b += 2) {
+        const dbl4 t = mm16(zero, blk(b + 1, b), blk(b, b), l15, kq);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        put16(blk(b + 1, b), t, 1.0, l15, kq);
+        __builtin_amdgcn_wave_barrier();
+        const dbl4 u = mm16(zero, blk(b + 1, b + 1), blk(b + 1, b), l15, kq);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        put16(blk(b + 1, b), u, -1.0, l15, kq);
+        __builtin_amdgcn_wave_barrier();
+    }
+    {
+        dbl4 t20 = mm16(mm16(zero, blk(2, 0), blk(0, 0), l15, kq), blk(2, 1), blk(1, 0), l15, kq);
+        dbl4 t30 = mm16(mm16(zero, blk(3, 0), blk(0, 0), l15, kq), blk(3, 1), blk(1, 0), l15, kq);
+        dbl4 t21 = mm16(zero, blk(2, 1), blk(1, 1), l15, kq);
+        dbl4 t31 = mm16(zero, blk(3, 1), blk(1, 1), l15, kq);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        put16(blk(2, 0), t20, 1.0, l15, kq);
+        put16(blk(3, 0), t30, 1.0, l15, kq);
+        put16(blk(2, 1), t21, 1.0, l15, kq);
+        put16(blk(3, 1), t31, 1.0, l15, kq);
+        __builtin_amdgcn_wave_barrier();
+        dbl4 x20 = mm16(zero, blk(2, 2), blk(2, 0), l15, kq);
+        dbl4 x21 = mm16(zero, blk(2, 2), blk(2, 1), l15, kq);
+        dbl4 x30 = mm16(mm16(zero, blk(3, 2), blk(2, 0), l15, kq), blk(3, 3), blk(3, 0), l15, kq);
+        dbl4 x31 = mm16(mm16(zero, blk(3, 2), blk(2, 1), l15, kq), blk(3, 3), blk(3, 1), l15, kq);
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        put16(blk(2, 0), x20, -1.0, l15, kq);
+        put16(blk(2, 1), x21, -1.0, l15, kq);
+        put16(blk(3, 0), x30, -1.0, l15, kq);
+        put16(blk(3, 1), x31, -1.0, l15, kq);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// acc[c] += A(16 w + ., k) B(k, 16 c + .) over k < 64, A(i, k) = A[i * ai + k * ak], B(k, j) = B[k * bk + j * bj] in LDS.
+// Wave w owns rows 16 w .. 16 w + 15 of the 64 x 64 result: acc[c][v] = C(16 w + kq + 4 v, 16 c + l15).
+__device__ __forceinline__ void mm64(dbl4 (&acc)[4], const double* __restrict__ A, int ai, int ak,
+                                     const double* __restrict__ B, int bk, int bj, int w, int l15, int kq) {
+#pragma unroll 4
+    for (int k4 = 0; k4 < kTile / 4; ++k4) {
+        const int k = 4 * k4 + kq;
+        const double a = A[(16 * w + l15) * ai + k * ak];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, B[k * bk + (16 * c + l15) * bj], acc[c], 0, 0, 0);
+    }
+}
+
+// Z(p, q) for positions p, q of the supernode's row list: the lower triangle through the map
+__device__ __forceinline__ int64_t zaddr(int64_t cbq, int64_t moq, const int32_t* __restrict__ gmap, int p) {
+    return cbq + gmap[moq + p];
+}
+
+// ---- tiled path --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_selinv_tinv(const SelinvBc* __restrict__ bcs, int d0,
+                                                    const double* __restrict__ L, double* __restrict__ scr) {
+    __shared__ double M[kTile * kLd];
+    const SelinvBc B = bcs[d0 + blockIdx.x];
+    tinv64(M, L + B.px, B.r, B.j0, B.wb);
+    __builtin_amdgcn_wave_barrier();
+    double* __restrict__ out = scr + (int64_t)B.tslot * kSlot;
+    for (int e = threadIdx.x; e < kSlot; e += 64) {
+        const int c = e >> 6, i = e & 63;
+        out[e] = (i < B.wb && c < B.wb) ? M[c * kLd + i] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(kSThreads) void k_selinv_y(const SelinvBc* __restrict__ bcs, const int32_t* __restrict__ tasks,
+                                                        const double* __restrict__ L, double* __restrict__ scr) {
+    __shared__ double As[kTile * kLd], Bs[kTile * kLd];
+    const int d = tasks[2 * blockIdx.x], t = tasks[2 * blockIdx.x + 1];
+    const SelinvBc B = bcs[d];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
+    const int p0 = B.j0 + B.wb, pr = p0 + kTile * t, nr = min(kTile, B.m - kTile * t);
+    const double* __restrict__ G = L + B.px;
+    const double* __restrict__ T = scr + (int64_t)B.tslot * kSlot;
+    for (int e = tid; e < kSlot; e += kSThreads) {
+        const int i = e & 63, k = e >> 6;
+        As[k * kLd + i] = (i < nr && k < B.wb) ? G[(int64_t)(B.j0 + k) * B.r + pr + i] : 0.0;
+        Bs[k * kLd + i] = T[e];
+    }
+    __syncthreads();
+    dbl4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    mm64(acc, As, 1, kLd, Bs, 1, kLd, w, l15, kq);
+    double* __restrict__ Y = scr + (int64_t)(B.yslot + t) * kSlot;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) Y[(16 * c + l15) * kTile + 16 * w + kq + 4 * v] = acc[c][v];
+}
+
+__global__ __launch_bounds__(kSThreads) void k_selinv_z(const SelinvBc* __restrict__ bcs, const int32_t* __restrict__ tasks,
+                                                        const int64_t* __restrict__ cb, const int64_t* __restrict__ mo,
+                                                        const int32_t* __restrict__ gmap, double* __restrict__ Z,
+                                                        double* __restrict__ scr) {
+    __shared__ double As[kTile * kLd], Bs[kTile * kLd];
+    __shared__ int64_t rcb[kTile], rmo[kTile], kcb[kTile], kmo[kTile];
+    const int d = tasks[2 * blockIdx.x], t = tasks[2 * blockIdx.x + 1];
+    const SelinvBc B = bcs[d];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, kq = lane >> 4;
+    const int p0 = B.j0 + B.wb, pr = p0 + kTile * t, nr = min(kTile, B.m - kTile * t);
+    if (tid < nr) {
+        rcb[tid] = cb[B.pi + pr + tid];
+        rmo[tid] = mo[B.pi + pr + tid];
+    }
+    dbl4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    const int nk = (B.m + kTile - 1) / kTile;
+    for (int kc = 0; kc < nk; ++kc) {
+        const int pk = p0 + kTile * kc, nkk = min(kTile, B.m - kTile * kc);
+        __syncthreads();   // (the previous chunk's products have read As / Bs)
+        if (tid < nkk) {
+            kcb[tid] = cb[B.pi + pk + tid];
+            kmo[tid] = mo[B.pi + pk + tid];
+        }
+        const double* __restrict__ Yk = scr + (int64_t)(B.yslot + kc) * kSlot;
+        for (int e = tid; e < kSlot; e += kSThreads) Bs[(e >> 6) * kLd + (e & 63)] = Yk[e];
+        __syncthreads();
+        // A(i, k) = Z(pr + i, pk + k): the stored entry of the pair's lower triangle
+        for (int e = tid; e < kSlot; e += kSThreads) {
+            const int i = e & 63, k = e >> 6, p = pr + i, q = pk + k;
+            double v = 0.0;
+            if (i < nr && k < nkk) v = Z[p >= q ? zaddr(kcb[k], kmo[k], gmap, p) : zaddr(rcb[i], rmo[i], gmap, q)];
+            As[k * kLd + i] = v;
+        }
+        __syncthreads();
+        mm64(acc, As, 1, kLd, Bs, 1, kLd, w, l15, kq);
+    }
+    __syncthreads();
+    // Z(tile, b) = -acc: through LDS (coalesced stores), kept there for the partial
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) As[(16 * c + l15) * kLd + 16 * w + kq + 4 * v] = -acc[c][v];
+    const double* __restrict__ Yt = scr + (int64_t)(B.yslot + t) * kSlot;
+    for (int e = tid; e < kSlot; e += kSThreads) Bs[(e >> 6) * kLd + (e & 63)] = Yt[e];
+    __syncthreads();
+    double* __restrict__ G = Z + B.px;
+    for (int e = tid; e < kSlot; e += kSThreads) {
+        const int i = e & 63, c = e >> 6;
+        if (i < nr && c < B.wb) G[(int64_t)(B.j0 + c) * B.r + pr + i] = As[c * kLd + i];
+    }
+    // partial P(a, c) = sum_i Y_t(i, a) Z(tile i, c)
+    dbl4 pacc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    mm64(pacc, Bs, kLd, 1, As, 1, kLd, w, l15, kq);
+    double* __restrict__ P = scr + (int64_t)(B.pslot + t) * kSlot;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) P[(16 * c + l15) * kTile + 16 * w + kq + 4 * v] = pacc[c][v];
+}
+
+// Z(b, b) = T'T - sum_t P_t (lower triangle), zeros in the rows above it (the supernode's diagonal block's upper part)
+__device__ __forceinline__ void write_diag_block(const SelinvBc& B, const double* __restrict__ Ts, int ldt,
+                                                 const double* __restrict__ Gs, const double* __restrict__ parts, int nparts,
+                                                 double* __restrict__ Z) {
+    double* __restrict__ G = Z + B.px;
+    for (int e = threadIdx.x; e < kSlot; e += kSThreads) {
+        const int a = e & 63, c = e >> 6;
+        if (a >= B.wb || c >= B.wb || a < c) continue;
+        double s = 0.0;
+        if (Gs) {   // small path: T'(T - G)
+            for (int q = a; q < B.wb; ++q) s = fma(Ts[a * ldt + q], Ts[c * ldt + q] - Gs[c * kLd + q], s);
+        } else {
+            for (int q = a; q < B.wb; ++q) s = fma(Ts[a * ldt + q], Ts[c * ldt + q], s);
+            for (int u = 0; u < nparts; ++u) s -= parts[(int64_t)u * kSlot + c * kTile + a];
+        }
+        G[(int64_t)(B.j0 + c) * B.r + B.j0 + a] = s;
+    }
+    for (int c = 0; c < B.wb; ++c)
+        for (int i = threadIdx.x; i < B.j0 + c; i += kSThreads) G[(int64_t)(B.j0 + c) * B.r + i] = 0.0;
+}
+
+__global__ __launch_bounds__(kSThreads) void k_selinv_zbb(const SelinvBc* __restrict__ bcs, int d0,
+                                                          const double* __restrict__ scr, double* __restrict__ Z) {
+    __shared__ double Ts[kTile * kLd];
+    const SelinvBc B = bcs[d0 + blockIdx.x];
+    const double* __restrict__ T = scr + (int64_t)B.tslot * kSlot;
+    for (int e = threadIdx.x; e < kSlot; e += kSThreads) Ts[(e >> 6) * kLd + (e & 63)] = T[e];
+    __syncthreads();
+    const int nparts = (B.m + kTile - 1) / kTile;
+    write_diag_block(B, Ts, kLd, nullptr, scr + (int64_t)B.pslot * kSlot, nparts, Z);
+}
+
+// ---- small path: one workgroup per block column -------------------------------------------------------------------
+__global__ __launch_bounds__(kSThreads) void k_selinv_small(const SelinvBc* __restrict__ bcs, int d0,
+                                                            const double* __restrict__ L, const int64_t* __restrict__ cb,
+                                                            const int64_t* __restrict__ mo, const int32_t* __restrict__ gmap,
+                                                            double* __restrict__ Z) {
+    __shared__ double M[kTile * kLd];          // T
+    __shared__ double Buf[2 * kTile * kLdC];   // W | Zc (32-row chunks, ld kLdC), later L's chunk in W; at the end G
+    const SelinvBc B = bcs[d0 + blockIdx.x];
+    const int tid = threadIdx.x, ci = tid & (kChunk - 1), tg = tid >> 5;   // chunk row ci; columns tg + 8 u
+    const double* __restrict__ Lp = L + B.px;
+    double* __restrict__ Zp = Z + B.px;
+    if (tid < 64) tinv64(M, Lp, B.r, B.j0, B.wb);
+    __syncthreads();
+    double* __restrict__ W = Buf;
+    double* __restrict__ Zc = Buf + kTile * kLdC;
+    const int p0 = B.j0 + B.wb;
+    double g[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) g[u] = 0.0;
+    for (int i0 = 0; i0 < B.m; i0 += kChunk) {
+        const int nr = min(kChunk, B.m - i0), p = p0 + i0 + ci;
+        // W(ci, t) = sum_k Z(p, p0 + k) L(p0 + k, j0 + t)
+        double acc[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = 0.0;
+        if (ci < nr) {
+            const int64_t pcb = cb[B.pi + p], pmo = mo[B.pi + p];
+            for (int k = 0; k < B.m; ++k) {
+                const int q = p0 + k;
+                const double z = Z[p >= q ? zaddr(cb[B.pi + q], mo[B.pi + q], gmap, p) : zaddr(pcb, pmo, gmap, q)];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int tc = tg + 8 * u;
+                    if (tc < B.wb) acc[u] = fma(z, Lp[(int64_t)(B.j0 + tc) * B.r + q], acc[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) W[(tg + 8 * u) * kLdC + ci] = acc[u];
+        __syncthreads();
+        // Zc(ci, c) = -sum_{t >= c} W(ci, t) T(t, c), stored to Z
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int c = tg + 8 * u;
+            double s = 0.0;
+            for (int q = c; q < B.wb; ++q) s = fma(W[q * kLdC + ci], M[c * kLd + q], s);
+            const bool ok = ci < nr && c < B.wb;
+            Zc[c * kLdC + ci] = ok ? -s : 0.0;
+            if (ok) Zp[(int64_t)(B.j0 + c) * B.r + p] = -s;
+        }
+        __syncthreads();
+        // L's chunk into W: W(ci, a) = L(p, j0 + a)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int a = tg + 8 * u;
+            W[a * kLdC + ci] = (ci < nr && a < B.wb) ? Lp[(int64_t)(B.j0 + a) * B.r + p] : 0.0;
+        }
+        __syncthreads();
+        // G(a, c) += sum_i W(i, a) Zc(i, c): entries tid + 256 u
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int e = tid + kSThreads * u, a = e & 63, c = e >> 6;
+            double s = g[u];
+            for (int i = 0; i < nr; ++i) s = fma(W[a * kLdC + i], Zc[c * kLdC + i], s);
+            g[u] = s;
+        }
+        __syncthreads();
+    }
+    double* __restrict__ Gs = Buf;   // G(a, c) at Gs[c * kLd + a]
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const int e = tid + kSThreads * u;
+        Gs[(e >> 6) * kLd + (e & 63)] = g[u];
+    }
+    __syncthreads();
+    write_diag_block(B, M, kLd, Gs, nullptr, 0, Z);
+}
+
+// ---- diagonal and log-determinant ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSThreads) void k_selinv_diag(const double* __restrict__ Z, const int64_t* __restrict__ doff,
+                                                           const int* __restrict__ perm, int n, double* __restrict__ diag) {
+    const int i = blockIdx.x * kSThreads + threadIdx.x;
+    if (i >= n) return;
+    diag[perm ? perm[i] : i] = Z[doff[i]];
+}
+
+// First pass: workgroup b sums log L_jj over its contiguous range of columns (fixed lane split and tree), and finds the
+// range's first column whose diagonal entry is not positive and finite.
+__global__ __launch_bounds__(kSThreads) void k_logdet_part(const double* __restrict__ L, const int64_t* __restrict__ doff,
+                                                           int n, double* __restrict__ part) {
+    __shared__ double ss[kSThreads];
+    __shared__ int sb[kSThreads];
+    const int per = (n + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = min(n, lo + per);
+    double s = 0.0;
+    int bad = INT_MAX;
+    for (int i = lo + threadIdx.x; i < hi; i += kSThreads) {
+        const double v = L[doff[i]];
+        if (v > 0.0 && v <= DBL_MAX) s += log(v);
+        else bad = min(bad, i);
+    }
+    ss[threadIdx.x] = s;
+    sb[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = kSThreads / 2; o; o >>= 1) {
+        if (threadIdx.x < o) {
+            ss[threadIdx.x] += ss[threadIdx.x + o];
+            sb[threadIdx.x] = min(sb[threadIdx.x], sb[threadIdx.x + o]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = ss[0];
+        part[kLogParts + blockIdx.x] = sb[0] == INT_MAX ? -1.0 : (double)sb[0];
+    }
+}
+
+// Second pass (one wave): the partials in order; out[0] = 2 sum (NaN on a bad column), out[1] = that column + 1, or 0.
+__global__ void k_logdet_final(double* __restrict__ part, int nparts) {
+    if (threadIdx.x != 0) return;
+    double s = 0.0, bad = -1.0;
+    for (int b = 0; b < nparts; ++b) {
+        s += part[b];
+        if (bad < 0 && part[kLogParts + b] >= 0) bad = part[kLogParts + b];
+    }
+    part[2 * kLogParts] = bad >= 0 ? __builtin_nan("") : 2.0 * s;
+    part[2 * kLogParts + 1] = bad + 1.0;
+}
+
+#define S_HIP(call)                                                                                  \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));                       \
+            return -1;                                                                               \
+        }                                                                                            \
+    } while (0)
+
+SelinvState& state(parsy_plan* pl) {
+    if (!pl->selinv) pl->selinv = new SelinvState;
+    return *pl->selinv;
+}
+
+// The refusals common to the calls (as the refinement calls refuse).
+int check_plan(parsy_plan* pl, const char* who) {
+    std::string w(who);
+    if (pl->device < 0) return set_last_error(w + ": plan was built without a device (device < 0)"), -1;
+    if (pl->solve_only) return set_last_error(w + ": plan was built from L's pattern only (no A pattern)"), -1;
+    if (pl->sn_mask_set || pl->piece_mask_set)
+        return set_last_error(w + ": plan is restricted by parsy_plan_set_active / _set_active_pieces"), -1;
+    if (pl->factor_open) return set_last_error(w + ": a factorization is still open (parsy_factor_begin)"), -1;
+    if (pl->levels_open) return set_last_error(w + ": a solve in steps of levels is still open"), -1;
+    return 0;
+}
+
+template <class T>
+int upload(T*& d, const std::vector<T>& h, int64_t& bytes) {
+    const size_t b = std::max<size_t>(h.size(), 1) * sizeof(T);
+    S_HIP(hipMalloc((void**)&d, b));
+    if (!h.empty()) S_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    bytes += (int64_t)b;
+    return 0;
+}
+
+// per column the offset of its diagonal entry, and the log-determinant's partials
+int ensure_diag(parsy_plan* pl) {
+    SelinvState& X = state(pl);
+    if (X.d_doff) return 0;
+    const Schedule& S = pl->S;
+    std::vector<int64_t> doff((size_t)S.n);
+    for (int s = 0; s < S.nsuper; ++s)
+        for (int q = 0; q < S.sn[s].w; ++q) doff[S.sn[s].c0 + q] = S.sn[s].px + (int64_t)q * S.sn[s].r + q;
+    S_HIP(hipSetDevice(pl->device));
+    int64_t bytes = 0;
+    if (upload(X.d_doff, doff, bytes) != 0) return -1;
+    S_HIP(hipMalloc((void**)&X.d_lpart, (2 * kLogParts + 2) * sizeof(double)));
+    bytes += (2 * kLogParts + 2) * sizeof(double);
+    X.diag_bytes = bytes;
+    pl->device_bytes += bytes;
+    return 0;
+}
+
+// the host schedule, the map on the device, and the split under the current threshold (descriptors, scratch)
+int ensure_selinv(parsy_plan* pl) {
+    SelinvState& X = state(pl);
+    S_HIP(hipSetDevice(pl->device));
+    if (!X.map_ready) {
+        std::string what;
+        if (!build_selinv(pl->S, X.X, what)) return set_last_error("parsy_selinv_device: " + what), -1;
+        int64_t bytes = 0;
+        if (upload(X.d_cb, X.X.cb, bytes) != 0 || upload(X.d_mo, X.X.mo, bytes) != 0 ||
+            upload(X.d_gmap, X.X.gmap, bytes) != 0)
+            return -1;
+        S_HIP(hipMalloc((void**)&X.d_bcs, std::max(X.X.nbc, 1) * sizeof(SelinvBc)));
+        bytes += std::max(X.X.nbc, 1) * sizeof(SelinvBc);
+        for (int b = 0; b < X.X.nbc; ++b) {
+            const SnDesc& d = pl->S.sn[X.X.bc_sn[b]];
+            const int j0 = X.X.bc_j[b] * kTile;
+            X.task_cap += (d.r - j0 - std::min(kTile, d.w - j0) + kTile - 1) / kTile;
+        }
+        S_HIP(hipMalloc((void**)&X.d_tasks, std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t)));
+        bytes += std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t);
+        X.map_bytes = bytes;
+        pl->device_bytes += bytes;
+        X.map_ready = true;
+    }
+    const int tmin = selinv_tiled_min();
+    if (X.sp.tiled_min != tmin) {
+        if (X.used) S_HIP(hipDeviceSynchronize());   // (an earlier call may still read the descriptors and the scratch)
+        split_selinv(pl->S, X.X, tmin, X.sp);
+        if (!X.sp.bcs.empty())
+            S_HIP(hipMemcpy(X.d_bcs, X.sp.bcs.data(), X.sp.bcs.size() * sizeof(SelinvBc), hipMemcpyHostToDevice));
+        if (!X.sp.tasks.empty())
+            S_HIP(hipMemcpy(X.d_tasks, X.sp.tasks.data(), X.sp.tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (X.sp.scratch_slots > X.scr_slots) {
+            if (X.d_scr) S_HIP(hipFree(X.d_scr));
+            X.d_scr = nullptr;
+            pl->device_bytes -= X.scr_bytes;
+            X.scr_bytes = 0;
+            X.scr_slots = 0;
+            S_HIP(hipMalloc((void**)&X.d_scr, (size_t)X.sp.scratch_slots * kSlot * sizeof(double)));
+            X.scr_slots = X.sp.scratch_slots;
+            X.scr_bytes = X.scr_slots * kSlot * (int64_t)sizeof(double);
+            pl->device_bytes += X.scr_bytes;
+        }
+    }
+    return 0;
+}
+
+// the caller's ordering from parsy_plan_set_perm (the refinement state's copy; null: identity)
+int perm_device(parsy_plan* pl, const int** out) {
+    *out = nullptr;
+    RefineState* R = pl->refine;
+    if (!R || R->perm.empty()) return 0;
+    if (!R->d_perm) {
+        S_HIP(hipMalloc((void**)&R->d_perm, R->perm.size() * 4));
+        S_HIP(hipMemcpy(R->d_perm, R->perm.data(), R->perm.size() * 4, hipMemcpyHostToDevice));
+        pl->device_bytes += (int64_t)R->perm.size() * 4;
+    }
+    *out = R->d_perm;
+    return 0;
+}
+
+}  // namespace
+
+void selinv_free(parsy_plan* pl) {
+    SelinvState* X = pl->selinv;
+    if (!X) return;
+    if (pl->device >= 0) {
+        for (void* p : {(void*)X->d_cb, (void*)X->d_mo, (void*)X->d_gmap, (void*)X->d_bcs, (void*)X->d_tasks,
+                        (void*)X->d_scr, (void*)X->d_doff, (void*)X->d_lpart, (void*)X->h_z, (void*)X->h_diag})
+            if (p) (void)hipFree(p);
+    }
+    delete X;
+    pl->selinv = nullptr;
+}
+
+int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stream) {
+    const char* who = "parsy_selinv_device";
+    if (check_plan(pl, who) != 0) return -1;
+    const int64_t xs = pl->S.xsize;
+    if (d_z < d_L + xs && d_L < d_z + xs) return set_last_error(std::string(who) + ": d_z overlaps d_lValues"), -1;
+    if (ensure_selinv(pl) != 0) return -1;
+    SelinvState& X = *pl->selinv;
+    const SelinvSplit& sp = X.sp;
+    X.used = true;
+    for (int l = 0; l < X.X.levels; ++l) {
+        const int d0 = sp.lvl_bc[l], nt = sp.lvl_ntiled[l], nsm = sp.lvl_bc[l + 1] - d0 - nt;
+        const int t0 = sp.lvl_task[l], ntask = sp.lvl_task[l + 1] - t0;
+        if (nt > 0) hipLaunchKernelGGL(k_selinv_tinv, dim3(nt), dim3(64), 0, stream, X.d_bcs, d0, d_L, X.d_scr);
+        if (ntask > 0) {
+            hipLaunchKernelGGL(k_selinv_y, dim3(ntask), dim3(kSThreads), 0, stream, X.d_bcs, X.d_tasks + 2 * t0, d_L,
+                               X.d_scr);
+            hipLaunchKernelGGL(k_selinv_z, dim3(ntask), dim3(kSThreads), 0, stream, X.d_bcs, X.d_tasks + 2 * t0,
+                               X.d_cb, X.d_mo, X.d_gmap, d_z, X.d_scr);
+        }
+        if (nt > 0) hipLaunchKernelGGL(k_selinv_zbb, dim3(nt), dim3(kSThreads), 0, stream, X.d_bcs, d0, X.d_scr, d_z);
+        if (nsm > 0)
+            hipLaunchKernelGGL(k_selinv_small, dim3(nsm), dim3(kSThreads), 0, stream, X.d_bcs, d0 + nt, d_L, X.d_cb,
+                               X.d_mo, X.d_gmap, d_z);
+    }
+    S_HIP(hipGetLastError());
+    return 0;
+}
+
+int plan_inverse_diag(parsy_plan* pl, const double* d_z, double* d_diag, hipStream_t stream) {
+    if (check_plan(pl, "parsy_inverse_diag_device") != 0) return -1;
+    S_HIP(hipSetDevice(pl->device));
+    const int* perm = nullptr;
+    if (ensure_diag(pl) != 0 || perm_device(pl, &perm) != 0) return -1;
+    const int n = pl->S.n;
+    if (n > 0)
+        hipLaunchKernelGGL(k_selinv_diag, dim3((n + kSThreads - 1) / kSThreads), dim3(kSThreads), 0, stream, d_z,
+                           pl->selinv->d_doff, perm, n, d_diag);
+    S_HIP(hipGetLastError());
+    return 0;
+}
+
+int plan_logdet(parsy_plan* pl, const double* d_L, double* logdet, hipStream_t stream) {
+    if (check_plan(pl, "parsy_logdet_device") != 0) return -1;
+    S_HIP(hipSetDevice(pl->device));
+    if (ensure_diag(pl) != 0) return -1;
+    SelinvState& X = *pl->selinv;
+    const int n = pl->S.n;
+    const int nparts = std::max(1, std::min(kLogParts, (n + kSThreads - 1) / kSThreads));
+    hipLaunchKernelGGL(k_logdet_part, dim3(nparts), dim3(kSThreads), 0, stream, d_L, X.d_doff, n, X.d_lpart);
+    hipLaunchKernelGGL(k_logdet_final, dim3(1), dim3(64), 0, stream, X.d_lpart, nparts);
+    S_HIP(hipGetLastError());
+    double out[2];
+    S_HIP(hipMemcpyAsync(out, X.d_lpart + 2 * kLogParts, sizeof(out), hipMemcpyDeviceToHost, stream));
+    S_HIP(hipStreamSynchronize(stream));
+    *logdet = out[0];
+    return (int)out[1];
+}
+
+}  // namespace parsy
+
+using parsy::set_last_error;
+
+extern "C" {
+
+int parsy_selinv_get_info(parsy_plan* pl, parsy_selinv_info* info) {
+    if (!pl || !info) {
+        set_last_error("parsy_selinv_get_info: null argument");
+        return -1;
+    }
+    const parsy::Schedule& S = pl->S;
+    parsy::SelinvSchedule own;
+    const parsy::SelinvSchedule* X = nullptr;
+    if (pl->selinv && pl->selinv->map_ready) {
+        X = &pl->selinv->X;
+    } else {
+        std::string what;
+        if (!parsy::build_selinv(S, own, what)) {
+            set_last_error("parsy_selinv_get_info: " + what);
+            return -1;
+        }
+        X = &own;
+    }
+    parsy::SelinvSplit sp;
+    parsy::split_selinv(S, *X, parsy::selinv_tiled_min(), sp);
+    info->levels = X->levels;
+    info->block_columns = X->nbc;
+    info->tiled_block_columns = sp.ntiled;
+    info->launches = sp.launches;
+    info->flops = X->flops;
+    info->device_bytes = pl->selinv ? pl->selinv->map_bytes + pl->selinv->scr_bytes : 0;
+    return 0;
+}
+
+int parsy_selinv_device(parsy_plan* pl, const double* d_lValues, double* d_z, void* stream) {
+    if (!pl || !d_lValues || !d_z) {
+        set_last_error("parsy_selinv_device: null argument");
+        return -1;
+    }
+    return parsy::plan_selinv(pl, d_lValues, d_z, (hipStream_t)stream);
+}
+
+int parsy_inverse_diag_device(parsy_plan* pl, const double* d_z, double* d_diag, void* stream) {
+    if (!pl || !d_z || !d_diag) {
+        set_last_error("parsy_inverse_diag_device: null argument");
+        return -1;
+    }
+    return parsy::plan_inverse_diag(pl, d_z, d_diag, (hipStream_t)stream);
+}
+
+int parsy_logdet_device(parsy_plan* pl, const double* d_lValues, double* logdet, void* stream) {
+    if (!pl || !d_lValues || !logdet) {
+        set_last_error("parsy_logdet_device: null argument");
+        return -1;
+    }
+    return parsy::plan_logdet(pl, d_lValues, logdet, (hipStream_t)stream);
+}
+
+int parsy_selinv_host(parsy_plan* pl, const double* lValues, double* z, double* diag, double* seconds) {
+    if (!pl || !lValues || !z) {
+        set_last_error("parsy_selinv_host: null argument");
+        return -1;
+    }
+    if (parsy::check_plan(pl, "parsy_selinv_host") != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    parsy::SelinvState& X = parsy::state(pl);
+    if (hipSetDevice(pl->device) != hipSuccess) {
+        set_last_error("parsy_selinv_host: hipSetDevice failed");
+        return -1;
+    }
+    const size_t xb = (size_t)std::max<int64_t>(S.xsize, 1) * 8, nb = (size_t)std::max(S.n, 1) * 8;
+    if ((!pl->h_L_dev && hipMalloc((void**)&pl->h_L_dev, xb) != hipSuccess) ||
+        (!X.h_z && hipMalloc((void**)&X.h_z, xb) != hipSuccess) ||
+        (!X.h_diag && hipMalloc((void**)&X.h_diag, nb) != hipSuccess)) {
+        set_last_error("parsy_selinv_host: hipMalloc failed");
+        return -1;
+    }
+    if (hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        set_last_error("parsy_selinv_host: upload failed");
+        return -1;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) (void)hipEventDestroy(e0);
+        set_last_error("parsy_selinv_host: hipEventCreate failed");
+        return -1;
+    }
+    (void)hipEventRecord(e0, nullptr);
+    int rc = parsy::plan_selinv(pl, pl->h_L_dev, X.h_z, nullptr);
+    if (rc == 0 && diag) rc = parsy::plan_inverse_diag(pl, X.h_z, X.h_diag, nullptr);
+    float ms = 0;
+    if (rc == 0 && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                    hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
+        set_last_error("parsy_selinv_host: timing the call failed");
+        rc = -1;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc != 0) return -1;
+    if (seconds) *seconds = ms * 1e-3;
+    if (hipMemcpy(z, X.h_z, (size_t)S.xsize * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (diag && S.n > 0 && hipMemcpy(diag, X.h_diag, (size_t)S.n * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_last_error("parsy_selinv_host: download failed");
+        return -1;
+    }
+    return 0;
+}
+
+}  // extern "C"
