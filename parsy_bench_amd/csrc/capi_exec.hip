@@ -796,12 +796,7 @@ int parsy_solve_host(parsy_plan* pl, const double* lValues, double* x, int nrhs,
     CAPI_HIP(hipSetDevice(pl->device), -1);
     if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
     const int64_t need = (int64_t)ldx * nrhs;
-    if (pl->h_x_len < need) {
-        if (pl->h_x_dev) (void)hipFree(pl->h_x_dev);
-        pl->h_x_dev = nullptr;
-        CAPI_HIP(hipMalloc((void**)&pl->h_x_dev, (size_t)need * 8), -1);
-        pl->h_x_len = need;
-    }
+    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
     CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
     CAPI_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice), -1);
     if (parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
@@ -867,12 +862,7 @@ int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs
     CAPI_HIP(hipSetDevice(pl->device), -1);
     if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
     const int64_t need = (int64_t)ldx * nrhs;
-    if (pl->h_x_len < need) {
-        if (pl->h_x_dev) (void)hipFree(pl->h_x_dev);
-        pl->h_x_dev = nullptr;
-        CAPI_HIP(hipMalloc((void**)&pl->h_x_dev, (size_t)need * 8), -1);
-        pl->h_x_len = need;
-    }
+    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
     CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
     CAPI_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice), -1);
     double sec = 0;
@@ -937,12 +927,7 @@ int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lVa
     if (!pl->h_values_dev) CAPI_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8), -1);
     if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
     const int64_t need = std::max<int64_t>((int64_t)S.n * nrhs, 1);
-    if (pl->h_x_len < need) {
-        if (pl->h_x_dev) (void)hipFree(pl->h_x_dev);
-        pl->h_x_dev = nullptr;
-        CAPI_HIP(hipMalloc((void**)&pl->h_x_dev, (size_t)need * 8), -1);
-        pl->h_x_len = need;
-    }
+    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
     const size_t row = (size_t)S.n * 8;
     CAPI_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice), -1);
     CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);

@@ -142,20 +142,13 @@ static int plan_upload(parsy_plan* pl) {
         pl->owned.push_back(d);
         pl->dp.sinfo = (int*)d;
         PARSY_HIP(hipMemset(d, 0, sizeof(int)));
-        pl->n_flags = std::max<int64_t>(S.n_dslots, 1) * kPassLanes;
-        const size_t fbytes = std::max<int64_t>(S.n_dslots, 1) * kPassLanes * sizeof(int);
-        pl->dp.flag_stride = (int)std::max<int64_t>(S.n_dslots, 1);
-        PARSY_HIP(hipMalloc(&d, fbytes));
-        pl->owned.push_back(d);
-        pl->dp.flags = (int*)d;
-        PARSY_HIP(hipMemset(d, 0, fbytes));
         const size_t tbytes = 2 * std::max<int64_t>(S.n_tflags, 1) * sizeof(int);
         pl->dp.n_tflags = (int)S.n_tflags;
         PARSY_HIP(hipMalloc(&d, tbytes));
         pl->owned.push_back(d);
         pl->dp.tflags = (int*)d;
         PARSY_HIP(hipMemset(d, 0, tbytes));
-        pl->device_bytes += (int64_t)(fbytes + tbytes);
+        pl->device_bytes += (int64_t)tbytes;
     }
     {
         // lowest priority: the side stream only fills what the main stream's chain leaves idle
@@ -339,12 +332,12 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                     launch_solve_small(pl->dp, l.first, l.count, l.jb, l.fused == 2, Lc, x, nrhs, ldx, pl->solve_ldq, stream);
                 break;
             case kLaunchSolvePanel:
-                if (l.fused && nrhs >= pl->dp.gates.chain_mrhs_min && !pl->old_mrhs_chain)
+                if (l.fused && nrhs >= pl->dp.gates.chain_mrhs_min)
                     launch_solve_blocks_mrhs(pl->dp, l.lds_bytes, l.wait_level, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx,
-                                             pl->solve_ldq, l.jb, pl->solve_wait_bias, stream);
-                else if (l.fused)
-                    launch_solve_chain(pl->dp, l.first, l.count, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx,
-                                       pl->epoch, l.jb, pl->solve_wait_bias, stream);
+                                             pl->solve_ldq, l.jb, pl->dp.gates.wait_bias, stream);
+                else if (l.fused)   // (one right-hand side: chain_mrhs_min is at most 2)
+                    launch_solve_chain(pl->dp, l.first, l.count, Lc, pl->dinv, x, pl->xscratch, l.jb, pl->dp.gates.wait_bias,
+                                       stream);
                 else
                     launch_solve_panel(pl->dp, l.first, l.count, Lc, x, pl->xscratch, nrhs, ldx, stream);
                 break;
@@ -357,7 +350,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
             case kLaunchBackBlock:
                 if (l.fused == 1 && nrhs == 1) {   // one right-hand side: the wave dataflow over block-column pairs
                     launch_bsolve_chain_w(pl->dp, l.lds_bytes, l.wait_level, Lc, pl->dinv, x, pl->xscratch, l.jb,
-                                          pl->solve_wait_bias, stream);
+                                          pl->dp.gates.wait_bias, stream);
                     break;
                 }
                 if (l.fused == 2 && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count) {
@@ -366,7 +359,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                 }
                 launch_bsolve_block(pl->dp, l.first, l.count, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx, l.fused,
                                     l.early,
-                                    l.fused == 1 ? l.jb : 0, pl->solve_wait_bias, stream);
+                                    l.fused == 1 ? l.jb : 0, pl->dp.gates.wait_bias, stream);
                 break;
         }
     }
@@ -384,10 +377,7 @@ static void run_launches(parsy_plan* pl, const std::vector<Launch>& seq, double*
     run_end(pl, stream);
 }
 
-// Start of a forward / backward solve: a fresh epoch range for its passes (flags of earlier solves go
-// stale; on wrap-around the flags are cleared first, so that no old value can pass for a new one), its own
-// status word and ticket counters zeroed.
-// (one: a ONE-launch solve -- its counters follow the status word; no flags, epochs or chain tickets)
+// Whether a solve is ONE launch (its counters follow the status word in the hand-off buffers; no chain tickets)
 // (how many right-hand sides: 8 where the launch has at most kOneSmallBlocks blocks -- ex15-class, 8: 0.130 -> 0.087 ms --, else
 // 4 -- from 6 on the level launches use the matrix cores: nd24k-class, 8: 0.75 vs 1.24 ms this way; 4: 0.81 -> 0.60 --, and 1 for
 // the backward solve beside a subtree launch -- parabolic_fem-class, 4: 0.79 vs 0.86 ms -- and for the much larger plans)
@@ -456,44 +446,99 @@ static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream
     st = state + 2 * k;
     st_next = state + 2 * (k ^ 1u);
     pl->solve_status_word = st;
-    const char* stall = std::getenv("PARSY_DEBUG_SOLVE_STALL");
-    pl->solve_wait_bias = (stall && stall[0] == '1') ? (1 << 20) : 0;
     return 0;
 }
 
-// (zero_words = false: the caller's k_solve_arm_wide launch zeroes the status word and the ticket counters)
-static int solve_begin(parsy_plan* pl, int passes, hipStream_t stream, bool zero_words = true) {
+// Argument checks of a device solve (`who`: the C ABI call the messages name).  A solve that starts here abandons one in
+// steps of levels that was never finished and reads the gates of its kernel variants, once for all its launches.
+static int solve_start(parsy_plan* pl, const char* who, bool args_ok, const char* need, bool starts = true) {
+    if (pl->device < 0) {
+        set_last_error(std::string(who) + ": plan was built without a device (device < 0)");
+        return -1;
+    }
+    if (!args_ok) {
+        set_last_error(std::string(who) + ": need " + need);
+        return -1;
+    }
+    if (starts) {
+        pl->levels_open = false;
+        pl->dp.gates = read_solve_gates();
+    }
+    return 0;
+}
+
+// The prologue of a solve by level launches: its own status word and the chain launches' ticket counters zeroed
+// (arm_wide: by the k_solve_arm_wide launch below instead), xscratch grown to `scratch` entries, the inverse diagonal
+// blocks and (bpart, one right-hand side) the backward partial sums allocated by the first solve that needs them; then
+// ev_s0, the hand-off buffer armed -- its first `armed` entries, or with arm_wide the wide supernodes' columns -- and
+// k_diag_inverse.  The chain launches hand x over through xscratch itself (solve_arm_handoff) and finish a block
+// column with a product with its inverse diagonal block.
+static int solve_prologue(parsy_plan* pl, const double* d_L, int nrhs, int ldx, int ldq, int64_t scratch, bool bpart,
+                          bool arm_wide, int64_t armed, hipStream_t stream) {
+    const Schedule& S = pl->S;
+    const int nwide = (int)S.solve_wide_list.size() / 2, ntickets = std::max(S.n_solve_chain_launches, 1);
     pl->solve_status_word = nullptr;
-    if (pl->epoch > INT_MAX - 2 * passes - 2) {
-        PARSY_HIP(hipMemsetAsync(pl->dp.flags, 0, (size_t)pl->n_flags * sizeof(int), stream));
-        PARSY_HIP(hipMemsetAsync(pl->dp.tflags, 0, 2 * (size_t)std::max(pl->dp.n_tflags, 1) * sizeof(int), stream));
-        pl->epoch = 0;
-    }
-    pl->epoch += 1;  // first pass uses this value; the kernels add the pass index
-    if (zero_words) {
+    if (!arm_wide) {
         PARSY_HIP(hipMemsetAsync(pl->dp.sinfo, 0, sizeof(int), stream));
-        PARSY_HIP(hipMemsetAsync(pl->dp.stickets, 0, (size_t)std::max(pl->S.n_solve_chain_launches, 1) * sizeof(int),
-                                 stream));
+        PARSY_HIP(hipMemsetAsync(pl->dp.stickets, 0, (size_t)ntickets * sizeof(int), stream));
     }
-    // diagnostic: PARSY_DEBUG_SOLVE_STALL=1 makes every waiter of the chain launches wait for an epoch that
-    // is never published -- the timeout path of the hand-offs, exercised by the tests
-    const char* st = std::getenv("PARSY_DEBUG_SOLVE_STALL");
-    pl->solve_wait_bias = (st && st[0] == '1') ? (1 << 20) : 0;
+    if (scratch > 0) PARSY_HIP(grow_device(pl->xscratch, pl->xscratch_len, scratch));
+    if (nwide > 0 && !pl->dinv) {
+        const size_t bytes = (size_t)std::max<int64_t>(S.n_dslots, 1) * kTile * kTile * sizeof(double);
+        PARSY_HIP(hipMalloc((void**)&pl->dinv, bytes));
+        pl->device_bytes += (int64_t)bytes;
+    }
+    if (bpart && nrhs == 1 && S.n_bpart_slots > 0 && !pl->dp.bpart) {
+        const size_t bytes = (size_t)S.n_bpart_slots * kTile * sizeof(double);
+        PARSY_HIP(hipMalloc((void**)&pl->dp.bpart, bytes));
+        pl->device_bytes += (int64_t)bytes;
+    }
+    PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
+    if (arm_wide) launch_solve_arm_wide(pl->dp, nwide, pl->xscratch, nrhs, ldx, ldq, ntickets, stream);
+    else if (armed > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch, armed, stream));
+    launch_diag_inverse(pl->dp, nwide, d_L, pl->dinv, stream);
+    return 0;
+}
+
+// The level launches of a whole forward / backward solve.  Where the subtree tiers serve it (sub_tiers_usable), the bands
+// of levels that are one launch each take the place of the level launches they cover: first in the forward solve, last
+// in the backward one.
+static void run_solve(parsy_plan* pl, bool backward, const double* d_L, double* x, int nrhs, int ldx, hipStream_t stream) {
+    const Schedule& S = pl->S;
+    const std::vector<Launch>& seq = backward ? S.bsolve : S.solve;
+    if (!sub_tiers_usable(pl, nrhs, ldx) || S.sub_cover_level < 0) {
+        run_launches(pl, seq, nullptr, d_L, x, nrhs, ldx, stream);
+        return;
+    }
+    run_begin(pl);
+    if (!backward) {
+        for (const SubTier& T : S.sub_tiers) {
+            profile_mark(pl, kLaunchSolveSmall, stream, pl->run_cursor, 0, 0, T.ntrees);
+            launch_solve_sub_mrhs(pl->dp, T, d_L, x, nrhs, ldx, pl->solve_ldq, stream);
+        }
+    }
+    for (size_t li = 0; li < seq.size(); ++li)
+        if (seq[li].fused != 2 && seq[li].level > S.sub_cover_level)
+            run_range(pl, seq, li, li + 1, nullptr, d_L, x, nrhs, ldx, stream);
+    if (backward) {
+        for (size_t k = S.sub_tiers.size(); k-- > 0;) {
+            profile_mark(pl, kLaunchBackBlock, stream, pl->run_cursor, 0, 0, S.sub_tiers[k].ntrees);
+            launch_bsolve_sub_mrhs(pl->dp, S.sub_tiers[k], d_L, x, nrhs, ldx, stream);
+        }
+    }
+    run_end(pl, stream);
+}
+
+static int solve_end(parsy_plan* pl, hipStream_t stream) {
+    PARSY_HIP(hipGetLastError());
+    PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
+    pl->have_s = true;
     return 0;
 }
 
 int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
-    if (pl->device < 0) {
-        set_last_error("parsy_backsolve: plan was built without a device (device < 0)");
-        return -1;
-    }
-    if (nrhs < 1 || ldx < pl->S.n) {
-        set_last_error("parsy_backsolve: need nrhs >= 1 and ldx >= n");
-        return -1;
-    }
-    pl->levels_open = false;
-    pl->dp.gates = read_solve_gates();
-    const int64_t need = (int64_t)ldx * nrhs;
+    if (solve_start(pl, "parsy_backsolve", nrhs >= 1 && ldx >= pl->S.n, "nrhs >= 1 and ldx >= n") != 0) return -1;
+    const Schedule& S = pl->S;
     double *y = nullptr, *y_next = nullptr;
     int *st = nullptr, *st_next = nullptr;
     int one_rc = solve_takes_one_launch(pl, nrhs, true) ? one_begin(pl, true, nrhs, stream, y, y_next, st, st_next) : 1;
@@ -503,67 +548,21 @@ int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int
         PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
         run_begin(pl);
         profile_mark(pl, kLaunchBackBlock, stream, pl->run_cursor, 0, 0, pl->dp.one_b.nblocks);
-        launch_bsolve_one(pl->dp, pl->S.n, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, pl->solve_wait_bias, pl->one_cap[1], stream);
-        if (pl->S.one_subtrees && pl->S.n_bsolve_subtrees > 0)
-            run_range(pl, pl->S.bsolve, pl->S.bsolve.size() - 1, pl->S.bsolve.size(), nullptr, d_L, d_x, nrhs, ldx, stream);
+        launch_bsolve_one(pl->dp, S.n, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, pl->dp.gates.wait_bias, pl->one_cap[1],
+                          stream);
+        if (S.one_subtrees && S.n_bsolve_subtrees > 0)
+            run_range(pl, S.bsolve, S.bsolve.size() - 1, S.bsolve.size(), nullptr, d_L, d_x, nrhs, ldx, stream);
         run_end(pl, stream);
-        PARSY_HIP(hipGetLastError());
-        PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
-        pl->have_s = true;
-        return 0;
+        return solve_end(pl, stream);
     }
-    // one epoch per pass of right-hand sides (what the chain launches publish / wait for)
-    const int passes = (nrhs + 3) / 4;
     // (several right-hand sides and wide supernodes: one prologue launch instead of memsets + a fill of n x nrhs entries)
-    const bool arm_wide = nrhs > 1 && !pl->S.solve_wide_list.empty() && !pl->old_mrhs_chain;
-    if (solve_begin(pl, passes, stream, !arm_wide) != 0) return -1;
-    if (pl->S.max_width > kTile && pl->xscratch_len < need) {
-        if (pl->xscratch) PARSY_HIP(hipFree(pl->xscratch));
-        pl->xscratch = nullptr;
-        PARSY_HIP(hipMalloc((void**)&pl->xscratch, (size_t)need * sizeof(double)));
-        pl->xscratch_len = need;
-    }
-    if (!pl->S.solve_wide_list.empty() && !pl->dinv) {
-        const size_t bytes = (size_t)std::max<int64_t>(pl->S.n_dslots, 1) * kTile * kTile * sizeof(double);
-        PARSY_HIP(hipMalloc((void**)&pl->dinv, bytes));
-        pl->device_bytes += (int64_t)bytes;
-    }
-    if (nrhs == 1 && pl->S.n_bpart_slots > 0 && !pl->dp.bpart) {
-        const size_t bytes = (size_t)pl->S.n_bpart_slots * kTile * sizeof(double);
-        PARSY_HIP(hipMalloc((void**)&pl->dp.bpart, bytes));
-        pl->device_bytes += (int64_t)bytes;
-    }
-    PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-    // the chain launches hand x over through xscratch itself (armed: see solve_arm_handoff) and finish a block
-    // column with a product with its inverse diagonal block
-    if (!pl->S.solve_wide_list.empty()) {
-        if (arm_wide)
-            launch_solve_arm_wide(pl->dp, (int)pl->S.solve_wide_list.size() / 2, pl->xscratch, nrhs, ldx, 0,
-                                  std::max(pl->S.n_solve_chain_launches, 1), stream);
-        else
-            PARSY_HIP(solve_arm_handoff(pl->xscratch, need, stream));
-        launch_diag_inverse(pl->dp, (int)pl->S.solve_wide_list.size() / 2, d_L, pl->dinv, stream);
-    }
-    if (sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_cover_level >= 0) {
-        run_begin(pl);
-        for (size_t li = 0; li < pl->S.bsolve.size(); ++li) {
-            const Launch& l = pl->S.bsolve[li];
-            if (l.fused == 2 || l.level <= pl->S.sub_cover_level) continue;
-            run_range(pl, pl->S.bsolve, li, li + 1, nullptr, d_L, d_x, nrhs, ldx, stream);
-        }
-        for (size_t k = pl->S.sub_tiers.size(); k-- > 0;) {
-            profile_mark(pl, kLaunchBackBlock, stream, pl->run_cursor, 0, 0, pl->S.sub_tiers[k].ntrees);
-            launch_bsolve_sub_mrhs(pl->dp, pl->S.sub_tiers[k], d_L, d_x, nrhs, ldx, stream);
-        }
-        run_end(pl, stream);
-    } else {
-        run_launches(pl, pl->S.bsolve, nullptr, d_L, d_x, nrhs, ldx, stream);
-    }
-    PARSY_HIP(hipGetLastError());
-    PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
-    pl->epoch += passes;
-    pl->have_s = true;
-    return 0;
+    const int64_t need = (int64_t)ldx * nrhs;
+    const bool wide = !S.solve_wide_list.empty();
+    if (solve_prologue(pl, d_L, nrhs, ldx, 0, S.max_width > kTile ? need : 0, true, nrhs > 1 && wide, wide ? need : 0,
+                       stream) != 0)
+        return -1;
+    run_solve(pl, true, d_L, d_x, nrhs, ldx, stream);
+    return solve_end(pl, stream);
 }
 
 // A solve in steps of etree levels (the exchange steps of a solve that is distributed above the cut go in between,
@@ -573,68 +572,36 @@ int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int
 // caller's layout of X, no ONE launch, no bands (a rank's share of the supernodes has neither).
 int plan_solve_levels(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream, int lev0,
                       int lev1, int flags) {
-    if (pl->device < 0) {
-        set_last_error("parsy_solve_levels: plan was built without a device (device < 0)");
-        return -1;
-    }
-    if (nrhs < 1 || ldx < pl->S.n || lev0 > lev1) {
-        set_last_error("parsy_solve_levels: need nrhs >= 1, ldx >= n and level_begin <= level_end");
-        return -1;
-    }
     const bool first = flags & 1, last = flags & 2, backward = flags & 4;
+    if (solve_start(pl, "parsy_solve_levels", nrhs >= 1 && ldx >= pl->S.n && lev0 <= lev1,
+                    "nrhs >= 1, ldx >= n and level_begin <= level_end", first) != 0)
+        return -1;
     if (!first && (!pl->levels_open || pl->levels_backward != backward || pl->levels_nrhs != nrhs)) {
         set_last_error("parsy_solve_levels: a step without PARSY_SOLVE_FIRST needs an open solve of the same direction and width");
         return -1;
     }
-    const int passes = backward ? (nrhs + 3) / 4 : (nrhs + 7) / 8;
-    const int64_t need = (int64_t)ldx * nrhs;
+    const Schedule& S = pl->S;
     if (first) {
-        pl->dp.gates = read_solve_gates();   // (once per solve: its later steps keep them)
-        if (solve_begin(pl, passes, stream) != 0) return -1;
-        {
-            const char* e = std::getenv("PARSY_OLD_MRHS_CHAIN");
-            pl->old_mrhs_chain = e && e[0] == '1';
-        }
-        if ((pl->S.n_solve_wide > 0 || pl->S.max_width > kTile) && pl->xscratch_len < need) {
-            if (pl->xscratch) PARSY_HIP(hipFree(pl->xscratch));
-            pl->xscratch = nullptr;
-            PARSY_HIP(hipMalloc((void**)&pl->xscratch, (size_t)need * sizeof(double)));
-            pl->xscratch_len = need;
-        }
-        if (!pl->S.solve_wide_list.empty() && !pl->dinv) {
-            const size_t bytes = (size_t)std::max<int64_t>(pl->S.n_dslots, 1) * kTile * kTile * sizeof(double);
-            PARSY_HIP(hipMalloc((void**)&pl->dinv, bytes));
-            pl->device_bytes += (int64_t)bytes;
-        }
-        if (backward && nrhs == 1 && pl->S.n_bpart_slots > 0 && !pl->dp.bpart) {
-            const size_t bytes = (size_t)pl->S.n_bpart_slots * kTile * sizeof(double);
-            PARSY_HIP(hipMalloc((void**)&pl->dp.bpart, bytes));
-            pl->device_bytes += (int64_t)bytes;
-        }
-        PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-        if (pl->xscratch && (pl->S.n_solve_wide > 0 || !pl->S.solve_wide_list.empty()))
-            PARSY_HIP(solve_arm_handoff(pl->xscratch, (!backward && nrhs == 1) ? (int64_t)ldx : need, stream));
-        if (!pl->S.solve_wide_list.empty())
-            launch_diag_inverse(pl->dp, (int)pl->S.solve_wide_list.size() / 2, d_L, pl->dinv, stream);
+        // (the wide supernodes' chains: one right-hand side forward hands over through the first ldx entries)
+        const int64_t need = (int64_t)ldx * nrhs;
+        const int64_t armed = S.n_solve_wide == 0 ? 0 : (!backward && nrhs == 1) ? (int64_t)ldx : need;
+        if (solve_prologue(pl, d_L, nrhs, ldx, 0, (S.n_solve_wide > 0 || S.max_width > kTile) ? need : 0, backward, false,
+                           armed, stream) != 0)
+            return -1;
         pl->solve_ldq = 0;
         run_begin(pl);
         pl->levels_open = true;
         pl->levels_backward = backward;
         pl->levels_nrhs = nrhs;
     }
-    const std::vector<Launch>& seq = backward ? pl->S.bsolve : pl->S.solve;
+    const std::vector<Launch>& seq = backward ? S.bsolve : S.solve;
     for (size_t li = 0; li < seq.size(); ++li)
         if ((seq[li].level >= lev0 && seq[li].level < lev1) || (last && seq[li].kind == kLaunchSolveFixup))
             run_range(pl, seq, li, li + 1, nullptr, d_L, d_x, nrhs, ldx, stream);
-    if (last) {
-        run_end(pl, stream);
-        PARSY_HIP(hipGetLastError());
-        PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
-        pl->epoch += passes;
-        pl->have_s = true;
-        pl->levels_open = false;
-    }
-    return 0;
+    if (!last) return 0;
+    run_end(pl, stream);
+    pl->levels_open = false;
+    return solve_end(pl, stream);
 }
 
 int plan_collect_profile(parsy_plan* pl) {
@@ -674,7 +641,6 @@ int plan_factor_begin(parsy_plan* pl, const double* d_values, double* d_L, hipSt
     // flags of earlier factorizations go stale; on wrap-around they are cleared, so that a value left by an
     // early factorization cannot pass for a new one
     if (pl->epoch >= INT_MAX - 4) {
-        PARSY_HIP(hipMemsetAsync(pl->dp.flags, 0, (size_t)pl->n_flags * sizeof(int), stream));
         PARSY_HIP(hipMemsetAsync(pl->dp.tflags, 0, 2 * (size_t)std::max(pl->dp.n_tflags, 1) * sizeof(int), stream));
         pl->epoch = 0;
     }
@@ -758,18 +724,9 @@ int plan_factor(parsy_plan* pl, const double* d_values, double* d_L, hipStream_t
     return plan_factor_end(pl, stream);
 }
 
-int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx,
-               hipStream_t stream) {
-    if (pl->device < 0) {
-        set_last_error("parsy_solve: plan was built without a device (device < 0)");
-        return -1;
-    }
-    if (nrhs < 1 || ldx < pl->S.n) {
-        set_last_error("parsy_solve: need nrhs >= 1 and ldx >= n");
-        return -1;
-    }
-    pl->levels_open = false;   // (a solve in steps of levels that was never finished is abandoned)
-    pl->dp.gates = read_solve_gates();
+int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
+    if (solve_start(pl, "parsy_solve", nrhs >= 1 && ldx >= pl->S.n, "nrhs >= 1 and ldx >= n") != 0) return -1;
+    const Schedule& S = pl->S;
     const SolveGates& G = pl->dp.gates;
     double *y = nullptr, *y_next = nullptr;
     int *st = nullptr, *st_next = nullptr;
@@ -780,102 +737,49 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
         PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
         run_begin(pl);
         pl->solve_ldq = 0;
-        if (pl->S.one_subtrees && pl->S.n_solve_subtrees > 0) run_range(pl, pl->S.solve, 0, 1, nullptr, d_L, d_x, nrhs, ldx, stream);
+        if (S.one_subtrees && S.n_solve_subtrees > 0) run_range(pl, S.solve, 0, 1, nullptr, d_L, d_x, nrhs, ldx, stream);
         profile_mark(pl, kLaunchSolveSmall, stream, pl->run_cursor, 0, 0, pl->dp.one_f.nblocks);
-        launch_solve_one(pl->dp, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, pl->solve_wait_bias, pl->one_cap[0], stream);
+        launch_solve_one(pl->dp, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, G.wait_bias, pl->one_cap[0], stream);
         run_end(pl, stream);
-        PARSY_HIP(hipGetLastError());
-        PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
-        pl->have_s = true;
-        return 0;
-    }
-    // one epoch per pass of right-hand sides (what the chain kernel publishes / waits for)
-    const int passes = (nrhs + 7) / 8;
-    {
-        const char* e = std::getenv("PARSY_OLD_MRHS_CHAIN");
-        pl->old_mrhs_chain = e && e[0] == '1';
-    }
-    // The prologue follows the chain launches the solve will take (run_range: kLaunchSolvePanel), chosen here once:
-    //   mrhs_chain -- k_solve_blocks_mrhs on the armed buffer (from G.chain_mrhs_min right-hand sides on: one as well under
-    //                 PARSY_MRHS_MIN=1): k_solve_arm_wide zeroes the status word and the tickets and arms the wide columns
-    //                 (where it can: no fixup list), else the memsets of solve_begin and the whole buffer armed;
-    //   one right-hand side otherwise -- k_solve_chain_w: memsets, whole buffer armed;
-    //   otherwise -- the flag protocol (k_solve_chain / k_solve_chain_mrhs): memsets, nothing armed.
-    const bool mrhs_chain = nrhs >= G.chain_mrhs_min && !pl->old_mrhs_chain;
-    const bool arm_wide = mrhs_chain && pl->S.n_solve_wide > 0 && !pl->S.solve_wide_list.empty() &&
-                          pl->S.solve_fix_list.empty();
-    if (solve_begin(pl, passes, stream, !arm_wide) != 0) return -1;
-    // (many right-hand sides: k_solve_blocks_mrhs on the armed buffer; PARSY_OLD_MRHS_CHAIN=1: the flag protocol of rounds 1-2)
-    {
-        const char* e = std::getenv("PARSY_OLD_MRHS_CHAIN");
-        pl->old_mrhs_chain = e && e[0] == '1';
+        return solve_end(pl, stream);
     }
     // From 16 right-hand sides on the solve works on X with the right-hand sides of a row contiguous (transposed in
     // and out: both kernels a solve of that many takes -- k_solve_small_mrhs, k_solve_blocks_mrhs -- read and write
     // whole rows then; a supernode's x block was 64 eight-byte pieces per column).  PARSY_XT_MIN=k (0: never).
-    const char* xt_env = std::getenv("PARSY_XT_MIN");
-    const int xt_min = xt_env && *xt_env ? std::atoi(xt_env) : 16;
     // (measured, 64 right-hand sides: Flan-class 23.1 -> 20.4 ms, nd24k-class 1.31 -> 1.19 ms; parabolic_fem-class 1.72 ->
     // 1.75 ms -- its factor has 67 entries per row and the two transposes, 0.3 ms, cost what the kernels gain: the layout
     // is taken from 200 entries of L per row on)
-    const bool use_xt = xt_min > 0 && nrhs >= xt_min && nrhs >= G.mrhs_min && nrhs >= G.chain_mrhs_min &&
-                        !pl->old_mrhs_chain && pl->S.solve_fix_list.empty() &&
-                        (pl->S.xsize >= (int64_t)150 * pl->S.n || (xt_env && *xt_env));
+    const bool use_xt = G.xt_min > 0 && nrhs >= G.xt_min && nrhs >= G.mrhs_min && S.solve_fix_list.empty() &&
+                        (S.xsize >= (int64_t)150 * S.n || G.xt_min_set);
     const int ldq = use_xt ? (nrhs + 15) & ~15 : 0;
-    const int64_t need = use_xt ? (int64_t)pl->S.n * ldq : (int64_t)ldx * nrhs;
-    if (pl->S.n_solve_wide > 0 && pl->xscratch_len < need) {
-        // grows only when a larger right-hand-side block shows up (not per call)
-        if (pl->xscratch) PARSY_HIP(hipFree(pl->xscratch));
-        pl->xscratch = nullptr;
-        PARSY_HIP(hipMalloc((void**)&pl->xscratch, (size_t)need * sizeof(double)));
-        pl->xscratch_len = need;
-    }
-    if (use_xt && pl->xt_len < need) {
-        if (pl->xt) PARSY_HIP(hipFree(pl->xt));
-        pl->xt = nullptr;
-        PARSY_HIP(hipMalloc((void**)&pl->xt, (size_t)need * sizeof(double)));
-        pl->xt_len = need;
-    }
-    if (!pl->S.solve_wide_list.empty() && !pl->dinv) {
-        const size_t bytes = (size_t)std::max<int64_t>(pl->S.n_dslots, 1) * kTile * kTile * sizeof(double);
-        PARSY_HIP(hipMalloc((void**)&pl->dinv, bytes));
-        pl->device_bytes += (int64_t)bytes;
-    }
-    PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-    // the chain launches hand x over through xscratch itself (one right-hand side: k_solve_chain_w; many:
-    // k_solve_blocks_mrhs): every entry holds the armed pattern when the solve starts
-    if (arm_wide)
-        launch_solve_arm_wide(pl->dp, (int)pl->S.solve_wide_list.size() / 2, pl->xscratch, nrhs, ldx, ldq,
-                              std::max(pl->S.n_solve_chain_launches, 1), stream);
-    else if ((mrhs_chain || nrhs == 1) && pl->S.n_solve_wide > 0)
-        PARSY_HIP(solve_arm_handoff(pl->xscratch, need, stream));
-    launch_diag_inverse(pl->dp, (int)pl->S.solve_wide_list.size() / 2, d_L, pl->dinv, stream);
+    const int64_t need = use_xt ? (int64_t)S.n * ldq : (int64_t)ldx * nrhs;
+    if (use_xt) PARSY_HIP(grow_device(pl->xt, pl->xt_len, need));
+    // The chain launches of the wide supernodes take the whole buffer armed -- k_solve_chain_w (one right-hand side),
+    // k_solve_blocks_mrhs (from G.chain_mrhs_min on) --, or where it can (no fixup list) the latter's prologue launch,
+    // k_solve_arm_wide, arms their columns and zeroes the status word and the tickets.
+    const bool arm_wide = nrhs >= G.chain_mrhs_min && S.n_solve_wide > 0 && !S.solve_wide_list.empty() &&
+                          S.solve_fix_list.empty();
+    const int64_t scratch = S.n_solve_wide > 0 ? need : 0;
+    if (solve_prologue(pl, d_L, nrhs, ldx, ldq, scratch, false, arm_wide, scratch, stream) != 0) return -1;
     pl->solve_ldq = ldq;
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, pl->S.n, nrhs, true, stream);
-    if (sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_cover_level >= 0) {
-        // the bands of levels that are one launch each (tiers), then the level launches above them
-        double* xw = use_xt ? pl->xt : d_x;
-        run_begin(pl);
-        for (const SubTier& T : pl->S.sub_tiers) {
-            profile_mark(pl, kLaunchSolveSmall, stream, pl->run_cursor, 0, 0, T.ntrees);
-            launch_solve_sub_mrhs(pl->dp, T, d_L, xw, nrhs, ldx, ldq, stream);
-        }
-        for (size_t li = 0; li < pl->S.solve.size(); ++li) {
-            const Launch& l = pl->S.solve[li];
-            if (l.fused == 2 || l.level <= pl->S.sub_cover_level) continue;
-            run_range(pl, pl->S.solve, li, li + 1, nullptr, d_L, xw, nrhs, ldx, stream);
-        }
-        run_end(pl, stream);
-    } else {
-        run_launches(pl, pl->S.solve, nullptr, d_L, use_xt ? pl->xt : d_x, nrhs, ldx, stream);
-    }
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, pl->S.n, nrhs, false, stream);
+    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, S.n, nrhs, true, stream);
+    run_solve(pl, false, d_L, use_xt ? pl->xt : d_x, nrhs, ldx, stream);
+    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, S.n, nrhs, false, stream);
     pl->solve_ldq = 0;
-    PARSY_HIP(hipGetLastError());
-    PARSY_HIP(hipEventRecord(pl->ev_s1, stream));
-    pl->epoch += passes;
-    pl->have_s = true;
-    return 0;
+    return solve_end(pl, stream);
+}
+
+hipError_t grow_device(double*& buf, int64_t& len, int64_t need) {
+    if (len >= need) return hipSuccess;
+    if (buf) {
+        const hipError_t e = hipFree(buf);
+        if (e != hipSuccess) return e;
+    }
+    buf = nullptr;
+    len = 0;
+    const hipError_t e = hipMalloc((void**)&buf, (size_t)need * sizeof(double));
+    if (e == hipSuccess) len = need;
+    return e;
 }
 
 }  // namespace parsy

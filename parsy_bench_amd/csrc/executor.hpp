@@ -28,9 +28,7 @@ struct parsy_plan {
     std::vector<void*> launch_owned; // the launch-array blocks
     parsy::DevicePattern dp;
     int64_t device_bytes = 0;
-    int epoch = 0;            // factorization counter (value the chain launches publish / wait for)
-    int64_t n_flags = 1;      // entries of dp.flags
-    int solve_wait_bias = 0;  // diagnostic (PARSY_DEBUG_SOLVE_STALL): added to the epoch the solve's waiters wait for
+    int epoch = 0;            // factorization counter (value the Cholesky chain launches publish / wait for)
 
     double* dinv = nullptr;       // inverse 64x64 diagonal blocks of the wide supernodes (solve)
     double* xscratch = nullptr;
@@ -81,7 +79,6 @@ struct parsy_plan {
     double* xt = nullptr;           // X with the right-hand sides of a row contiguous (forward solves with many of them)
     int64_t xt_len = 0;
     int solve_ldq = 0;              // > 0: the running solve works on xt with this row stride
-    bool old_mrhs_chain = false;    // PARSY_OLD_MRHS_CHAIN=1: forward chain launches with many right-hand sides by flags
     std::vector<hipEvent_t> pev;
     std::vector<int> pev_kind;
     std::vector<int> pev_level;     // per mark: level << 1 | side of a factorization launch (-1: other)
@@ -114,5 +111,7 @@ int plan_backsolve(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, i
 int plan_solve_levels(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream, int lev0,
                       int lev1, int flags);
 int plan_collect_profile(parsy_plan* plan);
+// buf (len doubles) made at least `need` doubles long; the contents are not kept
+hipError_t grow_device(double*& buf, int64_t& len, int64_t need);
 
 }  // namespace parsy

@@ -11,18 +11,22 @@ namespace parsy {
 
 constexpr int kPassLanes = 8;    // passes over the right-hand sides of a solve that run side by side
 
-// The thresholds that choose between the solves' kernel variants.  The defaults are the tuned values; the variables
-// (diagnostics, tests: every variant can be forced) are read ONCE at the start of every forward / backward solve call
-// (read_solve_gates, into the plan's DevicePattern, where the launch functions take them from) -- not per process, so a
-// test can change them between solves, and not per launch (a solve makes hundreds of launches).
+// The thresholds that choose between the solves' kernel variants, and the solves' diagnostics.  The defaults are the tuned
+// values; the variables (diagnostics, tests: every variant can be forced) are read ONCE at the start of every forward /
+// backward solve call (read_solve_gates, into the plan's DevicePattern, where the launch functions take them from) -- not
+// per process, so a test can change them between solves, and not per launch (a solve makes hundreds of launches).
 struct SolveGates {
-    int mrhs_min = 6;             // PARSY_MRHS_MIN=k (sets this and the next): narrow supernodes take k_solve_small_mrhs from here on
+    int mrhs_min = 6;             // PARSY_MRHS_MIN=k (this: k, the next: min(k, 2)): narrow supernodes take k_solve_small_mrhs from here on
     int chain_mrhs_min = 2;       // ... the wide supernodes' chain k_solve_blocks_mrhs (armed hand-off buffer)
     int bmrhs_min = 16;           // PARSY_BMRHS_MIN: the backward solve's many-right-hand-side kernels
     bool bmrhs_wide_only = true;  // PARSY_BMRHS_WIDE_ONLY=0: k_bsolve_block_mrhs on launches of few blocks too
     int bchain_min_blocks = 128;  // PARSY_BCHAIN_MIN_BLOCKS: chain launches take k_bsolve_chain_mrhs from this many block columns on
     int small_halves_min = 512;   // PARSY_SMALL_MRHS_HALVES_MIN: k_solve_small_mrhs<64> sweeps in halves from this many supernodes on
     int sub_mrhs_min = 6;         // PARSY_SUB_MRHS_MIN: the subtree launches take the many-right-hand-side form (0: never)
+    int xt_min = 16;              // PARSY_XT_MIN: forward solves of this many right-hand sides work on X row-major (0: never)
+    bool xt_min_set = false;      // ... set: whatever the factor's density
+    int wait_bias = 0;            // PARSY_DEBUG_SOLVE_STALL=1: 1 << 20, no hand-off wait of the solve is ever satisfied
+    int sub_abl = 0;              // PARSY_SUB_ABL: ablation mask of the subtree kernels (diagnostic build, trsv_sub_kernels.hip)
 };
 SolveGates read_solve_gates();
 
@@ -38,10 +42,8 @@ SolveGates read_solve_gates();
     X(SolveSmallMrhs64Halves, "k_solve_small_mrhs<64,true>")                                                         \
     X(SolvePanel, "k_solve_panel")                                                                                   \
     X(DiagInverse, "k_diag_inverse")                                                                                 \
-    X(SolveChain8, "k_solve_chain<8>")                                                                               \
     X(SolveChainW2, "k_solve_chain_w<2>")                                                                            \
     X(SolveChainW4, "k_solve_chain_w<4>")                                                                            \
-    X(SolveChainMrhs, "k_solve_chain_mrhs")                                                                          \
     X(SolveBlocksMrhsNarrow, "k_solve_blocks_mrhs<true>")                                                            \
     X(SolveBlocksMrhs, "k_solve_blocks_mrhs<false>")                                                                 \
     X(TransposeX, "k_transpose_x")                                                                                   \
@@ -109,12 +111,10 @@ struct DevicePattern {           // device copies of Schedule arrays
     const int32_t* sub_out_rows = nullptr;
     int sub_ntiers = 0;
     int* info = nullptr;         // first failed pivot column + 1 (0x7f7f7f7f = none, < 0: wait timed out)
-    int* flags = nullptr;        // solve chain: per block column, epoch of the pass that published it
     int* tflags = nullptr;       // Cholesky chain: per tile, epoch of the factorization that published it
                                  // ([0, n_tflags): finished tiles, [n_tflags, 2 n_tflags): tiles prepared for the walker)
     int n_tflags = 0;
     int* tickets = nullptr;      // one counter per CHAIN launch (zeroed at the start of a factorization)
-    int flag_stride = 0;         // flags holds kPassLanes sets of this many entries (one per lane of passes)
     int* sinfo = nullptr;        // status of the last solve: 0 ok, < 0 a hand-off wait timed out (own word: a solve
                                  // never touches the factorization's status)
     int* stickets = nullptr;     // one counter per chain launch of the forward / backward solve
@@ -154,9 +154,8 @@ void launch_bsolve_one(const DevicePattern& P, int n, const double* L, double* x
                        double* y, double* y_next, int* state, int* state_next, int wait_bias, int cap, hipStream_t stream);
 void launch_solve_panel(const DevicePattern& P, int first, int count, const double* L, double* x,
                         double* xscratch, int nrhs, int ldx, hipStream_t stream);
-void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
-                        double* x, double* xscratch, int nrhs, int ldx, int epoch0, int ticket, int wait_bias,
-                        hipStream_t stream);
+void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv, double* x,
+                        double* xscratch, int ticket, int wait_bias, hipStream_t stream);   // (one right-hand side)
 void launch_solve_blocks_mrhs(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
                               double* x, double* xscratch, int nrhs, int ldx, int ldq, int ticket, int wait_bias,
                               hipStream_t stream);

@@ -380,12 +380,7 @@ int residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* 
     // solve fills it afresh, the residual runs between solves)
     const int ldq = (nrhs + 15) & ~15;
     const int64_t need = (int64_t)n * ldq;
-    if (pl->xt_len < need) {
-        if (pl->xt) R_HIP(hipFree(pl->xt));
-        pl->xt = nullptr;
-        R_HIP(hipMalloc((void**)&pl->xt, (size_t)need * sizeof(double)));
-        pl->xt_len = need;
-    }
+    R_HIP(grow_device(pl->xt, pl->xt_len, need));
     launch_transpose_x(const_cast<double*>(z), n, pl->xt, ldq, n, nrhs, true, stream);
     const int L = nrhs <= 8 ? 8 : nrhs <= 16 ? 16 : nrhs <= 32 ? 32 : 64;
     const int nb = nblocks(kRThreads / L);

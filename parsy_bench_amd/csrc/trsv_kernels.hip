@@ -21,8 +21,7 @@ static constexpr unsigned long long kSolveSpinTicks = 200000000ull;  // 2 s of t
 static constexpr int kLdDiag = kTile + 1;
 static constexpr int kRhs = 8;  // right-hand sides carried per pass over a panel
 // Passes over the right-hand sides are independent of each other: up to kPassLanes of them run side by
-// side (workgroups of their own; the chain launches keep one set of flags per lane), the rest follow in
-// rounds.  A block of 64 right-hand sides then costs about one pass of latency instead of eight.
+// side (workgroups of their own), the rest follow in rounds.  A block of 64 right-hand sides then costs about one pass of latency instead of eight.
 
 // Forward solve of the staged block xs[c][q] (c < w <= 64, q < nq) with the lower-triangular
 // block Dg (column-major, ld kLdDiag; entries outside w x w must be an identity).  Blocked by
@@ -739,173 +738,8 @@ void launch_diag_inverse(const DevicePattern& P, int count, const double* L, dou
     hipLaunchKernelGGL(k_diag_inverse, dim3(count), dim3(64), 0, stream, P.sn, P.solve_wide_list, L, dinv);
 }
 
-// SOLVE_CHAIN: the whole block-column chain of a wide supernode in ONE launch.  Workgroup c
-// owns rows [256c, 256c+256) of the panel and keeps the running update of its rows in
-// registers (pull form: no atomics inside the supernode).  For block column jb the owner of
-// rows [64jb, 64jb+64) multiplies its up-to-date rows by the inverse diagonal block
-// (DIAG_INVERSE) and publishes x_jb as 8-byte agent-scope atomics + a flag
-// (cdna_hip_programming.md Guideline 16, "8-B agent atomics both sides"); workgroups with rows
-// below wait for the flag (bounded), read x_jb and update their rows.  Rows below the
-// supernode's own columns are scattered once, at the end, with atomics (other supernodes of
-// the level update the same ancestor rows).  All workgroups of a launch are resident at
-// once (the host caps their number), so the waits cannot starve the workgroup they wait for.
-template <int NQ>
-__global__ __launch_bounds__(kThreads) void k_solve_chain(const SnDesc* __restrict__ sn,
-                                                          const PanelDesc* __restrict__ pds,
-                                                          const int32_t* __restrict__ rows,
-                                                          const double* __restrict__ L,
-                                                          const double* __restrict__ dinv,
-                                                          double* __restrict__ x,
-                                                          double* __restrict__ xscratch, int nrhs,
-                                                          int ldx, int* __restrict__ flags, int epoch0,
-                                                          int* __restrict__ info, int* __restrict__ ticket,
-                                                          int wait_bias, int nchunks, int fstride) {
-    __shared__ double Di[2][kTile * kLdDiag];  // inverse diagonal blocks, double buffered
-    __shared__ double xs[kTile][NQ];
-    __shared__ double ts[kTile][NQ];
-    __shared__ int32_t s_ok, s_task;
-    const int tid = threadIdx.x;
-    // chunks are listed producers first (the owner of a block column before the chunks below it) and a
-    // workgroup takes its chunk from a ticket counter when it starts: whatever it waits for belongs to a
-    // workgroup that has already started -- no assumption on residency or dispatch order
-    if (tid == 0) s_task = atomicAdd(ticket, 1);
-    __syncthreads();
-    // the launch holds every chunk once per pass lane: tickets 0..nchunks-1 are lane 0, and so on
-    const int plane = s_task / nchunks;
-    const PanelDesc pd = pds[s_task - plane * nchunks];
-    flags += (int64_t)plane * fstride;   // one set of flags per lane
-    const SnDesc D = sn[pd.sn];
-    const int r = D.r, w = D.w, chunk = pd.jb, row0 = pd.row0;
-    const int nbc = (w + kTile - 1) / kTile;
-    const double* __restrict__ G = L + D.px;
-    const int k = row0 + tid;          // this thread's panel row
-    const bool kv = k < r;
-    const bool kdiag = kv && k < w;    // row inside the supernode's own columns
-    // block columns whose diagonal block this workgroup owns: [jb_first, jb_last)
-    const int jb_first = row0 / kTile, jb_last = min(nbc, (row0 + kSolveRows) / kTile);
-    auto load_inv = [&](int jb, double (&regs)[kTile * kTile / kThreads]) {
-        const double* __restrict__ src = dinv + (int64_t)(D.dslot + jb) * (kTile * kTile);
-#pragma unroll
-        for (int t = 0; t < kTile * kTile / kThreads; ++t) regs[t] = src[t * kThreads + tid];
-    };
-    auto store_inv = [&](int buf, const double (&regs)[kTile * kTile / kThreads]) {
-#pragma unroll
-        for (int t = 0; t < kTile * kTile / kThreads; ++t) {
-            const int e = t * kThreads + tid;
-            Di[buf][(e >> 6) * kLdDiag + (e & 63)] = regs[t];
-        }
-    };
-    for (int pass = plane; pass * NQ < nrhs; pass += kPassLanes) {
-        const int q0 = pass * NQ;
-        const int nq = min(NQ, nrhs - q0);
-        const int epoch = epoch0 + pass / kPassLanes;   // round of this lane
-        double xv[NQ], acc[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            acc[q] = 0.0;
-            xv[q] = (kdiag && q < nq) ? x[(int64_t)(q0 + q) * ldx + D.c0 + k] : 0.0;
-        }
-        double inv_regs[kTile * kTile / kThreads];
-        if (jb_first < jb_last) {
-            load_inv(jb_first, inv_regs);
-            store_inv(jb_first & 1, inv_regs);
-        }
-        for (int jb = 0; jb < nbc; ++jb) {
-            const int cb = jb * kTile, wbk = min(kTile, w - cb);
-            const int owner = cb / kSolveRows;
-            if (chunk < owner) break;  // no rows at or below this block column
-            // this thread's row of L against block column jb: all 64 loads are issued here, BEFORE the
-            // wait for x_jb, so that their latency hides behind the hand-off
-            const bool below = kv && k >= cb + wbk;
-            double lv[kTile];
-            if (below) {
-#pragma unroll
-                for (int c = 0; c < kTile; ++c) lv[c] = (c < wbk) ? G[(int64_t)(cb + c) * r + k] : 0.0;
-            }
-            __syncthreads();           // xs / ts of the previous block column are free
-            if (chunk == owner) {
-                const int lr = k - cb;  // row inside the block for the 64 threads that hold it
-                if (lr >= 0 && lr < kTile) {
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) ts[lr][q] = (lr < wbk) ? xv[q] - acc[q] : 0.0;
-                }
-                __syncthreads();
-                // x_jb = inv(Ljj) t : thread (i, q-slice); the next owned inverse is fetched meanwhile
-                const bool next_owned = jb + 1 < jb_last;
-                if (next_owned) load_inv(jb + 1, inv_regs);
-                {
-                    const double* __restrict__ Dv = Di[jb & 1];
-                    for (int e = tid; e < kTile * nq; e += kThreads) {
-                        const int i = e & 63, q = e >> 6;
-                        double sacc = 0.0;
-                        for (int k2 = 0; k2 <= i; ++k2) sacc = fma(Dv[k2 * kLdDiag + i], ts[k2][q], sacc);
-                        xs[i][q] = sacc;
-                    }
-                }
-                __syncthreads();
-                for (int e = tid; e < wbk * nq; e += kThreads) {
-                    const int q = e / wbk, c = e - q * wbk;
-                    const double v = xs[c][q];
-                    __hip_atomic_store(&xscratch[(int64_t)(q0 + q) * ldx + D.c0 + cb + c], v, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                    x[(int64_t)(q0 + q) * ldx + D.c0 + cb + c] = v;
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0)
-                    __hip_atomic_store(&flags[D.dslot + jb], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (next_owned) store_inv((jb + 1) & 1, inv_regs);
-            } else {
-                if (tid == 0) {
-                    const unsigned long long t0 = wall_clock64();
-                    int ok = 1;
-                    // epochs only grow: a later pass of this solve may already have raised the flag.  The wait is
-                    // bounded and watches the solve's status word: one timeout ends every wait of the solve
-                    int spins = 0;
-                    while (__hip_atomic_load(&flags[D.dslot + jb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) -
-                               (epoch + wait_bias) < 0) {
-                        if ((++spins & 15) == 0 &&
-                            (wall_clock64() - t0 > kSolveSpinTicks ||
-                             __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
-                            ok = 0;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(4);
-                    }
-                    s_ok = ok;
-                }
-                __syncthreads();
-                if (!s_ok) {
-                    if (tid == 0) atomicMin(info, -1);
-                    return;
-                }
-                for (int e = tid; e < kTile * nq; e += kThreads) {
-                    const int q = e >> 6, c = e & 63;
-                    xs[c][q] = (c < wbk) ? __hip_atomic_load(&xscratch[(int64_t)(q0 + q) * ldx + D.c0 + cb + c],
-                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                         : 0.0;
-                }
-                __syncthreads();
-            }
-            // rows strictly below the diagonal block: acc += L[k, cb..cb+wbk) x_jb
-            if (below) {
-#pragma unroll
-                for (int c = 0; c < kTile; ++c)
-#pragma unroll
-                    for (int q = 0; q < NQ; ++q) acc[q] = fma(lv[c], xs[c][q], acc[q]);
-            }
-        }
-        if (kv && !kdiag) {
-            const int row = rows[D.pi + k];
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-                if (q < nq) atomicAdd(&x[(int64_t)(q0 + q) * ldx + row], -acc[q]);
-        }
-    }
-}
-
-// SOLVE_CHAIN for ONE right-hand side: a dataflow of single waves, no workgroup barrier (but one when the
-// workgroup starts) and no flag in memory.
+// SOLVE_CHAIN (the block-column chains of a level's wide supernodes in ONE launch) for ONE right-hand side: a dataflow
+// of single waves, no workgroup barrier (but one when the workgroup starts) and no flag in memory.
 // A workgroup = eight waves = one of the launch's 256-row chunks, taken from the launch's ticket counter (tickets
 // follow the row order, so whatever a wave waits for belongs to a workgroup that has started).  Two waves share
 // each 64-row block of the chunk (lane = row): wave p of the pair streams the block columns jb = p, p + 2, ... to
@@ -1115,197 +949,13 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
     if (kv && k >= w) atomicAdd(&x[rows[D.pi + k]], -acc);
 }
 
-// SOLVE_CHAIN for many right-hand sides (nrhs >= 16): the same protocol (256-row chunks, pull form, the owner of a
-// block column publishes x_jb, tickets, flags per lane of passes) with 64 right-hand sides per pass over the panel
-// and every product on v_mfma_f64_16x16x4_f64, so that L is read once per 64 right-hand sides.  Wave v of a chunk
-// owns its rows 64 v .. 64 v + 63; the running update of a row lives in accumulator layout as
-// D[i = right-hand side][j = row] (lanes along the rows), started at -x for the rows of the supernode's own
-// columns, so that the owner's t_jb = x - sum is just the negated accumulator.  x_jb = inv(L_jj) t_jb is an MFMA
-// product too (t through LDS into operand layout); the rows below the supernode's columns are scattered at the end
-// with atomics, as in the one-vector kernel.
 static constexpr int kMrhsWideBlocks = 128;   // backward launches of at least this many blocks take 64 right-hand sides per pass
 static constexpr int kLdXm = kRhsM + 16;  // row stride of the staged x_jb / t_jb (doubles): conflict-free operand reads
 static constexpr int kSolveRowsM = kSolveRowsMrhs;   // rows of a chunk task of k_solve_blocks_mrhs (schedule.hpp)
 
-__global__ __launch_bounds__(kThreads, 1) void k_solve_chain_mrhs(const SnDesc* __restrict__ sn,
-                                                                  const PanelDesc* __restrict__ pds,
-                                                                  const int32_t* __restrict__ rows,
-                                                                  const double* __restrict__ L,
-                                                                  const double* __restrict__ dinv,
-                                                                  double* __restrict__ x, double* __restrict__ xscratch,
-                                                                  int nrhs, int ldx, int* __restrict__ flags, int epoch0,
-                                                                  int* __restrict__ info, int* __restrict__ ticket,
-                                                                  int wait_bias, int nchunks, int fstride) {
-    __shared__ double Di[kTile * kLdDiag];   // inverse diagonal block of the block column being solved (owner)
-    __shared__ double xs[kTile * kLdXm];     // x_jb: xs[c * kLdXm + q]
-    __shared__ double ts[kTile * kLdXm];     // t_jb: ts[row * kLdXm + q]
-    __shared__ int32_t s_ok, s_task;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, kq = lane >> 4;
-    if (tid == 0) s_task = atomicAdd(ticket, 1);
-    __syncthreads();
-    const int plane = s_task / nchunks;
-    const PanelDesc pd = pds[s_task - plane * nchunks];
-    flags += (int64_t)plane * fstride;
-    const SnDesc D = sn[pd.sn];
-    const int r = D.r, w = D.w, chunk = pd.jb, row0 = pd.row0;
-    const int nbc = (w + kTile - 1) / kTile;
-    const double* __restrict__ G = L + D.px;
-    const int wrow0 = row0 + 64 * wave;                 // first panel row of this wave
-    int prow[4];                                        // this lane's row of each 16-row fragment (-1: past the panel)
-#pragma unroll
-    for (int rf = 0; rf < 4; ++rf) prow[rf] = (wrow0 + 16 * rf + l15 < r) ? wrow0 + 16 * rf + l15 : -1;
-
-    for (int pass = plane; pass * kRhsM < nrhs; pass += kPassLanes) {
-        const int q0 = pass * kRhsM;
-        const int nq = min(kRhsM, nrhs - q0);
-        const int nfn = (nq + 15) >> 4;                 // 16-wide fragments of right-hand sides in use
-        const int epoch = epoch0 + pass / kPassLanes;
-        double4_s acc[4][4];                            // [fragment of right-hand sides][fragment of rows]
-#pragma unroll
-        for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-            for (int rf = 0; rf < 4; ++rf)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int q = 16 * nf + kq + 4 * v;
-                    const bool diag = prow[rf] >= 0 && prow[rf] < w && q < nq;
-                    acc[nf][rf][v] = diag ? -x[(int64_t)(q0 + q) * ldx + D.c0 + prow[rf]] : 0.0;
-                }
-        for (int jb = 0; jb < nbc; ++jb) {
-            const int cb = jb * kTile, wbk = min(kTile, w - cb);
-            const int owner = cb / kSolveRows;
-            if (chunk < owner) break;
-            // this wave's rows of L against block column jb, in B-operand layout (lane = (k >> 2 group, row)):
-            // issued before the wait for x_jb
-            const bool wave_below = wrow0 + 64 > cb + wbk && wrow0 < r;
-            double lv[4][16];
-            if (wave_below) {
-#pragma unroll
-                for (int rf = 0; rf < 4; ++rf)
-#pragma unroll
-                    for (int st = 0; st < 16; ++st) {
-                        const int c = 4 * st + kq;
-                        const bool ok = prow[rf] >= cb + wbk && c < wbk;
-                        lv[rf][st] = ok ? G[(int64_t)(cb + c) * r + prow[rf]] : 0.0;
-                    }
-            }
-            __syncthreads();  // xs / ts of the previous block column are free
-            if (chunk == owner) {
-                // t_jb = -(accumulator) of the block's 64 rows (one wave holds them) -> LDS, row-major
-                const int wv_o = (cb - row0) >> 6;
-                for (int e = tid; e < kTile * kTile; e += kThreads) {  // inverse diagonal block -> LDS
-                    Di[(e >> 6) * kLdDiag + (e & 63)] = dinv[(int64_t)(D.dslot + jb) * (kTile * kTile) + e];
-                }
-                if (wave == wv_o) {
-#pragma unroll
-                    for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-                        for (int rf = 0; rf < 4; ++rf)
-#pragma unroll
-                            for (int v = 0; v < 4; ++v)
-                                ts[(16 * rf + l15) * kLdXm + 16 * nf + kq + 4 * v] =
-                                    (16 * rf + l15 < wbk) ? -acc[nf][rf][v] : 0.0;
-                }
-                __syncthreads();
-                // x_jb = inv(L_jj) t_jb: wave n takes the right-hand sides 16 n .. 16 n + 15
-                if (wave < nfn) {
-                    double4_s xa[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-                    for (int st = 0; st < 16; ++st) {
-                        const int kr = 4 * st + kq;
-                        const double av = ts[kr * kLdXm + 16 * wave + l15];          // t[kr][q]
-#pragma unroll
-                        for (int rf = 0; rf < 4; ++rf) {
-                            const double bv = Di[kr * kLdDiag + 16 * rf + l15];      // inv[row][kr]
-                            xa[rf] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, xa[rf], 0, 0, 0);
-                        }
-                    }
-#pragma unroll
-                    for (int rf = 0; rf < 4; ++rf)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            const int q = 16 * wave + kq + 4 * v, c = 16 * rf + l15;
-                            xs[c * kLdXm + q] = xa[rf][v];
-                            if (c < wbk && q < nq) {
-                                __hip_atomic_store(&xscratch[(int64_t)(q0 + q) * ldx + D.c0 + cb + c], xa[rf][v],
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                x[(int64_t)(q0 + q) * ldx + D.c0 + cb + c] = xa[rf][v];
-                            }
-                        }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0)
-                    __hip_atomic_store(&flags[D.dslot + jb], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                if (tid == 0) {
-                    const unsigned long long t0 = wall_clock64();
-                    int ok = 1, spins = 0;
-                    while (__hip_atomic_load(&flags[D.dslot + jb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) -
-                               (epoch + wait_bias) < 0) {
-                        if ((++spins & 15) == 0 &&
-                            (wall_clock64() - t0 > kSolveSpinTicks ||
-                             __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
-                            ok = 0;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(4);
-                    }
-                    s_ok = ok;
-                }
-                __syncthreads();
-                if (!s_ok) {
-                    if (tid == 0) atomicMin(info, -1);
-                    return;
-                }
-                for (int e = tid; e < kTile * kRhsM; e += kThreads) {
-                    const int q = e >> 6, c = e & 63;
-                    xs[c * kLdXm + q] = (c < wbk && q < nq)
-                                            ? __hip_atomic_load(&xscratch[(int64_t)(q0 + q) * ldx + D.c0 + cb + c],
-                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                            : 0.0;
-                }
-                __syncthreads();
-            }
-            // rows below the diagonal block: accumulator += x_jb' L(rows, jb)'
-            if (wave_below) {
-#pragma unroll
-                for (int nf = 0; nf < 4; ++nf) {
-                    if (nf < nfn) {
-#pragma unroll
-                        for (int st = 0; st < 16; ++st) {
-                            const double av = xs[(4 * st + kq) * kLdXm + 16 * nf + l15];
-#pragma unroll
-                            for (int rf = 0; rf < 4; ++rf)
-                                acc[nf][rf] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, lv[rf][st], acc[nf][rf], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-        // rows below the supernode's own columns: x[row] -= accumulated update
-#pragma unroll
-        for (int rf = 0; rf < 4; ++rf) {
-            if (prow[rf] >= w) {
-                const int xrow = rows[D.pi + prow[rf]];
-#pragma unroll
-                for (int nf = 0; nf < 4; ++nf)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int q = 16 * nf + kq + 4 * v;
-                        if (q < nq) atomicAdd(&x[(int64_t)(q0 + q) * ldx + xrow], -acc[nf][rf][v]);
-                    }
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
-// Forward chain launch for many right-hand sides, round 3 (replaces k_solve_chain_mrhs's protocol: flag + barrier +
-// staged copy per block column, 35 us per block column on the parabolic_fem-class root): the armed buffer of the
-// one-vector kernels -- the data is the flag -- and two kinds of workgroups, taken by ticket, producers first:
+// Forward chain launch for many right-hand sides: the armed buffer of the one-vector kernels -- the data is the flag --
+// and two kinds of workgroups, taken by ticket, producers first:
 //   * one per BLOCK COLUMN jb of a wide supernode (task row0 < 0), the counterpart of k_bsolve_block_mrhs's chain form:
 //       T = B_jb - sum_{k < jb} L(jb, k) X_k,     X_jb = inv(L_jj) T
 //     with the COLUMNS of the earlier blocks as the contraction index: wave v takes columns 16 v .. 16 v + 15 of every
@@ -1873,16 +1523,24 @@ SolveGates read_solve_gates() {
     auto num = [](const char* name, int& v) {
         const char* e = std::getenv(name);
         if (e && *e) v = std::atoi(e);
+        return e && *e;
     };
     int m = 0;
     num("PARSY_MRHS_MIN", m);
-    if (m > 0) g.mrhs_min = g.chain_mrhs_min = m;
+    if (m > 0) {
+        g.mrhs_min = m;
+        g.chain_mrhs_min = std::min(m, g.chain_mrhs_min);
+    }
     num("PARSY_BMRHS_MIN", g.bmrhs_min);
     const char* w = std::getenv("PARSY_BMRHS_WIDE_ONLY");
     g.bmrhs_wide_only = !(w && w[0] == '0');
     num("PARSY_BCHAIN_MIN_BLOCKS", g.bchain_min_blocks);
     num("PARSY_SMALL_MRHS_HALVES_MIN", g.small_halves_min);
     num("PARSY_SUB_MRHS_MIN", g.sub_mrhs_min);
+    g.xt_min_set = num("PARSY_XT_MIN", g.xt_min);
+    const char* st = std::getenv("PARSY_DEBUG_SOLVE_STALL");
+    g.wait_bias = (st && st[0] == '1') ? (1 << 20) : 0;
+    num("PARSY_SUB_ABL", g.sub_abl);
     return g;
 }
 
@@ -1941,38 +1599,20 @@ void launch_solve_arm_wide(const DevicePattern& P, int npairs, double* xscratch,
                        xscratch, nrhs, (int64_t)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), P.sinfo, P.stickets, ntickets);
 }
 
-void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
-                        double* x, double* xscratch, int nrhs, int ldx, int epoch0, int ticket, int wait_bias,
-                        hipStream_t stream) {
+// One right-hand side: xscratch was armed by the caller (solve_arm_handoff)
+void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv, double* x,
+                        double* xscratch, int ticket, int wait_bias, hipStream_t stream) {
     if (count <= 0) return;
-    if (nrhs >= P.gates.chain_mrhs_min) {
-        const int lanes_m = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
-        witness_launch(kWSolveChainMrhs);
-        hipLaunchKernelGGL(k_solve_chain_mrhs, dim3(count * lanes_m), dim3(kThreads), 0, stream, P.sn,
-                           P.solve_panels + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, P.flags, epoch0, P.sinfo,
-                           P.stickets + ticket, wait_bias, count, P.flag_stride);
-        return;
-    }
-    const int nq = nrhs == 1 ? 1 : kRhs;
-    const int lanes = std::min(kPassLanes, (nrhs + nq - 1) / nq);
-    if (nrhs == 1) {   // (xscratch was armed by the caller: solve_arm_handoff)
-        if (count <= kChainFewChunks) {
-            witness_launch(kWSolveChainW2);
-            hipLaunchKernelGGL(k_solve_chain_w<2>, dim3(2 * count), dim3(kChainThreads), 0, stream, P.sn,
-                               P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
-                               wait_bias);
-        } else {
-            witness_launch(kWSolveChainW4);
-            hipLaunchKernelGGL(k_solve_chain_w<4>, dim3(count), dim3(kChainThreads), 0, stream, P.sn,
-                               P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
-                               wait_bias);
-        }
+    if (count <= kChainFewChunks) {
+        witness_launch(kWSolveChainW2);
+        hipLaunchKernelGGL(k_solve_chain_w<2>, dim3(2 * count), dim3(kChainThreads), 0, stream, P.sn,
+                           P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
+                           wait_bias);
     } else {
-        static_assert(kRhs == 8, "witness entry k_solve_chain<8>");
-        witness_launch(kWSolveChain8);
-        hipLaunchKernelGGL(k_solve_chain<kRhs>, dim3(count * lanes), dim3(kThreads), 0, stream, P.sn,
-                           P.solve_panels + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, P.flags, epoch0,
-                           P.sinfo, P.stickets + ticket, wait_bias, count, P.flag_stride);
+        witness_launch(kWSolveChainW4);
+        hipLaunchKernelGGL(k_solve_chain_w<4>, dim3(count), dim3(kChainThreads), 0, stream, P.sn,
+                           P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket,
+                           wait_bias);
     }
 }
 
@@ -2873,7 +2513,7 @@ void launch_bsolve_one(const DevicePattern& P, int n, const double* L, double* x
 
 // ---------------------------------------------------------------------------
 // Backward solve, many right-hand sides (from mrhs_min() on): the counterpart of k_solve_small_mrhs /
-// k_solve_chain_mrhs -- 64 right-hand sides per pass over L instead of 4, every product on the matrix cores.
+// k_solve_blocks_mrhs -- 64 right-hand sides per pass over L instead of 4, every product on the matrix cores.
 // One workgroup (4 waves) per block of <= 64 columns, as k_bsolve_block:
 //     T = Y_blk - L(below, blk)' X(below)        (64 columns x 64 right-hand sides)
 // with the panel ROWS as the contraction index of v_mfma_f64_16x16x4_f64: lane (c, kk) holds L[k0 + kk][cb + c]

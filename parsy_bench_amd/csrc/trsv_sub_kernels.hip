@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "kernels.hpp"
 
@@ -475,11 +474,6 @@ __global__ __launch_bounds__(256) void k_bsolve_sub_mrhs(const SubMember* __rest
     }
 }
 
-static int sub_abl() {
-    const char* e = std::getenv("PARSY_SUB_ABL");
-    return e && *e ? std::atoi(e) : 0;
-}
-
 // LDS a workgroup of these kernels may ask for: 64 KB, or what solve_sub_prepare was granted
 static int g_sub_lds_cap = 64 * 1024;
 
@@ -504,7 +498,7 @@ void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doubl
     witness_launch(kWSolveSubMrhs);
     hipLaunchKernelGGL(k_solve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
                        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs,
-                       (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, sub_abl());
+                       (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, P.gates.sub_abl);
 }
 
 void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const double* L, double* x, int nrhs, int ldx,
@@ -517,7 +511,7 @@ void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doub
     witness_launch(kWBsolveSubMrhs);
     hipLaunchKernelGGL(k_bsolve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
                        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs, 1u,
-                       (int64_t)ldx, sub_abl());
+                       (int64_t)ldx, P.gates.sub_abl);
 }
 
 // Once per plan: a workgroup of four waves on the largest trees may need more than 64 KB of LDS -- ask for it (up to

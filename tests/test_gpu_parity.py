@@ -170,11 +170,10 @@ def test_product_gate_with_row_major_x_forced(api, oracle, monkeypatch, name, nr
 
 
 @pytest.mark.parametrize("nrhs", [3, 19])
-def test_solve_flag_protocol_chain_matches_oracle(api, oracle, monkeypatch, nrhs):
-    """PARSY_OLD_MRHS_CHAIN=1: the chain launches of rounds 1-2 (flags + staged copies per block column; 8 right-hand
-    sides per pass below 16) stay available as a fallback and stay correct.  The witness proves which ran: below
-    PARSY_MRHS_MIN=16 k_solve_chain<8>, from there on k_solve_chain_mrhs, never the armed-buffer chain."""
-    monkeypatch.setenv("PARSY_OLD_MRHS_CHAIN", "1")
+def test_solve_mrhs_min_16_chain_matches_oracle(api, oracle, monkeypatch, nrhs):
+    """PARSY_MRHS_MIN=16 moves the narrow supernodes' threshold only: the wide supernodes' chain still takes
+    k_solve_blocks_mrhs (armed buffer) from 2 right-hand sides on, and no retired flag-protocol kernel runs (the witness
+    has no entry for them).  Below the threshold the narrow supernodes keep the 8-per-pass kernels."""
     monkeypatch.setenv("PARSY_SOLVE_ONE", "0")
     monkeypatch.setenv("PARSY_MRHS_MIN", "16")
     A, sym, plan, lv, lo = _factor_both(api, oracle, "lap30")
@@ -184,9 +183,10 @@ def test_solve_flag_protocol_chain_matches_oracle(api, oracle, monkeypatch, nrhs
     X, _ = plan.solve(lo, B)
     assert plan.solve_status() == 0
     seen = api.kernel_launches()
-    assert seen["k_solve_chain<8>" if nrhs < 16 else "k_solve_chain_mrhs"] > 0, _launched(seen)
-    assert seen["k_solve_blocks_mrhs<true>"] == seen["k_solve_blocks_mrhs<false>"] == seen["k_solve_arm_wide"] == 0
-    if nrhs < 16:   # (the narrow supernodes: the 8-per-pass kernels below the threshold as well)
+    assert seen["k_solve_blocks_mrhs<true>" if nrhs <= 16 else "k_solve_blocks_mrhs<false>"] > 0, _launched(seen)
+    assert "k_solve_chain<8>" not in seen and "k_solve_chain_mrhs" not in seen, sorted(seen)
+    assert seen["k_solve_chain_w<2>"] == seen["k_solve_chain_w<4>"] == 0, _launched(seen)
+    if nrhs < 16:   # (the narrow supernodes: the 8-per-pass kernels below the threshold)
         assert seen["k_solve_small"] > 0 and not any(seen[f"k_solve_small_mrhs<{w}>"] for w in (16, 32, 64)), _launched(seen)
     for q in range(nrhs):
         xo = oracle.blocked_lsolve(sym, lo, B[:, q], "serial")
@@ -1510,8 +1510,6 @@ _COVERAGE = [
     ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_BCHAIN_MIN_BLOCKS": "16", "PARSY_BMRHS_WIDE_ONLY": "0"}, 19, False,
      ["k_bsolve_chain_mrhs", "k_bsolve_block_mrhs<1>", "k_bsolve_tiny_mrhs"]),
     ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_SMALL_MRHS_HALVES_MIN": "1"}, 70, True, ["k_solve_small_mrhs<64,true>"]),
-    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_OLD_MRHS_CHAIN": "1", "PARSY_MRHS_MIN": "16"}, 3, True, ["k_solve_chain<8>"]),
-    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_OLD_MRHS_CHAIN": "1"}, 19, True, ["k_solve_chain_mrhs"]),
     ("lap30", {"PARSY_SOLVE_ONE": "2"}, 1, True, ["k_solve_one<1>"]),
     ("lap30", {"PARSY_SOLVE_ONE": "2"}, 3, True, ["k_solve_one<4>"]),
     ("lap30", {"PARSY_SOLVE_ONE": "2"}, 8, True, ["k_solve_one<8>"]),
@@ -1532,16 +1530,16 @@ _NOT_COVERED = {
 _PLAN_VARIABLES = ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED")   # (read when the plan is made; the others per solve)
 
 
-def test_every_solve_kernel_is_reached(api, oracle, monkeypatch):
+def test_coverage_matrix_reaches_every_solve_kernel(api, oracle, monkeypatch):
     """Every cell of _COVERAGE against the oracle / the checker (every column) and its witness; the union of the cells'
-    launches covers the witness table but the listed exclusions.  PARSY_OLD_MRHS_CHAIN=1 reaches the flag-protocol kernels;
-    parsy_rhs_ones_device is k_rhs_ones (against the oracle's rhs_init_blocked)."""
+    launches covers the witness table but the listed exclusions.  parsy_rhs_ones_device is k_rhs_ones (against the
+    oracle's rhs_init_blocked)."""
     import torch
     union = {}
     plans = {}
     for name, env, nrhs, fwd, want in _COVERAGE:
         for k in ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED", "PARSY_XT_MIN", "PARSY_BCHAIN_MIN_BLOCKS", "PARSY_BMRHS_WIDE_ONLY",
-                  "PARSY_SMALL_MRHS_HALVES_MIN", "PARSY_OLD_MRHS_CHAIN", "PARSY_MRHS_MIN", "PARSY_SUB_MRHS_MIN"):
+                  "PARSY_SMALL_MRHS_HALVES_MIN", "PARSY_MRHS_MIN", "PARSY_SUB_MRHS_MIN"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)

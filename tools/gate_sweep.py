@@ -32,7 +32,7 @@ GATES = {
     "many-RHS subtree / band kernels (kSubTier*)": [{"PARSY_SUB_MRHS_MIN": "0"}, {"PARSY_SUB_TIER_MIN_TREES": "0"},
                                                     {"PARSY_SUB_TIER_MIN_TREES": "512"}, {"PARSY_SUB_TIER_MIN_TREES": "128"}],
     "row-major X from 16 right-hand sides (200 entries per row)": [{"PARSY_XT_MIN": "0"}, {"PARSY_XT_MIN": "16"}],
-    "many-RHS kernels from 6 / 2 (PARSY_MRHS_MIN)": [{"PARSY_MRHS_MIN": "16"}],
+    "narrow supernodes' many-RHS kernels from 6 (PARSY_MRHS_MIN)": [{"PARSY_MRHS_MIN": "16"}],
     "backward rows below (kBelow*)": [{"PARSY_BSOLVE_BELOW": "0"}, {"PARSY_BSOLVE_BELOW": "2"}],
     "dense update kernel (kDense*)": [{"PARSY_BIG_DENSE": "0"}, {"PARSY_BIG_DENSE": "2"}],
     "two chain launches per level (kChainSplitAutoFlops)": [{"PARSY_CHAIN_SPLIT": "0"}, {"PARSY_CHAIN_SPLIT": "2"}],
