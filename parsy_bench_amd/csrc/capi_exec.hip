@@ -15,6 +15,7 @@
 
 #include "../../include/parsy_amd.h"
 #include "errors.hpp"
+#include "hip_check.hpp"
 #include "dist.hpp"
 #include "executor.hpp"
 #include "inspector.hpp"
@@ -23,15 +24,6 @@
 using parsy::set_last_error;
 
 namespace {
-
-#define CAPI_HIP(call, ret)                                                          \
-    do {                                                                             \
-        hipError_t e_ = (call);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));       \
-            return ret;                                                              \
-        }                                                                            \
-    } while (0)
 
 double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -669,10 +661,10 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
         return -1;
     }
     const parsy::Schedule& S = pl->S;
-    CAPI_HIP(hipSetDevice(pl->device), -1);
-    if (!pl->h_values_dev) CAPI_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8), -1);
-    if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
-    CAPI_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice), -1);
+    PARSY_HIP(hipSetDevice(pl->device));
+    if (!pl->h_values_dev) PARSY_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8));
+    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
     // Small factors: kernels, then one download.  Large ones (PARSY_HOST_PIPELINE=0: never): the download of every
     // band of levels runs BEHIND the kernels of the levels above it -- a worker thread copies the runs of lValues
     // that a band has made final while this thread's stream goes on (Flan-class: 19.4 GB at PCIe speed take as long
@@ -682,9 +674,9 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
     const bool pipeline_on = !(pe && pe[0] == '0'), pipeline_forced = pe && pe[0] == '2';
     if (!pipeline_on || (!pipeline_forced && S.xsize * 8 < (int64_t)256 << 20) || pl->profile || S.cnlevels < 1) {
         if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
-        CAPI_HIP(hipDeviceSynchronize(), -1);
+        PARSY_HIP(hipDeviceSynchronize());
         if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-        CAPI_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost), -1);
+        PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
         return 0;
     }
     if (!pl->h_ready) {
@@ -716,9 +708,9 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
             evs.erase(std::remove(evs.begin(), evs.end(), (hipEvent_t) nullptr), evs.end());
             undo();
             if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
-            CAPI_HIP(hipDeviceSynchronize(), -1);
+            PARSY_HIP(hipDeviceSynchronize());
             if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-            CAPI_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost), -1);
+            PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
             return 0;
         }
         pl->h_stream = hs;
@@ -793,17 +785,17 @@ int parsy_solve_host(parsy_plan* pl, const double* lValues, double* x, int nrhs,
         return -1;
     }
     const parsy::Schedule& S = pl->S;
-    CAPI_HIP(hipSetDevice(pl->device), -1);
-    if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
+    PARSY_HIP(hipSetDevice(pl->device));
+    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
     const int64_t need = (int64_t)ldx * nrhs;
-    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
-    CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
-    CAPI_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice), -1);
+    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
     if (parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-    CAPI_HIP(hipDeviceSynchronize(), -1);
+    PARSY_HIP(hipDeviceSynchronize());
     if (parsy_solve_status(pl) != 0) return -1;  // (x stays untouched: it would not be the solution)
     if (seconds) *seconds = parsy_last_solve_ms(pl) * 1e-3;
-    CAPI_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost), -1);
+    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -832,7 +824,7 @@ int parsy_copy_segments_device(double* d_dst, const double* d_src, const int64_t
         return -1;
     }
     parsy::launch_copy_segments(d_dst, d_src, d_dst_off, d_src_off, d_len, nseg, (hipStream_t)stream);
-    CAPI_HIP(hipGetLastError(), -1);
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
@@ -841,10 +833,10 @@ int parsy_rhs_ones_device(parsy_plan* pl, const double* d_lValues, double* d_b, 
         set_last_error("parsy_rhs_ones_device: null argument or plan without a device");
         return -1;
     }
-    CAPI_HIP(hipSetDevice(pl->device), -1);
-    CAPI_HIP(hipMemsetAsync(d_b, 0, (size_t)pl->S.n * sizeof(double), (hipStream_t)stream), -1);
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipMemsetAsync(d_b, 0, (size_t)pl->S.n * sizeof(double), (hipStream_t)stream));
     parsy::launch_rhs_ones(pl->dp, pl->S.nsuper, pl->S.max_rows, d_lValues, d_b, (hipStream_t)stream);
-    CAPI_HIP(hipGetLastError(), -1);
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
@@ -859,25 +851,25 @@ int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs
         return -1;
     }
     const parsy::Schedule& S = pl->S;
-    CAPI_HIP(hipSetDevice(pl->device), -1);
-    if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
+    PARSY_HIP(hipSetDevice(pl->device));
+    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
     const int64_t need = (int64_t)ldx * nrhs;
-    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
-    CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
-    CAPI_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice), -1);
+    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
     double sec = 0;
     if (forward) {
         if (parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-        CAPI_HIP(hipDeviceSynchronize(), -1);
+        PARSY_HIP(hipDeviceSynchronize());
         if (parsy_solve_status(pl) != 0) return -1;
         sec += parsy_last_solve_ms(pl) * 1e-3;
     }
     if (parsy::plan_backsolve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-    CAPI_HIP(hipDeviceSynchronize(), -1);
+    PARSY_HIP(hipDeviceSynchronize());
     if (parsy_solve_status(pl) != 0) return -1;
     sec += parsy_last_solve_ms(pl) * 1e-3;
     if (seconds) *seconds = sec;
-    CAPI_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost), -1);
+    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -923,17 +915,17 @@ int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lVa
         set_last_error("parsy_solve_spd_host: need nrhs >= 1 and leading dimensions >= n");
         return -1;
     }
-    CAPI_HIP(hipSetDevice(pl->device), -1);
-    if (!pl->h_values_dev) CAPI_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8), -1);
-    if (!pl->h_L_dev) CAPI_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8), -1);
+    PARSY_HIP(hipSetDevice(pl->device));
+    if (!pl->h_values_dev) PARSY_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8));
+    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
     const int64_t need = std::max<int64_t>((int64_t)S.n * nrhs, 1);
-    CAPI_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need), -1);
+    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
     const size_t row = (size_t)S.n * 8;
-    CAPI_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice), -1);
-    CAPI_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice), -1);
-    if (S.n > 0) CAPI_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice), -1);
+    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice));
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    CAPI_HIP(hipEventCreate(&e0), -1);
+    PARSY_HIP(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) {
         (void)hipEventDestroy(e0);
         set_last_error("parsy_solve_spd_host: hipEventCreate failed");
@@ -954,7 +946,7 @@ int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lVa
     // (max_steps == 0 without steps / berr: nothing synchronised inside the call, so the solves' status is read here)
     if (parsy_solve_status(pl) != 0) return -1;
     if (seconds) *seconds = ms * 1e-3;
-    if (S.n > 0) CAPI_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost), -1);
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -14,15 +14,13 @@
 
 #include <climits>
 
+#include "device_util.hpp"
 #include "kernels.hpp"
 
 namespace parsy {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
 static constexpr int kThreads = 256;
 static constexpr int kLdSub = kSub + 1;   // padded leading dimension of a wave's sub-tile in LDS
-static constexpr int kLdDiag = kTile + 1; // padded leading dimension of a diagonal block in LDS
 
 #ifdef PARSY_BIGSTAMPS
 // diagnostic build only (tools/big_timeline.py): shader-clock stamps of the phases of k_chol_big's chunk loop, for
@@ -98,10 +96,6 @@ void launch_scatter_a(const double* values, const int64_t* a_dst, double* L, int
 typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) double lds_f64;
 static constexpr int kPotrfScratch = 2 * 4 * kTile;
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src_lane),
-                            __builtin_amdgcn_readlane(__double2loint(v), src_lane));
-}
 __device__ __forceinline__ void potrf64_regs(double (&a)[4][4], double* __restrict__ scr, int ti, int tj,
                                              int nb, int& bad, double* __restrict__ inv_out = nullptr) {
     const bool lower = ti >= tj;
@@ -195,124 +189,6 @@ __device__ __forceinline__ void potrf64_regs(double (&a)[4][4], double* __restri
                     for (int k = 0; k < 4; ++k) a[ri][ci] = fma(-li[ri][k], lc[ci][k], a[ri][ci]);
         }
         PPROBE(4);
-    }
-}
-
-// Step (a) of potrf64_panel, by ONE wave, out of line: the sweep keeps ~30 wave-uniform multipliers in scalar
-// registers at a time, which the walker around it has none to spare for (inlined, the compiler parked them in
-// vector lanes: 1 000 extra lane moves per panel).  Returns the first column (1-based, within the tile) of the panel
-// whose pivot was not positive, or 0.
-__device__ __noinline__ int potrf64_panel_sweep(lds_f64* __restrict__ Cb, int c0, int nb, lds_f64* __restrict__ inv_out,
-                                                lds_f64* __restrict__ scr) {
-    const int lane = threadIdx.x & 63;
-    // lane l holds row c0 + l of the tile (the rows above the panel have nothing in it), so that the pivot of
-    // column j sits in lane j and the multiplier of column c in lane c: constant lane numbers
-    const int row = c0 + lane;
-    const bool live = row < nb;          // (rows past nb: an identity, never stored)
-    // column c0 + j of this lane's row: j * kLdSub doubles from `mine` (a panel lies inside one 32-column half)
-    const int rowc = min(row, kTile - 1);
-    lds_f64* __restrict__ mine = Cb + ((rowc >> 5) * 2 + (c0 >> 5)) * (kSub * kLdSub) + (c0 & 31) * kLdSub + (rowc & 31);
-    double x[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const double v = mine[j * kLdSub];
-        x[j] = (lane >= j && live && c0 + j < nb) ? v : ((lane == j) ? 1.0 : 0.0);
-    }
-    double mydiag = 1.0, myinv = 1.0;    // lane j: L[j][j] and its reciprocal
-    // Column j: pivot and the multiplier of column j + 1 -- the critical chain -- reach the lanes as wave-uniform
-    // values (v_readlane); the multipliers of the later columns go through 16 doubles of LDS (lanes 0..15 park the
-    // scaled column, everybody reads the ones it needs two at a time as broadcasts): a third of the instructions of
-    // reading every multiplier lane by lane, and a single wave is bound by the instructions it issues.
-    typedef __attribute__((address_space(3))) double2_t lds_f64x2;
-    lds_f64x2* __restrict__ bc = (lds_f64x2*)scr;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const double d = readlane_f64(x[j], j);
-        // 1/sqrt(d): hardware estimate + one correction step (as potrf64_regs); a pivot that is not positive
-        // leaves a NaN on the diagonal, which is how it is found below
-        const double y0 = __builtin_amdgcn_rsq(d);
-        const double e = fma(-d * y0, y0, 1.0);
-        const double inv = fma(y0 * e, fma(e, 0.375, 0.5), y0);
-        const double ljj = d * inv;
-        mydiag = (lane == j) ? ljj : mydiag;
-        myinv = (lane == j) ? inv : myinv;
-        x[j] = (lane == j) ? ljj : x[j] * inv;
-        if (j + 1 < 16) {
-            if (j + 2 < 16 && lane < 16) scr[lane] = x[j];
-            const double l1 = readlane_f64(x[j], j + 1);
-            x[j + 1] = fma(-x[j], l1, x[j + 1]);
-            // (pairs (c, c + 1) from an even c on: 16-byte broadcast reads)
-#pragma unroll
-            for (int c = (j + 2) & ~1; c < 16; c += 2) {
-                const double2_t l = bc[c >> 1];
-                if (c >= j + 2) x[c] = fma(-x[j], l[0], x[c]);
-                x[c + 1] = fma(-x[j], l[1], x[c + 1]);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);   // (columns one after the other: hoisted reads cost registers the caller must save)
-    }
-    const bool in_block = lane < 16 && row < nb;
-    const unsigned long long badmask = __ballot(in_block && !(mydiag > 0.0));
-    if (lane < 16) inv_out[row] = in_block ? myinv : 1.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-        if (lane >= j && live && c0 + j < nb) mine[j * kLdSub] = x[j];
-    return badmask != 0 ? c0 + (int)__builtin_ctzll(badmask) + 1 : 0;
-}
-
-// ---------------------------------------------------------------------------
-// POTRF of a 64x64 diagonal tile held in LDS (sub-tile layout of the tile kernel: 4 x 32x33, lower triangle valid), in
-// place, by 16-column panels (the walker of the chain launch; reference dpotrf at parallel_PB_Cholesky_05.h:204):
-//   (a) wave 0 factors the panel with ONE ROW PER LANE: lane i keeps its 16 entries of the panel in registers; per
-//       column the pivot and the multipliers of the later columns reach all lanes as wave-uniform values
-//       (v_readlane), so a column costs one pivot chain + (15 - j) independent multiply-adds per lane, and the rows
-//       below the diagonal block are solved by the same instructions (the TRSM of the panel comes for free) -- no
-//       barrier, no LDS traffic inside a panel;
-//   (b) the panel goes back to LDS, one barrier;
-//   (c) the four waves subtract P_i P_j' from the 16x16 blocks to the right of the panel (v_mfma_f64_16x16x4_f64,
-//       K = 16: four products per block, at most two blocks per wave), one barrier.
-// 4 barrier pairs and 64 pivots in sequence instead of 16 steps of (4 pivots + 4x4 solve + publish + barrier + rank-4
-// update) over the 256 threads' register blocks (potrf64_regs above, still the SMALL kernel's).  Rows / columns past
-// nb are treated as an identity.  `bad` receives (1-based, lane 0 of wave 0 only) the first column whose pivot was
-// not positive; inv_out (64 doubles of LDS) the reciprocals of the factor's diagonal; scr: 16 doubles of LDS, 16-byte
-// aligned.  A workgroup barrier must precede the call; one ends it.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void potrf64_panel(double* __restrict__ Cb, int nb, int& bad, double* __restrict__ inv_out,
-                                              double* __restrict__ scr) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, kq = lane >> 4;
-    auto cell = [&](int i, int c) -> double& {
-        return Cb[((i >> 5) * 2 + (c >> 5)) * (kSub * kLdSub) + (c & 31) * kLdSub + (i & 31)];
-    };
-    bad = 0;
-    const int np = (nb + 15) >> 4;
-    for (int p = 0; p < np; ++p) {
-        const int c0 = 16 * p;
-        if (wave == 0) {
-            const int pb = potrf64_panel_sweep((lds_f64*)Cb, c0, nb, (lds_f64*)inv_out, (lds_f64*)scr);
-            if (lane == 0 && bad == 0) bad = pb;   // (the first of the whole block: later panels see its NaNs)
-        }
-        __syncthreads();
-        // blocks (bi, bj), p < bj <= bi < np, in the order (p+1,p+1), (p+2,p+1), (p+2,p+2), ...: block q to wave q % 4
-        int q = 0;
-        for (int bi = p + 1; bi < np; ++bi)
-            for (int bj = p + 1; bj <= bi; ++bj, ++q) {
-                if ((q & 3) != wave) continue;
-                double4_t acc = {0, 0, 0, 0};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double av = cell(16 * bi + l15, c0 + kq + 4 * u);
-                    const double bv = cell(16 * bj + l15, c0 + kq + 4 * u);
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int i = 16 * bi + kq + 4 * v, c = 16 * bj + l15;
-                    if (i >= c && i < nb) cell(i, c) -= acc[v];   // (rows past nb may be rows of the panel below the block)
-                }
-            }
-        __syncthreads();
     }
 }
 
@@ -655,26 +531,20 @@ __device__ __forceinline__ void lower_bound3(const int32_t* __restrict__ a, int 
 }
 
 
-// X := B inv(Ljj') on the 64 rows of the LDS tile `tile` (sub-tile layout of the tile kernel: 4 x
-// 32x33); Dg holds Ljj (Dg[c * 65 + i], zeros above the diagonal), invd the reciprocals of its
-// diagonal.  One workgroup barrier is expected before the call, one ends it.  The walker inlines
-// it (values in flight across it); the other two places share one out-of-line copy, which keeps
-// their register allocation apart from the stream's.
-// inverses of the four 16x16 diagonal sub-blocks of Ljj, one column per thread, written
+// inverses of the four 16x16 diagonal sub-blocks of Ljj (Dg[c * 65 + i], zeros above the diagonal), written
 // transposed into the (unused) strict upper triangle of the same sub-block:
 // Dg[(16b+r)*ld + 16b+c] = inv(L_bb)[r][c] for r > c.  A TRSM against Ljj is then all products
 // (what a blocked dtrsm does): X_b = (B_b - sum_{p<b} X_p L_bp') inv(L_bb)'.  Ends with a workgroup barrier.
 // (round 5) One WAVE per 16 x 16 sub-block, one ENTRY per lane, by halves -- inv [A 0; B C] = [inv A, 0; -inv(C) B inv(A),
 // inv C]: the four 4 x 4 diagonal blocks by substitution (lane = (block, row, column)), then the two 4 x 4 and the one
 // 8 x 8 off-diagonal blocks as two small products each (T = B inv(A), then -inv(C) T; T goes through 64 doubles of scratch).
-// Five LDS round trips of a few reads each: about 0.5 us.  The form before (kept below, PARSY_INVERT16_COLUMNS) gave a
+// Five LDS round trips of a few reads each: about 0.5 us.  The form before (git history, docs/history.md) gave a
 // column to a thread and walked its 16 rows one after the other, every second multiply-add waiting for its own LDS
 // read: 3.7 us of the walker's 28.6-us step and ~2 us of every other tile's TRSM.  Scratch: a 16 x 16 block of Dg ABOVE the
 // block diagonal (rows of an earlier sub-block, columns of a later one: zeros that nothing reads -- the TRSM takes
 // L(b, p), p < b, from below the diagonal and the inverses from the upper triangles of the diagonal sub-blocks).
 // Divisions: none (invd holds the reciprocals of the diagonal).
 __device__ __forceinline__ void invert_diag_blocks(lds_f64* __restrict__ Dg, lds_f64* __restrict__ invd) {
-#ifndef PARSY_INVERT16_COLUMNS
     const int tid = threadIdx.x, lane = tid & 63;
     const int b = __builtin_amdgcn_readfirstlane(tid >> 6);   // sub-block = wave
     lds_f64* __restrict__ B0 = Dg + (16 * b) * kLdDiag + 16 * b;      // L[i][c] = B0[c * ld + i]; W[r][c] (r > c) -> B0[r * ld + c]
@@ -748,33 +618,17 @@ __device__ __forceinline__ void invert_diag_blocks(lds_f64* __restrict__ Dg, lds
         for (int m = 0; m < 8; ++m) w = fma(i > m ? wc[m] : (i == m ? di : 0.0), tt[m], w);
         B0[(8 + i) * kLdDiag + j] = -w;
     }
-#else
-    const int tid = threadIdx.x;
-    if (tid < kTile) {
-        const int b16 = (tid >> 4) * 16, c = tid & 15;
-        double y[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) y[k] = (k == c) ? invd[b16 + k] : 0.0;
-#pragma unroll
-        for (int rr = 1; rr < 16; ++rr) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int k = 0; k < rr; ++k) sacc = fma(Dg[(b16 + k) * kLdDiag + b16 + rr], y[k], sacc);
-            y[rr] = (rr > c) ? -sacc * invd[b16 + rr] : y[rr];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of the sub-block precede the in-place writes
-#pragma unroll
-        for (int rr = 1; rr < 16; ++rr)
-            if (rr > c) Dg[(b16 + rr) * kLdDiag + b16 + c] = y[rr];
-    }
-#endif
     // a barrier for LDS alone: vector-memory loads the caller has in flight (the walker's next diagonal tile) stay
     // in flight (__syncthreads() would wait for them: 1.5 us of the walker's step)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
-template <bool INVERT = true>
+// X := B inv(Ljj') on the 64 rows of the LDS tile `tile` (sub-tile layout of the tile kernel: 4 x
+// 32x33); Dg holds Ljj (Dg[c * 65 + i], zeros above the diagonal), invd the reciprocals of its
+// diagonal.  One workgroup barrier is expected before the call, one ends it.  The walker calls it out of
+// line (invert_and_trsm below), which keeps its register allocation apart from the walker's own; the body stays
+// a separate inline function because folding the two changes the compiler's operand order in four instructions.
 __device__ __forceinline__ void invert_and_trsm_inline(lds_f64* __restrict__ tile, lds_f64* __restrict__ Dg,
                                                        lds_f64* __restrict__ invd, int nb) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -782,7 +636,7 @@ __device__ __forceinline__ void invert_and_trsm_inline(lds_f64* __restrict__ til
     auto cell = [&](int i, int c) -> lds_f64& {
         return tile[((i >> 5) * 2 + (c >> 5)) * (kSub * kLdSub) + (c & 31) * kLdSub + (i & 31)];
     };
-    if (INVERT) invert_diag_blocks(Dg, invd);   // (false: the caller has done it)
+    invert_diag_blocks(Dg, invd);
     // each wave owns 16 rows of the tile for the whole solve: no barrier between blocks
     const int rbase = 16 * wave;
     for (int b16 = 0; b16 < nb; b16 += 16) {
@@ -1489,17 +1343,8 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
             const int f_diag = D.tflag0 + J * nbc + J;
             const int row1 = col0 + kTile;  // tiles (J+1,J) and (J+1,J+1)
             const int f_b = D.tflag0 + (J + 1) * nbc + J, f_c = f_b + 1;
-            // prepared tile (J+1,J) -> registers -> T, prepared diagonal tile (J+1,J+1) -> registers
-            double bv[kSub * kSub / 64], cpart[kSub * kSub / 64];
-            auto load_b = [&]() {  // tile (J+1,J), all four quadrants
-                const int sr = row1 + kSub * wa, nr = min(kSub, r - sr), scb = col0 + kSub * wb;
-#pragma unroll
-                for (int q = 0; q < kSub * kSub / 64; ++q) {
-                    const int e = q * 64 + lane;
-                    const int cc = e >> 5, rr = e & 31;
-                    bv[q] = (rr < nr) ? ld_sc1(&G[(int64_t)(scb + cc) * ld + sr + rr]) : 0.0;
-                }
-            };
+            // prepared diagonal tile (J+1,J+1) -> registers (tile (J+1,J) goes straight into the TRSM's accumulators below)
+            double cpart[kSub * kSub / 64];
             auto load_c = [&]() {  // diagonal tile (J+1,J+1), lower part
                 const int sr = row1 + kSub * wa, nr = min(kSub, r - sr);
                 const int scc = row1 + kSub * wb, ncc = min(kSub, w - scc);
@@ -1519,7 +1364,6 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
 #ifdef PARSY_STAMPS
             if (tid == 0 && J < 512) g_trace[J * 16 + 8] = clock64();
 #endif
-#ifndef PARSY_WALKER_POTRF_PANEL   // the 4-columns-per-step form over the 256 threads' register blocks (default)
             double a[4][4];
 #pragma unroll
             for (int ci = 0; ci < 4; ++ci)
@@ -1531,20 +1375,6 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                     a[ri][ci] = v;
                 }
             potrf64_regs(a, colbuf, ti, tj, nb, bad, s_invd);
-#else
-            // (the 16-column panel form: built and measured in round 3 -- 14.8 vs 14.5 us per 64 x 64 block on the
-            // nd24k-class input: one wave is bound by the instructions it issues, not by the pivots' chain -- not the default)
-            potrf64_panel(Cb, nb, bad, s_invd, colbuf);
-            double a[4][4];   // thread (ti, tj)'s 4x4 block of the factor, as the rest of the step takes it
-#pragma unroll
-            for (int ci = 0; ci < 4; ++ci)
-#pragma unroll
-                for (int ri = 0; ri < 4; ++ri) {
-                    const int i = 4 * ti + ri, c = 4 * tj + ci;
-                    a[ri][ci] = (c < nb && i < nb && i >= c) ? cell(Cb, i, c) : 0.0;
-                }
-            __syncthreads();   // (the buffer that held the tile may be the one Ljj is laid out in below)
-#endif
 #ifdef PARSY_STAMPS
             if (tid == 0 && J < 512) g_trace[J * 16 + 9] = clock64();
 #endif
@@ -1604,7 +1434,6 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             }
-#ifndef PARSY_WALKER_LDS_TRSM
             // (round 5) tile (J+1,J) straight into the accumulator layout of the TRSM below -- wave q: rows 16 q + l15 of the
             // tile, xa[g][v] = column 16 g + kq + 4 v (lanes along the rows: 128-byte segments)
             double4_t xa[4];
@@ -1616,9 +1445,6 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                     for (int v = 0; v < 4; ++v)
                         xa[g][v] = row < r ? ld_sc1(&G[(int64_t)(col0 + 16 * g + kq + 4 * v) * ld + row]) : 0.0;
             }
-#else
-            load_b();
-#endif
             TRACE(J, 4);
             // Diagonal tile J is published as soon as its stores have landed, without a workgroup
             // barrier: every wave drains its own stores (behind the loads it has to wait for anyway)
@@ -1630,23 +1456,15 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                 if (arrived == kThreads / 64 - 1)
                     __hip_atomic_store(&tflags[f_diag], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-#ifdef PARSY_WALKER_LDS_TRSM
-#pragma unroll
-            for (int q = 0; q < kSub * kSub / 64; ++q) {
-                const int e = q * 64 + lane;
-                Tw[(e >> 5) * kLdSub + (e & 31)] = bv[q];
-            }
-#endif
-            __syncthreads();  // Ljj (and, LDS form, the tile) are in LDS
+            __syncthreads();  // Ljj is in LDS
             TRACE(J, 3);
             load_c();  // lands behind the TRSM
             invert_diag_blocks((lds_f64*)dgbuf, (lds_f64*)invd);
             TRACE(J, 10);
-#ifndef PARSY_WALKER_LDS_TRSM
             {
                 // The blocked TRSM on the accumulators, as the other tiles do it ("finishes in REGISTERS"): in the transposed
                 // form X_b' = inv(L_bb) (B_b' - sum_{p<b} L_bp X_p') register u of a 16-column block IS the operand of k step u
-                // of the next product -- no LDS round trip between the four blocks (the LDS form: 3.2 us of the step) --, then X
+                // of the next product -- no LDS round trip between the four blocks (through LDS: 3.2 us of the step) --, then X
                 // goes to the panel from the registers and, for the SYRK, into the tile buffer.
                 const lds_f64* __restrict__ Dgl = (const lds_f64*)dgbuf;
                 const lds_f64* __restrict__ iv = (const lds_f64*)invd;
@@ -1683,27 +1501,6 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                     }
                 __syncthreads();   // X is in the tile buffer: the SYRK reads other waves' rows
             }
-#else
-            invert_and_trsm_inline<false>((lds_f64*)Tflat, (lds_f64*)dgbuf, (lds_f64*)invd, kTile);
-            TRACE(J, 5);
-#endif
-#ifdef PARSY_WALKER_LDS_TRSM
-            {   // X = final tile (J+1,J): this wave's quadrant, all LDS reads first, then the stores
-                const int sr = row1 + kSub * wa, nr = min(kSub, r - sr), scx = col0 + kSub * wb;
-                double xq[kSub * kSub / 64];
-#pragma unroll
-                for (int q = 0; q < kSub * kSub / 64; ++q) {
-                    const int e = q * 64 + lane;
-                    xq[q] = Tw[(e >> 5) * kLdSub + (e & 31)];
-                }
-#pragma unroll
-                for (int q = 0; q < kSub * kSub / 64; ++q) {
-                    const int e = q * 64 + lane;
-                    const int cc = e >> 5, rr = e & 31;
-                    if (rr < nr) st_sc1(&G[(int64_t)(scx + cc) * ld + sr + rr], xq[q]);
-                }
-            }
-#endif
             TRACE(J, 11);
             // X is published the same way (drain half way through the SYRK below).
             auto publish_x_wave = [&]() {
@@ -1832,50 +1629,36 @@ __global__ __launch_bounds__(kThreads, 3) void k_chol_chain_rows(const SnDesc* _
 // tile belongs to this workgroup alone within the launch, sources in list order: fixed summation
 // order.
 // ---------------------------------------------------------------------------
-#ifndef PARSY_BK
-#define PARSY_BK 16
-#endif
-static constexpr int kBK = PARSY_BK;           // k extent of a staged chunk
+static constexpr int kBK = 16;                 // k extent of a staged chunk
 static constexpr int kBLd = kBigTile + 16;     // k stride of a staged chunk in LDS: lanes 16..31 (k + 1) of an
                                                // operand read hit the other half of the banks
-#ifndef PARSY_BIG_WC
-#define PARSY_BIG_WC 4
-#endif
-static constexpr int kBigWC = PARSY_BIG_WC;    // waves along the tile's columns: 4 (8 waves: 2 x 4, up to 64 x 32 outputs
+static constexpr int kBigWC = 4;               // waves along the tile's columns (8 waves: 2 x 4, up to 64 x 32 outputs
                                                // each; two workgroups per CU = 4 waves per SIMD, so that the start of one
-                                               // task hides behind the multiplies of the others) or 2 (4 waves of 64 x 64)
-static constexpr int kBigWCols = kBigTile / kBigWC;   // columns of a wave's block (32 / 64)
-static constexpr int kBigNfc = kBigWCols / 16;        // 16-column fragments of it (2 / 4)
-#ifndef PARSY_BIG_WR
-#define PARSY_BIG_WR 2
-#endif
-static constexpr int kBigWR = PARSY_BIG_WR;           // waves along the tile's rows: 2, or 4 (16 waves of up to 32 x 32
-                                                      // outputs: one workgroup per compute unit with PARSY_BK = 32)
-static constexpr int kBigNfr = kBigTile / kBigWR / 16;   // 16-row fragments of a wave's block (4 / 2)
+                                               // task hides behind the multiplies of the others)
+static constexpr int kBigNfc = kBigTile / kBigWC / 16;   // 16-column fragments of a wave's block: 2
+static constexpr int kBigWR = 2;                         // waves along the tile's rows
+static constexpr int kBigNfr = kBigTile / kBigWR / 16;   // 16-row fragments of a wave's block: 4
 static constexpr int kBigWaves = kBigWR * kBigWC;
 static constexpr int kBigThreads = 64 * kBigWaves;
-static_assert(kBK % 4 == 0 && kBK % kBigWaves == 0 && kBigWaves >= 4, "k_chol_big: a wave stages kBK / waves columns per operand");
+static_assert(kBK % 4 == 0 && kBK % kBigWaves == 0, "k_chol_big: a wave stages kBK / waves columns per operand");
 struct BigLds {
     double R[2][kBK * kBLd];
     double C[2][kBK * kBLd];
 };
 
 // one LDS-DMA instruction: 16 bytes per lane from the lane's own global address to lds + 16 * lane
-#ifndef PARSY_GLDS_AUX
-#define PARSY_GLDS_AUX 0     // (cache-policy bits of the staging loads: 2 = nt, 16 = sc1; measured: no gain, see DESIGN)
-#endif
+static constexpr int kGldsAux = 0;   // (cache-policy bits of the staging loads: 2 = nt, 16 = sc1; measured: no gain, see DESIGN)
 __device__ __forceinline__ void glds16(const double* g, double* lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)lds, 16, 0, PARSY_GLDS_AUX);
+                                     (__attribute__((address_space(3))) void*)lds, 16, 0, kGldsAux);
 }
 
-__global__ __launch_bounds__(kBigThreads, kBigThreads / 64 >= 16 ? 4 : kBigWC) void k_chol_big(const SnDesc* __restrict__ sn,
+__global__ __launch_bounds__(kBigThreads, 4) void k_chol_big(const SnDesc* __restrict__ sn,
                                                              const int32_t* __restrict__ relpos,
                                                              const WaveEntry* __restrict__ ents,
                                                              const TileDesc* __restrict__ tasks,
                                                              double* __restrict__ L) {
     __shared__ __attribute__((aligned(16))) BigLds S;
-#ifndef PARSY_BIG_NOAGPR
     // The accumulators live in AGPRs (64 of the wave's 128 registers): one inline-asm operand of class "a" makes the
     // compiler select the AGPR form of the matrix instructions (it still places every wait state itself); the
     // atomic adds of the tile update take their data straight from there.
@@ -1883,10 +1666,9 @@ __global__ __launch_bounds__(kBigThreads, kBigThreads / 64 >= 16 ? 4 : kBigWC) v
         int agpr_hint = 0;
         asm volatile("; accumulators in AGPRs %0" ::"a"(agpr_hint));
     }
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / kBigWC, wc = wave % kBigWC, l15 = lane & 15, kq = lane >> 4;
+    const int l15 = lane & 15, kq = lane >> 4;
     const TileDesc td = tasks[blockIdx.x];
     const SnDesc D = sn[td.sn];
     double* __restrict__ G = L + D.px;
@@ -1986,27 +1768,22 @@ __global__ __launch_bounds__(kBigThreads, kBigThreads / 64 >= 16 ? 4 : kBigWC) v
         // operands addressed on their own: registers the kernel does not have).
         int wrs = 1;                                   // log2 of the waves along the rows: 2 x 4
         int best = ((NR + 1) >> 1) * ((NC + 3) >> 2);
-        if (kBigWR == 2 && kBigWC == 4) {
-            if (NR <= 4 && NR * ((NC + 7) >> 3) < best) {            // 1 x 8
-                best = NR * ((NC + 7) >> 3);
-                wrs = 0;
-            }
-            if (NC <= 4 && ((NR + 3) >> 2) * ((NC + 1) >> 1) < best) {   // 4 x 2
-                best = ((NR + 3) >> 2) * ((NC + 1) >> 1);
-                wrs = 2;
-            }
-            if (NC <= 2 && ((NR + 7) >> 3) * NC < best) {            // 8 x 1
-                best = ((NR + 7) >> 3) * NC;
-                wrs = 3;
-            }
+        if (NR <= 4 && NR * ((NC + 7) >> 3) < best) {            // 1 x 8
+            best = NR * ((NC + 7) >> 3);
+            wrs = 0;
         }
-        static_assert(kBigWaves == 8 || (kBigWR != 2 || kBigWC != 4), "k_chol_big: the entry grids are shapes of 8 waves");
-        const int wcs = (kBigWR == 2 && kBigWC == 4) ? 3 - wrs : 0;
-        const int WR = (kBigWR == 2 && kBigWC == 4) ? 1 << wrs : kBigWR, WC = (kBigWR == 2 && kBigWC == 4) ? 1 << wcs : kBigWC;
-        const int gwr = (kBigWR == 2 && kBigWC == 4) ? wave >> wcs : wr;
-        const int gwc = (kBigWR == 2 && kBigWC == 4) ? wave & (WC - 1) : wc;   // (for 2 x 4: wr, wc)
-        const int frb = (kBigWR == 2 && kBigWC == 4) ? (NR + WR - 1) >> wrs : (NR + WR - 1) / WR;
-        const int fcb = (kBigWR == 2 && kBigWC == 4) ? (NC + WC - 1) >> wcs : (NC + WC - 1) / WC;
+        if (NC <= 4 && ((NR + 3) >> 2) * ((NC + 1) >> 1) < best) {   // 4 x 2
+            best = ((NR + 3) >> 2) * ((NC + 1) >> 1);
+            wrs = 2;
+        }
+        if (NC <= 2 && ((NR + 7) >> 3) * NC < best) {            // 8 x 1
+            best = ((NR + 7) >> 3) * NC;
+            wrs = 3;
+        }
+        const int wcs = 3 - wrs;
+        const int WR = 1 << wrs, WC = 1 << wcs;
+        const int gwr = wave >> wcs, gwc = wave & (WC - 1);   // (for 2 x 4: wave / kBigWC, wave % kBigWC)
+        const int frb = (NR + WR - 1) >> wrs, fcb = (NC + WC - 1) >> wcs;
         r0 = 16 * frb * gwr;
         c0 = 16 * fcb * gwc;
         nfr = min(frb, max(0, NR - frb * gwr));

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "errors.hpp"
+#include "hip_check.hpp"
 #include "plan_fwd.hpp"
 #include "refine.hpp"
 #include "selinv.hpp"
@@ -14,15 +15,6 @@
 namespace parsy {
 
 const Schedule& plan_schedule(const parsy_plan* plan) { return plan->S; }
-
-#define PARSY_HIP(call)                                                                      \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return -1;                                                                       \
-        }                                                                                    \
-    } while (0)
 
 template <typename T>
 static int upload(parsy_plan* pl, const std::vector<T>& v, const T*& dptr, bool launch_array) {
@@ -305,24 +297,21 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
             case kLaunchSmall: launch_chol_small(pl->dp, l.first, l.count, l.lds_bytes, l.jb, l.fused == 2, L, stream); break;
             case kLaunchTiles:
             case kLaunchBig:
-            case kLaunchDense:
+            case kLaunchDense: {
+                const hipStream_t st = on_side ? pl->side_stream : stream;
                 if (on_side) {
                     record_levels_below(l.wait_level + 1);
-                    (void)hipStreamWaitEvent(pl->side_stream,
-                                             l.wait_level >= 0 ? pl->ev_level_done[l.wait_level] : pl->ev_init, 0);
-                    if (l.kind == kLaunchBig) launch_chol_big(pl->dp, l.first, l.count, L, pl->side_stream);
-                    else if (l.kind == kLaunchDense) launch_chol_dense(pl->dp, l.first, l.count, L, pl->side_stream);
-                    else launch_chol_tiles(pl->dp, l.first, l.count, L, pl->side_stream);
-                    (void)hipEventRecord(pl->ev_early_done[l.level], pl->side_stream);
+                    (void)hipStreamWaitEvent(st, l.wait_level >= 0 ? pl->ev_level_done[l.wait_level] : pl->ev_init, 0);
+                }
+                if (l.kind == kLaunchBig) launch_chol_big(pl->dp, l.first, l.count, L, st);
+                else if (l.kind == kLaunchDense) launch_chol_dense(pl->dp, l.first, l.count, L, st);
+                else launch_chol_tiles(pl->dp, l.first, l.count, L, st);
+                if (on_side) {
+                    (void)hipEventRecord(pl->ev_early_done[l.level], st);
                     early_seen[l.level] = 1;
-                } else if (l.kind == kLaunchBig) {
-                    launch_chol_big(pl->dp, l.first, l.count, L, stream);
-                } else if (l.kind == kLaunchDense) {
-                    launch_chol_dense(pl->dp, l.first, l.count, L, stream);
-                } else {
-                    launch_chol_tiles(pl->dp, l.first, l.count, L, stream);
                 }
                 break;
+            }
             case kLaunchChain: launch_chol_chain(pl->dp, l.first, l.count, l.jb, pl->epoch, l.fused != 0, L, stream); break;
             case kLaunchSolveSmall:
                 // (the subtree launch with many right-hand sides: a wave per subtree and 16 right-hand sides, traffic in LDS)

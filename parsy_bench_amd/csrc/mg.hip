@@ -14,20 +14,12 @@
 #include "../../include/parsy_amd.h"
 #include "dist.hpp"
 #include "errors.hpp"
+#include "hip_check.hpp"
 #include "executor.hpp"
 #include "inspector.hpp"
 #include "plan_fwd.hpp"
 
 using parsy::set_last_error;
-
-#define MG_HIP(call, ret)                                                            \
-    do {                                                                             \
-        hipError_t e_ = (call);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));       \
-            return ret;                                                              \
-        }                                                                            \
-    } while (0)
 
 struct parsy_mg {
     int nranks = 0;
@@ -49,12 +41,12 @@ struct parsy_mg {
 namespace {
 
 int upload(parsy_mg* mg, int dev, const void* host, size_t bytes, void** out) {
-    MG_HIP(hipSetDevice(dev), -1);
+    PARSY_HIP(hipSetDevice(dev));
     void* d = nullptr;
-    MG_HIP(hipMalloc(&d, std::max<size_t>(bytes, 8)), -1);
+    PARSY_HIP(hipMalloc(&d, std::max<size_t>(bytes, 8)));
     mg->owned.push_back(d);
     mg->owned_dev.push_back(dev);
-    if (bytes) MG_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice), -1);
+    if (bytes) PARSY_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
     *out = d;
     return 0;
 }
@@ -189,8 +181,8 @@ int parsy_mg_set_values(parsy_mg* mg, const double* values) {
         return -1;
     }
     for (int r = 0; r < mg->nranks; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipMemcpy(mg->values[(size_t)r], values, (size_t)mg->nnzA * sizeof(double), hipMemcpyHostToDevice), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipMemcpy(mg->values[(size_t)r], values, (size_t)mg->nnzA * sizeof(double), hipMemcpyHostToDevice));
     }
     mg->have_values = true;
     return 0;
@@ -200,19 +192,19 @@ static int mg_factor_enqueue(parsy_mg* mg, double* seconds) {
     const parsy::Dist& D = parsy_dist_cxx(mg->dist);
     const int nr = mg->nranks;
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
     }
     const auto w0 = std::chrono::steady_clock::now();
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipEventRecord(mg->t0[(size_t)r], mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipEventRecord(mg->t0[(size_t)r], mg->stream[(size_t)r]));
         if (parsy::plan_factor_begin(mg->plan[(size_t)r], mg->values[(size_t)r], mg->L[(size_t)r], mg->stream[(size_t)r], true) != 0)
             return -1;
     }
     for (int lev = 0; lev < D.nlevels; ++lev) {
         for (int r = 0; r < nr; ++r) {
-            MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
+            PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
             if (parsy::plan_factor_levels(mg->plan[(size_t)r], lev, lev + 1, mg->L[(size_t)r], mg->stream[(size_t)r]) != 0)
                 return -1;
         }
@@ -222,26 +214,26 @@ static int mg_factor_enqueue(parsy_mg* mg, double* seconds) {
         for (int64_t m = m0; m < m1; ++m) sends[(size_t)D.msgs[(size_t)m].src] = 1;
         for (int r = 0; r < nr; ++r)
             if (sends[(size_t)r]) {
-                MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-                MG_HIP(hipEventRecord(mg->level_done[(size_t)r][(size_t)lev], mg->stream[(size_t)r]), -1);
+                PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+                PARSY_HIP(hipEventRecord(mg->level_done[(size_t)r][(size_t)lev], mg->stream[(size_t)r]));
             }
         for (int64_t m = m0; m < m1; ++m) {
             const parsy::DistMessage& M = D.msgs[(size_t)m];
-            MG_HIP(hipSetDevice(mg->device[(size_t)M.dst]), -1);
-            MG_HIP(hipStreamWaitEvent(mg->stream[(size_t)M.dst], mg->level_done[(size_t)M.src][(size_t)lev], 0), -1);
+            PARSY_HIP(hipSetDevice(mg->device[(size_t)M.dst]));
+            PARSY_HIP(hipStreamWaitEvent(mg->stream[(size_t)M.dst], mg->level_done[(size_t)M.src][(size_t)lev], 0));
             parsy::launch_copy_segments(mg->L[(size_t)M.dst], mg->L[(size_t)M.src], mg->dmsg[(size_t)m].off,
                                         mg->dmsg[(size_t)m].off, mg->dmsg[(size_t)m].len, (int64_t)M.off.size(),
                                         mg->stream[(size_t)M.dst]);
         }
     }
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
         if (parsy::plan_factor_end(mg->plan[(size_t)r], mg->stream[(size_t)r]) != 0) return -1;
-        MG_HIP(hipEventRecord(mg->t1[(size_t)r], mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipEventRecord(mg->t1[(size_t)r], mg->stream[(size_t)r]));
     }
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
     }
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
     for (int r = 0; r < nr; ++r) {
@@ -281,48 +273,48 @@ static int mg_profile_run(parsy_mg* mg, double* main_ms, double* side_ms, double
     const int nr = mg->nranks, nl = D.nlevels;
     if (copy_ms) std::fill(copy_ms, copy_ms + (size_t)nr * nl, 0.0);
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
-        MG_HIP(hipEventCreate(&c0[(size_t)r]), -1);
-        MG_HIP(hipEventCreate(&c1[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
+        PARSY_HIP(hipEventCreate(&c0[(size_t)r]));
+        PARSY_HIP(hipEventCreate(&c1[(size_t)r]));
         parsy_plan_profile(mg->plan[(size_t)r], 2);
         if (parsy::plan_factor_begin(mg->plan[(size_t)r], mg->values[(size_t)r], mg->L[(size_t)r], mg->stream[(size_t)r], true) != 0)
             return -1;
-        MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
     }
     for (int lev = 0; lev < nl; ++lev) {
         for (int r = 0; r < nr; ++r) {   // one rank at a time: its step has the device to itself
-            MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
+            PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
             if (parsy::plan_factor_levels(mg->plan[(size_t)r], lev, lev + 1, mg->L[(size_t)r], mg->stream[(size_t)r]) != 0)
                 return -1;
-            MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+            PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
         }
         for (int r = 0; r < nr; ++r) {   // the copies a rank receives, timed as one block
             bool any = false;
-            MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
+            PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
             for (int64_t m = D.level_msg0[(size_t)lev]; m < D.level_msg0[(size_t)lev + 1]; ++m) {
                 const parsy::DistMessage& M = D.msgs[(size_t)m];
                 if (M.dst != r) continue;
-                if (!any) MG_HIP(hipEventRecord(c0[(size_t)r], mg->stream[(size_t)r]), -1);
+                if (!any) PARSY_HIP(hipEventRecord(c0[(size_t)r], mg->stream[(size_t)r]));
                 any = true;
                 parsy::launch_copy_segments(mg->L[(size_t)M.dst], mg->L[(size_t)M.src], mg->dmsg[(size_t)m].off,
                                             mg->dmsg[(size_t)m].off, mg->dmsg[(size_t)m].len, (int64_t)M.off.size(),
                                             mg->stream[(size_t)r]);
             }
             if (any) {
-                MG_HIP(hipEventRecord(c1[(size_t)r], mg->stream[(size_t)r]), -1);
-                MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+                PARSY_HIP(hipEventRecord(c1[(size_t)r], mg->stream[(size_t)r]));
+                PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
                 float ms = 0;
-                MG_HIP(hipEventElapsedTime(&ms, c0[(size_t)r], c1[(size_t)r]), -1);
+                PARSY_HIP(hipEventElapsedTime(&ms, c0[(size_t)r], c1[(size_t)r]));
                 if (copy_ms) copy_ms[(size_t)r * nl + lev] = ms;
             }
         }
     }
     int status = 0;
     for (int r = 0; r < nr; ++r) {
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
         if (parsy::plan_factor_end(mg->plan[(size_t)r], mg->stream[(size_t)r]) != 0) return -1;
-        MG_HIP(hipStreamSynchronize(mg->stream[(size_t)r]), -1);
+        PARSY_HIP(hipStreamSynchronize(mg->stream[(size_t)r]));
         parsy_plan_profile_collect(mg->plan[(size_t)r]);
         parsy_plan_profile_levels(mg->plan[(size_t)r], main_ms ? main_ms + (size_t)r * nl : nullptr,
                                   side_ms ? side_ms + (size_t)r * nl : nullptr);
@@ -353,8 +345,8 @@ int parsy_mg_rank_ms(parsy_mg* mg, double* rank_ms) {
     if (!mg || !rank_ms) return -1;
     for (int r = 0; r < mg->nranks; ++r) {
         float ms = -1;
-        MG_HIP(hipSetDevice(mg->device[(size_t)r]), -1);
-        MG_HIP(hipEventElapsedTime(&ms, mg->t0[(size_t)r], mg->t1[(size_t)r]), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+        PARSY_HIP(hipEventElapsedTime(&ms, mg->t0[(size_t)r], mg->t1[(size_t)r]));
         rank_ms[r] = ms;
     }
     return 0;
@@ -376,8 +368,8 @@ int parsy_mg_gather_host(parsy_mg* mg, double* lValues) {
         const int64_t a = R0.px + (int64_t)S.csn[(size_t)p].rbias * R0.r;
         const int64_t b = R1.px + (int64_t)(S.csn[(size_t)q].rbias + S.csn[(size_t)q].w) * R1.r;
         const int rk = D.owner[(size_t)p];
-        MG_HIP(hipSetDevice(mg->device[(size_t)rk]), -1);
-        MG_HIP(hipMemcpy(lValues + a, mg->L[(size_t)rk] + a, (size_t)(b - a) * sizeof(double), hipMemcpyDeviceToHost), -1);
+        PARSY_HIP(hipSetDevice(mg->device[(size_t)rk]));
+        PARSY_HIP(hipMemcpy(lValues + a, mg->L[(size_t)rk] + a, (size_t)(b - a) * sizeof(double), hipMemcpyDeviceToHost));
         p = q + 1;
     }
     return 0;

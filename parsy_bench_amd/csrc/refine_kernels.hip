@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "errors.hpp"
+#include "hip_check.hpp"
 #include "executor.hpp"
 #include "kernels.hpp"
 #include "refine.hpp"
@@ -215,15 +216,6 @@ __global__ __launch_bounds__(kRThreads) void k_refine_state(const u64* __restric
     }
 }
 
-#define R_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));                       \
-            return -1;                                                                               \
-        }                                                                                            \
-    } while (0)
-
 dim3 grid_nq(int n, int nrhs) { return dim3((unsigned)((n + kRThreads - 1) / kRThreads), (unsigned)nrhs); }
 
 // the per-column state inside colstate (refine.hpp)
@@ -308,15 +300,15 @@ int ensure_pattern(parsy_plan* pl) {
     R.max_row = max_row;
     const double mean = n > 0 ? (double)nf / n : 0;
     R.group = mean > 24 ? 32 : mean > 12 ? 16 : mean > 6 ? 8 : 4;
-    R_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     const size_t brp = (size_t)(n + 1) * 8, bci = ci.size() * 4, bvf = ci.size() * 8;
-    R_HIP(hipMalloc((void**)&R.d_rp, brp));
-    R_HIP(hipMalloc((void**)&R.d_ci, bci));
-    R_HIP(hipMalloc((void**)&R.d_src, bci));
-    R_HIP(hipMalloc((void**)&R.d_vf, bvf));
-    R_HIP(hipMemcpy(R.d_rp, rp.data(), brp, hipMemcpyHostToDevice));
-    R_HIP(hipMemcpy(R.d_ci, ci.data(), bci, hipMemcpyHostToDevice));
-    R_HIP(hipMemcpy(R.d_src, src.data(), bci, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMalloc((void**)&R.d_rp, brp));
+    PARSY_HIP(hipMalloc((void**)&R.d_ci, bci));
+    PARSY_HIP(hipMalloc((void**)&R.d_src, bci));
+    PARSY_HIP(hipMalloc((void**)&R.d_vf, bvf));
+    PARSY_HIP(hipMemcpy(R.d_rp, rp.data(), brp, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(R.d_ci, ci.data(), bci, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(R.d_src, src.data(), bci, hipMemcpyHostToDevice));
     R.pattern_bytes = (int64_t)(brp + 2 * bci + bvf);
     pl->device_bytes += R.pattern_bytes;
     return 0;
@@ -326,29 +318,29 @@ int ensure_pattern(parsy_plan* pl) {
 int ensure_workspace(parsy_plan* pl, int nrhs) {
     RefineState& R = state(pl);
     const int64_t need = 3 * (int64_t)pl->S.n * nrhs;
-    R_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     if (R.ws_len < need) {
-        if (R.ws) R_HIP(hipFree(R.ws));
+        if (R.ws) PARSY_HIP(hipFree(R.ws));
         pl->device_bytes -= R.ws_len * 8;
         R.ws = nullptr;
         R.ws_len = 0;
-        R_HIP(hipMalloc((void**)&R.ws, (size_t)need * 8));
+        PARSY_HIP(hipMalloc((void**)&R.ws, (size_t)need * 8));
         R.ws_len = need;
         pl->device_bytes += need * 8;
     }
     if (R.colstate_cap < nrhs) {
         const auto bytes = [](int cap) { return (int64_t)cap * (kRefinePartials * 8 + 8 + 8 + 4 + 4) + 8; };
-        if (R.colstate) R_HIP(hipFree(R.colstate));
+        if (R.colstate) PARSY_HIP(hipFree(R.colstate));
         pl->device_bytes -= R.colstate_cap ? bytes(R.colstate_cap) : 0;
         R.colstate = nullptr;
         R.colstate_cap = 0;
-        R_HIP(hipMalloc(&R.colstate, (size_t)bytes(nrhs)));
+        PARSY_HIP(hipMalloc(&R.colstate, (size_t)bytes(nrhs)));
         R.colstate_cap = nrhs;
         pl->device_bytes += bytes(nrhs);
     }
     if (!R.perm.empty() && !R.d_perm) {
-        R_HIP(hipMalloc((void**)&R.d_perm, R.perm.size() * 4));
-        R_HIP(hipMemcpy(R.d_perm, R.perm.data(), R.perm.size() * 4, hipMemcpyHostToDevice));
+        PARSY_HIP(hipMalloc((void**)&R.d_perm, R.perm.size() * 4));
+        PARSY_HIP(hipMemcpy(R.d_perm, R.perm.data(), R.perm.size() * 4, hipMemcpyHostToDevice));
         pl->device_bytes += (int64_t)R.perm.size() * 4;
     }
     return 0;
@@ -373,14 +365,14 @@ int residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* 
         R_GROUPS(4) R_GROUPS(8) R_GROUPS(16) R_GROUPS(32)
 #undef R_GROUPS
 #undef R_GROUP
-        R_HIP(hipGetLastError());
+        PARSY_HIP(hipGetLastError());
         return nb;
     }
     // stage z with the right-hand sides of a row contiguous in the plan's xt (the forward solves' staging buffer: a
     // solve fills it afresh, the residual runs between solves)
     const int ldq = (nrhs + 15) & ~15;
     const int64_t need = (int64_t)n * ldq;
-    R_HIP(grow_device(pl->xt, pl->xt_len, need));
+    PARSY_HIP(grow_device(pl->xt, pl->xt_len, need));
     launch_transpose_x(const_cast<double*>(z), n, pl->xt, ldq, n, nrhs, true, stream);
     const int L = nrhs <= 8 ? 8 : nrhs <= 16 ? 16 : nrhs <= 32 ? 32 : 64;
     const int nb = nblocks(kRThreads / L);
@@ -391,7 +383,7 @@ int residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* 
                            ldq, pb, r, n, nrhs, safe1, safe2, part);
     R_MRHS(8) R_MRHS(16) R_MRHS(32) R_MRHS(64)
 #undef R_MRHS
-    R_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return nb;
 }
 
@@ -400,7 +392,7 @@ int gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream) {
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(8192, (R.nnz_full + kRThreads - 1) / kRThreads));
     hipLaunchKernelGGL(k_refine_gather_values, dim3((unsigned)nb), dim3(kRThreads), 0, stream, d_values, R.d_src, R.d_vf,
                        R.nnz_full);
-    R_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
@@ -414,7 +406,7 @@ int solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* c
     if (plan_backsolve(pl, d_L, x, nrhs, n, stream) != 0) return -1;
     hipLaunchKernelGGL(k_refine_note_status, dim3(1), dim3(64), 0, stream,
                        pl->solve_status_word ? pl->solve_status_word : pl->dp.sinfo, ctl);
-    R_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
@@ -483,11 +475,11 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
     if (berr) {
         hipLaunchKernelGGL(k_refine_state, dim3(nrhs), dim3(kRThreads), 0, stream, c.part, nb, c.berr, c.lstres, c.active,
                            c.steps, 0, 1, c.ctl);
-        R_HIP(hipGetLastError());
-        R_HIP(hipMemcpyAsync(berr, c.berr, (size_t)nrhs * 8, hipMemcpyDeviceToHost, stream));
-        R_HIP(hipStreamSynchronize(stream));
+        PARSY_HIP(hipGetLastError());
+        PARSY_HIP(hipMemcpyAsync(berr, c.berr, (size_t)nrhs * 8, hipMemcpyDeviceToHost, stream));
+        PARSY_HIP(hipStreamSynchronize(stream));
     }
-    R_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
@@ -505,7 +497,7 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
     const int64_t nn = (int64_t)n * nrhs;
     double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
-    R_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
+    PARSY_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
     if (n > 0)
         hipLaunchKernelGGL(k_refine_permute_in, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, d_b, (int64_t)ldb, R.d_perm,
                            pb, z, n);
@@ -514,15 +506,15 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
         if (gather_values(pl, d_values, stream) != 0) return -1;
         hipLaunchKernelGGL(k_refine_init, dim3((nrhs + 255) / 256), dim3(256), 0, stream, c.lstres, c.active, c.steps, nrhs);
         for (;;) {
-            R_HIP(hipMemsetAsync(c.ctl, 0, sizeof(int), stream));
+            PARSY_HIP(hipMemsetAsync(c.ctl, 0, sizeof(int), stream));
             const int nb = residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
             if (nb < 0) return -1;
             hipLaunchKernelGGL(k_refine_state, dim3(nrhs), dim3(kRThreads), 0, stream, c.part, nb, c.berr, c.lstres,
                                c.active, c.steps, max_steps, 0, c.ctl);
-            R_HIP(hipGetLastError());
+            PARSY_HIP(hipGetLastError());
             int ctl[2] = {0, 0};
-            R_HIP(hipMemcpyAsync(ctl, c.ctl, sizeof(ctl), hipMemcpyDeviceToHost, stream));
-            R_HIP(hipStreamSynchronize(stream));
+            PARSY_HIP(hipMemcpyAsync(ctl, c.ctl, sizeof(ctl), hipMemcpyDeviceToHost, stream));
+            PARSY_HIP(hipStreamSynchronize(stream));
             if (ctl[1] < 0)
                 return set_last_error(std::string(who) +
                                       ": a hand-off wait inside a chain launch timed out; x is not the solution"),
@@ -536,10 +528,10 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
     if (n > 0)
         hipLaunchKernelGGL(k_refine_permute_out, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, z, R.d_perm, d_x,
                            (int64_t)ldx, n);
-    R_HIP(hipGetLastError());
-    if (steps) R_HIP(hipMemcpyAsync(steps, c.steps, (size_t)nrhs * 4, hipMemcpyDeviceToHost, stream));
-    if (berr) R_HIP(hipMemcpyAsync(berr, c.berr, (size_t)nrhs * 8, hipMemcpyDeviceToHost, stream));
-    if (steps || berr) R_HIP(hipStreamSynchronize(stream));
+    PARSY_HIP(hipGetLastError());
+    if (steps) PARSY_HIP(hipMemcpyAsync(steps, c.steps, (size_t)nrhs * 4, hipMemcpyDeviceToHost, stream));
+    if (berr) PARSY_HIP(hipMemcpyAsync(berr, c.berr, (size_t)nrhs * 8, hipMemcpyDeviceToHost, stream));
+    if (steps || berr) PARSY_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 

@@ -22,7 +22,9 @@
 #include <vector>
 
 #include "../../include/parsy_amd.h"
+#include "device_util.hpp"
 #include "errors.hpp"
+#include "hip_check.hpp"
 #include "executor.hpp"
 #include "refine.hpp"
 #include "selinv.hpp"
@@ -53,27 +55,14 @@ struct SelinvState {
 namespace {
 
 constexpr int kSThreads = 256;
-constexpr int kLd = kTile + 1;          // LDS leading dimension of a 64-row block
+constexpr int kLd = kLdDiag;            // LDS leading dimension of a 64-row block
 constexpr int kSlot = kTile * kTile;    // doubles of a scratch slot
 constexpr int kChunk = 32;              // rows of R_b per step of the small path
 constexpr int kLdC = kChunk + 1;
 constexpr int kLogParts = 256;          // workgroups of the log-determinant's first pass
-typedef double dbl4 __attribute__((ext_vector_type(4)));
 
-// ---- T = L_bb^-1 in LDS, one wave (the blocked inversion of the solves' k_diag_inverse) ---------------------------
-// 16x16 MFMA product acc += X Y of blocks of the LDS matrix (column-major, ld kLd); lane (l15, kq) holds column l15,
-// rows kq + 4 v of the result (v_mfma_f64_16x16x4_f64: A lane = (row l15, k kq), B lane = (k kq, column l15)).
-__device__ __forceinline__ dbl4 mm16(dbl4 acc, const double* __restrict__ X, const double* __restrict__ Y, int l15, int kq) {
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[(4 * st + kq) * kLd + l15], Y[l15 * kLd + 4 * st + kq], acc, 0, 0, 0);
-    return acc;
-}
-__device__ __forceinline__ void put16(double* __restrict__ Z, dbl4 acc, double sign, int l15, int kq) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) Z[l15 * kLd + kq + 4 * v] = sign * acc[v];
-}
-
+// ---- T = L_bb^-1 in LDS, one wave: the blocked inversion of the solves' k_diag_inverse (trsv_kernels.hip), spelled out
+// here a second time -- one shared inline function changed the instruction schedule of both (mm16 / put16: device_util.hpp)
 // M (64 x kLd doubles of LDS) := inv(L_bb), lower triangle, zeros above, an identity past wb.  Lanes 0..63 of one wave.
 __device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int r, int j0, int wb) {
     const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
@@ -106,25 +95,25 @@ __device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int
         for (int rr = 0; rr < 16; ++rr) B[l15 * kLd + rr] = y[rr];
     }
     __builtin_amdgcn_wave_barrier();
-    const dbl4 zero = {0, 0, 0, 0};
+    const double4_t zero = {0, 0, 0, 0};
 #pragma unroll
     for (int b = 0; b < 4; b += 2) {
-        const dbl4 t = mm16(zero, blk(b + 1, b), blk(b, b), l15, kq);
+        const double4_t t = mm16(zero, blk(b + 1, b), blk(b, b), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(b + 1, b), t, 1.0, l15, kq);
         __builtin_amdgcn_wave_barrier();
-        const dbl4 u = mm16(zero, blk(b + 1, b + 1), blk(b + 1, b), l15, kq);
+        const double4_t u = mm16(zero, blk(b + 1, b + 1), blk(b + 1, b), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(b + 1, b), u, -1.0, l15, kq);
         __builtin_amdgcn_wave_barrier();
     }
     {
-        dbl4 t20 = mm16(mm16(zero, blk(2, 0), blk(0, 0), l15, kq), blk(2, 1), blk(1, 0), l15, kq);
-        dbl4 t30 = mm16(mm16(zero, blk(3, 0), blk(0, 0), l15, kq), blk(3, 1), blk(1, 0), l15, kq);
-        dbl4 t21 = mm16(zero, blk(2, 1), blk(1, 1), l15, kq);
-        dbl4 t31 = mm16(zero, blk(3, 1), blk(1, 1), l15, kq);
+        double4_t t20 = mm16(mm16(zero, blk(2, 0), blk(0, 0), l15, kq), blk(2, 1), blk(1, 0), l15, kq);
+        double4_t t30 = mm16(mm16(zero, blk(3, 0), blk(0, 0), l15, kq), blk(3, 1), blk(1, 0), l15, kq);
+        double4_t t21 = mm16(zero, blk(2, 1), blk(1, 1), l15, kq);
+        double4_t t31 = mm16(zero, blk(3, 1), blk(1, 1), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(2, 0), t20, 1.0, l15, kq);
@@ -132,10 +121,10 @@ __device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int
         put16(blk(2, 1), t21, 1.0, l15, kq);
         put16(blk(3, 1), t31, 1.0, l15, kq);
         __builtin_amdgcn_wave_barrier();
-        dbl4 x20 = mm16(zero, blk(2, 2), blk(2, 0), l15, kq);
-        dbl4 x21 = mm16(zero, blk(2, 2), blk(2, 1), l15, kq);
-        dbl4 x30 = mm16(mm16(zero, blk(3, 2), blk(2, 0), l15, kq), blk(3, 3), blk(3, 0), l15, kq);
-        dbl4 x31 = mm16(mm16(zero, blk(3, 2), blk(2, 1), l15, kq), blk(3, 3), blk(3, 1), l15, kq);
+        double4_t x20 = mm16(zero, blk(2, 2), blk(2, 0), l15, kq);
+        double4_t x21 = mm16(zero, blk(2, 2), blk(2, 1), l15, kq);
+        double4_t x30 = mm16(mm16(zero, blk(3, 2), blk(2, 0), l15, kq), blk(3, 3), blk(3, 0), l15, kq);
+        double4_t x31 = mm16(mm16(zero, blk(3, 2), blk(2, 1), l15, kq), blk(3, 3), blk(3, 1), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(2, 0), x20, -1.0, l15, kq);
@@ -148,7 +137,7 @@ __device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int
 
 // acc[c] += A(16 w + ., k) B(k, 16 c + .) over k < 64, A(i, k) = A[i * ai + k * ak], B(k, j) = B[k * bk + j * bj] in LDS.
 // Wave w owns rows 16 w .. 16 w + 15 of the 64 x 64 result: acc[c][v] = C(16 w + kq + 4 v, 16 c + l15).
-__device__ __forceinline__ void mm64(dbl4 (&acc)[4], const double* __restrict__ A, int ai, int ak,
+__device__ __forceinline__ void mm64(double4_t (&acc)[4], const double* __restrict__ A, int ai, int ak,
                                      const double* __restrict__ B, int bk, int bj, int w, int l15, int kq) {
 #pragma unroll 4
     for (int k4 = 0; k4 < kTile / 4; ++k4) {
@@ -194,7 +183,7 @@ __global__ __launch_bounds__(kSThreads) void k_selinv_y(const SelinvBc* __restri
         Bs[k * kLd + i] = T[e];
     }
     __syncthreads();
-    dbl4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    double4_t acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     mm64(acc, As, 1, kLd, Bs, 1, kLd, w, l15, kq);
     double* __restrict__ Y = scr + (int64_t)(B.yslot + t) * kSlot;
 #pragma unroll
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(kSThreads) void k_selinv_z(const SelinvBc* __restri
         rcb[tid] = cb[B.pi + pr + tid];
         rmo[tid] = mo[B.pi + pr + tid];
     }
-    dbl4 acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    double4_t acc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     const int nk = (B.m + kTile - 1) / kTile;
     for (int kc = 0; kc < nk; ++kc) {
         const int pk = p0 + kTile * kc, nkk = min(kTile, B.m - kTile * kc);
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(kSThreads) void k_selinv_z(const SelinvBc* __restri
         if (i < nr && c < B.wb) G[(int64_t)(B.j0 + c) * B.r + pr + i] = As[c * kLd + i];
     }
     // partial P(a, c) = sum_i Y_t(i, a) Z(tile i, c)
-    dbl4 pacc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    double4_t pacc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     mm64(pacc, Bs, kLd, 1, As, 1, kLd, w, l15, kq);
     double* __restrict__ P = scr + (int64_t)(B.pslot + t) * kSlot;
 #pragma unroll
@@ -423,15 +412,6 @@ __global__ void k_logdet_final(double* __restrict__ part, int nparts) {
     part[2 * kLogParts + 1] = bad + 1.0;
 }
 
-#define S_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            set_last_error(std::string(#call) + ": " + hipGetErrorString(e_));                       \
-            return -1;                                                                               \
-        }                                                                                            \
-    } while (0)
-
 SelinvState& state(parsy_plan* pl) {
     if (!pl->selinv) pl->selinv = new SelinvState;
     return *pl->selinv;
@@ -452,8 +432,8 @@ int check_plan(parsy_plan* pl, const char* who) {
 template <class T>
 int upload(T*& d, const std::vector<T>& h, int64_t& bytes) {
     const size_t b = std::max<size_t>(h.size(), 1) * sizeof(T);
-    S_HIP(hipMalloc((void**)&d, b));
-    if (!h.empty()) S_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    PARSY_HIP(hipMalloc((void**)&d, b));
+    if (!h.empty()) PARSY_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     bytes += (int64_t)b;
     return 0;
 }
@@ -466,10 +446,10 @@ int ensure_diag(parsy_plan* pl) {
     std::vector<int64_t> doff((size_t)S.n);
     for (int s = 0; s < S.nsuper; ++s)
         for (int q = 0; q < S.sn[s].w; ++q) doff[S.sn[s].c0 + q] = S.sn[s].px + (int64_t)q * S.sn[s].r + q;
-    S_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     int64_t bytes = 0;
     if (upload(X.d_doff, doff, bytes) != 0) return -1;
-    S_HIP(hipMalloc((void**)&X.d_lpart, (2 * kLogParts + 2) * sizeof(double)));
+    PARSY_HIP(hipMalloc((void**)&X.d_lpart, (2 * kLogParts + 2) * sizeof(double)));
     bytes += (2 * kLogParts + 2) * sizeof(double);
     X.diag_bytes = bytes;
     pl->device_bytes += bytes;
@@ -479,7 +459,7 @@ int ensure_diag(parsy_plan* pl) {
 // the host schedule, the map on the device, and the split under the current threshold (descriptors, scratch)
 int ensure_selinv(parsy_plan* pl) {
     SelinvState& X = state(pl);
-    S_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     if (!X.map_ready) {
         std::string what;
         if (!build_selinv(pl->S, X.X, what)) return set_last_error("parsy_selinv_device: " + what), -1;
@@ -487,14 +467,14 @@ int ensure_selinv(parsy_plan* pl) {
         if (upload(X.d_cb, X.X.cb, bytes) != 0 || upload(X.d_mo, X.X.mo, bytes) != 0 ||
             upload(X.d_gmap, X.X.gmap, bytes) != 0)
             return -1;
-        S_HIP(hipMalloc((void**)&X.d_bcs, std::max(X.X.nbc, 1) * sizeof(SelinvBc)));
+        PARSY_HIP(hipMalloc((void**)&X.d_bcs, std::max(X.X.nbc, 1) * sizeof(SelinvBc)));
         bytes += std::max(X.X.nbc, 1) * sizeof(SelinvBc);
         for (int b = 0; b < X.X.nbc; ++b) {
             const SnDesc& d = pl->S.sn[X.X.bc_sn[b]];
             const int j0 = X.X.bc_j[b] * kTile;
             X.task_cap += (d.r - j0 - std::min(kTile, d.w - j0) + kTile - 1) / kTile;
         }
-        S_HIP(hipMalloc((void**)&X.d_tasks, std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t)));
+        PARSY_HIP(hipMalloc((void**)&X.d_tasks, std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t)));
         bytes += std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t);
         X.map_bytes = bytes;
         pl->device_bytes += bytes;
@@ -502,19 +482,19 @@ int ensure_selinv(parsy_plan* pl) {
     }
     const int tmin = selinv_tiled_min();
     if (X.sp.tiled_min != tmin) {
-        if (X.used) S_HIP(hipDeviceSynchronize());   // (an earlier call may still read the descriptors and the scratch)
+        if (X.used) PARSY_HIP(hipDeviceSynchronize());   // (an earlier call may still read the descriptors and the scratch)
         split_selinv(pl->S, X.X, tmin, X.sp);
         if (!X.sp.bcs.empty())
-            S_HIP(hipMemcpy(X.d_bcs, X.sp.bcs.data(), X.sp.bcs.size() * sizeof(SelinvBc), hipMemcpyHostToDevice));
+            PARSY_HIP(hipMemcpy(X.d_bcs, X.sp.bcs.data(), X.sp.bcs.size() * sizeof(SelinvBc), hipMemcpyHostToDevice));
         if (!X.sp.tasks.empty())
-            S_HIP(hipMemcpy(X.d_tasks, X.sp.tasks.data(), X.sp.tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            PARSY_HIP(hipMemcpy(X.d_tasks, X.sp.tasks.data(), X.sp.tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         if (X.sp.scratch_slots > X.scr_slots) {
-            if (X.d_scr) S_HIP(hipFree(X.d_scr));
+            if (X.d_scr) PARSY_HIP(hipFree(X.d_scr));
             X.d_scr = nullptr;
             pl->device_bytes -= X.scr_bytes;
             X.scr_bytes = 0;
             X.scr_slots = 0;
-            S_HIP(hipMalloc((void**)&X.d_scr, (size_t)X.sp.scratch_slots * kSlot * sizeof(double)));
+            PARSY_HIP(hipMalloc((void**)&X.d_scr, (size_t)X.sp.scratch_slots * kSlot * sizeof(double)));
             X.scr_slots = X.sp.scratch_slots;
             X.scr_bytes = X.scr_slots * kSlot * (int64_t)sizeof(double);
             pl->device_bytes += X.scr_bytes;
@@ -529,8 +509,8 @@ int perm_device(parsy_plan* pl, const int** out) {
     RefineState* R = pl->refine;
     if (!R || R->perm.empty()) return 0;
     if (!R->d_perm) {
-        S_HIP(hipMalloc((void**)&R->d_perm, R->perm.size() * 4));
-        S_HIP(hipMemcpy(R->d_perm, R->perm.data(), R->perm.size() * 4, hipMemcpyHostToDevice));
+        PARSY_HIP(hipMalloc((void**)&R->d_perm, R->perm.size() * 4));
+        PARSY_HIP(hipMemcpy(R->d_perm, R->perm.data(), R->perm.size() * 4, hipMemcpyHostToDevice));
         pl->device_bytes += (int64_t)R->perm.size() * 4;
     }
     *out = R->d_perm;
@@ -575,36 +555,36 @@ int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stre
             hipLaunchKernelGGL(k_selinv_small, dim3(nsm), dim3(kSThreads), 0, stream, X.d_bcs, d0 + nt, d_L, X.d_cb,
                                X.d_mo, X.d_gmap, d_z);
     }
-    S_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
 int plan_inverse_diag(parsy_plan* pl, const double* d_z, double* d_diag, hipStream_t stream) {
     if (check_plan(pl, "parsy_inverse_diag_device") != 0) return -1;
-    S_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     const int* perm = nullptr;
     if (ensure_diag(pl) != 0 || perm_device(pl, &perm) != 0) return -1;
     const int n = pl->S.n;
     if (n > 0)
         hipLaunchKernelGGL(k_selinv_diag, dim3((n + kSThreads - 1) / kSThreads), dim3(kSThreads), 0, stream, d_z,
                            pl->selinv->d_doff, perm, n, d_diag);
-    S_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     return 0;
 }
 
 int plan_logdet(parsy_plan* pl, const double* d_L, double* logdet, hipStream_t stream) {
     if (check_plan(pl, "parsy_logdet_device") != 0) return -1;
-    S_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(hipSetDevice(pl->device));
     if (ensure_diag(pl) != 0) return -1;
     SelinvState& X = *pl->selinv;
     const int n = pl->S.n;
     const int nparts = std::max(1, std::min(kLogParts, (n + kSThreads - 1) / kSThreads));
     hipLaunchKernelGGL(k_logdet_part, dim3(nparts), dim3(kSThreads), 0, stream, d_L, X.d_doff, n, X.d_lpart);
     hipLaunchKernelGGL(k_logdet_final, dim3(1), dim3(64), 0, stream, X.d_lpart, nparts);
-    S_HIP(hipGetLastError());
+    PARSY_HIP(hipGetLastError());
     double out[2];
-    S_HIP(hipMemcpyAsync(out, X.d_lpart + 2 * kLogParts, sizeof(out), hipMemcpyDeviceToHost, stream));
-    S_HIP(hipStreamSynchronize(stream));
+    PARSY_HIP(hipMemcpyAsync(out, X.d_lpart + 2 * kLogParts, sizeof(out), hipMemcpyDeviceToHost, stream));
+    PARSY_HIP(hipStreamSynchronize(stream));
     *logdet = out[0];
     return (int)out[1];
 }

@@ -12,13 +12,13 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "device_util.hpp"
 #include "kernels.hpp"
 
 namespace parsy {
 
 static constexpr int kThreads = 256;
 static constexpr unsigned long long kSolveSpinTicks = 200000000ull;  // 2 s of the 100 MHz wall clock (as the factorization's waits)
-static constexpr int kLdDiag = kTile + 1;
 static constexpr int kRhs = 8;  // right-hand sides carried per pass over a panel
 // Passes over the right-hand sides are independent of each other: up to kPassLanes of them run side by
 // side (workgroups of their own), the rest follow in rounds.  A block of 64 right-hand sides then costs about one pass of latency instead of eight.
@@ -154,11 +154,6 @@ __device__ __forceinline__ void block_solve_apply16(const double* Dg, const doub
         }
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src_lane),
-                            __builtin_amdgcn_readlane(__double2loint(v), src_lane));
 }
 
 // An entry of x that earlier supernodes of the same launch may have updated with atomics (subtree launches: the
@@ -312,7 +307,6 @@ __global__ __launch_bounds__(64) void k_solve_tiny(const SnDesc* __restrict__ sn
 //       registers as the A operand, the 16 x 64 piece of L comes straight from the panel (16 consecutive rows
 //       per k: 128-B segments) as the B operand -- formed as x_s' L21' so that the lanes run along the ROWS --
 //       and is subtracted from x with atomics (the reference's `omp atomic`, Triangular_BCSC.h:154).
-typedef double double4_s __attribute__((ext_vector_type(4)));
 static constexpr int kRhsM = 64;        // right-hand sides per pass
 // The many-right-hand-side kernels (64 per pass over L, matrix cores) take over from the 8-per-pass kernels
 //   * for the narrow supernodes (k_solve_small_mrhs) from 6 right-hand sides on,
@@ -396,7 +390,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
             const int qc = 16 * wave + l15;  // this lane's right-hand side as B operand / result column
             for (int b16 = 0; b16 < wpad; b16 += 16) {
                 // y_b = inv(L_bb) x_b
-                double4_s acc = {0, 0, 0, 0};
+                double4_t acc = {0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
                     const int k = 4 * st + kq, i = l15;
@@ -410,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
                 for (int v = 0; v < 4; ++v) xs[(b16 + kq + 4 * v) * kLdXs + qc] = acc[v];
                 // the sub-blocks below: x_b2 -= L(b2, b) y_b
                 for (int b2 = b16 + 16; b2 < wpad; b2 += 16) {
-                    double4_s a2 = {0, 0, 0, 0};
+                    double4_t a2 = {0, 0, 0, 0};
 #pragma unroll
                     for (int st = 0; st < 4; ++st) {
                         const int k = 4 * st + kq;
@@ -463,7 +457,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
 #pragma unroll
                     for (int n = 0; n < kNh; ++n) {
                         if (n0 + n < nfrag_n) {
-                            double4_s acc = {0, 0, 0, 0};
+                            double4_t acc = {0, 0, 0, 0};
 #pragma unroll
                             for (int st = 0; st < kSt; ++st)
                                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[st], xa[n][st], acc, 0, 0, 0);
@@ -480,7 +474,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
 #pragma unroll
                 for (int n = 0; n < kNh; ++n) {
                     if (n0 + n < nfrag_n) {
-                        double4_s acc = {0, 0, 0, 0};
+                        double4_t acc = {0, 0, 0, 0};
 #pragma unroll
                         for (int st = 0; st < kSt; ++st)
                             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[n][st], lv[st], acc, 0, 0, 0);
@@ -627,21 +621,6 @@ void launch_solve_panel(const DevicePattern& P, int first, int count, const doub
 // products instead of a 64-step substitution whose longest column is a chain of two thousand dependent
 // multiply-adds.  dinv[(dslot + jb) * 4096 + c * 64 + i] = inv(L_jj)[i][c], zeros above the diagonal; a block
 // narrower than 64 is padded with an identity.
-__device__ __forceinline__ double4_s mm16(double4_s acc, const double* __restrict__ X, const double* __restrict__ Y,
-                                          int l15, int kq) {
-    // acc += X * Y for 16x16 blocks of the LDS matrix (column-major, ld kLdDiag); result layout: lane (l15, kq)
-    // holds column l15, rows kq + 4 v
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(X[(4 * st + kq) * kLdDiag + l15], Y[l15 * kLdDiag + 4 * st + kq], acc,
-                                                   0, 0, 0);
-    return acc;
-}
-__device__ __forceinline__ void put16(double* __restrict__ Z, double4_s acc, double sign, int l15, int kq) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) Z[l15 * kLdDiag + kq + 4 * v] = sign * acc[v];
-}
-
 __global__ __launch_bounds__(64) void k_diag_inverse(const SnDesc* __restrict__ sn,
                                                      const int32_t* __restrict__ list,
                                                      const double* __restrict__ L,
@@ -683,16 +662,16 @@ __global__ __launch_bounds__(64) void k_diag_inverse(const SnDesc* __restrict__ 
         for (int rr = 0; rr < 16; ++rr) B[l15 * kLdDiag + rr] = y[rr];
     }
     __builtin_amdgcn_wave_barrier();
-    const double4_s zero = {0, 0, 0, 0};
+    const double4_t zero = {0, 0, 0, 0};
     // the two 32x32 diagonal blocks: block (b+1, b) := -inv(L_{b+1,b+1}) L_{b+1,b} inv(L_bb), b = 0, 2
 #pragma unroll
     for (int b = 0; b < 4; b += 2) {
-        const double4_s t = mm16(zero, blk(b + 1, b), blk(b, b), l15, kq);
+        const double4_t t = mm16(zero, blk(b + 1, b), blk(b, b), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(b + 1, b), t, 1.0, l15, kq);
         __builtin_amdgcn_wave_barrier();
-        const double4_s u = mm16(zero, blk(b + 1, b + 1), blk(b + 1, b), l15, kq);
+        const double4_t u = mm16(zero, blk(b + 1, b + 1), blk(b + 1, b), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(b + 1, b), u, -1.0, l15, kq);
@@ -701,10 +680,10 @@ __global__ __launch_bounds__(64) void k_diag_inverse(const SnDesc* __restrict__ 
     // the 32x32 block below: X := -inv(C) B inv(A), A = blocks (0..1, 0..1), C = blocks (2..3, 2..3), both inverted
     {
         // T = B inv(A): T_i0 = B_i0 A00 + B_i1 A10, T_i1 = B_i1 A11  (i = 2, 3)
-        double4_s t20 = mm16(mm16(zero, blk(2, 0), blk(0, 0), l15, kq), blk(2, 1), blk(1, 0), l15, kq);
-        double4_s t30 = mm16(mm16(zero, blk(3, 0), blk(0, 0), l15, kq), blk(3, 1), blk(1, 0), l15, kq);
-        double4_s t21 = mm16(zero, blk(2, 1), blk(1, 1), l15, kq);
-        double4_s t31 = mm16(zero, blk(3, 1), blk(1, 1), l15, kq);
+        double4_t t20 = mm16(mm16(zero, blk(2, 0), blk(0, 0), l15, kq), blk(2, 1), blk(1, 0), l15, kq);
+        double4_t t30 = mm16(mm16(zero, blk(3, 0), blk(0, 0), l15, kq), blk(3, 1), blk(1, 0), l15, kq);
+        double4_t t21 = mm16(zero, blk(2, 1), blk(1, 1), l15, kq);
+        double4_t t31 = mm16(zero, blk(3, 1), blk(1, 1), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(2, 0), t20, 1.0, l15, kq);
@@ -713,10 +692,10 @@ __global__ __launch_bounds__(64) void k_diag_inverse(const SnDesc* __restrict__ 
         put16(blk(3, 1), t31, 1.0, l15, kq);
         __builtin_amdgcn_wave_barrier();
         // X = -inv(C) T: X_2j = -C22 T_2j, X_3j = -(C32 T_2j + C33 T_3j)
-        double4_s x20 = mm16(zero, blk(2, 2), blk(2, 0), l15, kq);
-        double4_s x21 = mm16(zero, blk(2, 2), blk(2, 1), l15, kq);
-        double4_s x30 = mm16(mm16(zero, blk(3, 2), blk(2, 0), l15, kq), blk(3, 3), blk(3, 0), l15, kq);
-        double4_s x31 = mm16(mm16(zero, blk(3, 2), blk(2, 1), l15, kq), blk(3, 3), blk(3, 1), l15, kq);
+        double4_t x20 = mm16(zero, blk(2, 2), blk(2, 0), l15, kq);
+        double4_t x21 = mm16(zero, blk(2, 2), blk(2, 1), l15, kq);
+        double4_t x30 = mm16(mm16(zero, blk(3, 2), blk(2, 0), l15, kq), blk(3, 3), blk(3, 0), l15, kq);
+        double4_t x31 = mm16(mm16(zero, blk(3, 2), blk(2, 1), l15, kq), blk(3, 3), blk(3, 1), l15, kq);
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
         put16(blk(2, 0), x20, -1.0, l15, kq);
@@ -1046,9 +1025,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
         double* __restrict__ Ms = ts;   // Ms[k][row] = M[row][k], ld kLdDiag (the layout of Dg: the same operand reads)
         if (jb > 0) {
             const int cbp = cb - kTile;
-            double4_s am[4];
+            double4_t am[4];
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) am[rg] = double4_s{0, 0, 0, 0};
+            for (int rg = 0; rg < 4; ++rg) am[rg] = double4_t{0, 0, 0, 0};
             // B operand: lane (j = l15, kk = kq) holds L(jb, jb-1)[4 st + kk][16 v + j]
             const double* __restrict__ bcol = G + (int64_t)(cbp + 16 * wave + l15) * r + cb;
             double lb[16];
@@ -1127,7 +1106,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                         else __builtin_amdgcn_s_sleep(1);
                     }
                 };
-                double4_s a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+                double4_t a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
                 for (int k = 0; k < jb - 1 && ok; ++k) {
                     double av[16];
 #pragma unroll
@@ -1154,7 +1133,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                 for (int v = 0; v < 4; ++v) Tx[(16 * wave + 4 * v + kq) * 17 + l15] = tvo[v] - (a0[v] + a1[v]);
                 __syncthreads();
                 if (!s_ok) return;
-                double4_s out = {0, 0, 0, 0};
+                double4_t out = {0, 0, 0, 0};
                 for (int st = 0; st < 4 * wave + 4; ++st)     // (inv(L_jj)[row][k] = 0 for k > row)
                     out = __builtin_amdgcn_mfma_f64_16x16x4f64(Dg[(4 * st + kq) * kLdDiag + 16 * wave + l15], Tx[(4 * st + kq) * 17 + l15], out, 0, 0, 0);
                 if (jb > 0) {
@@ -1167,7 +1146,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                         if (lane == 0) atomicMin(info, -1);
                         s_ok = 0;
                     }
-                    double4_s m0 = {0, 0, 0, 0}, m1 = {0, 0, 0, 0};
+                    double4_t m0 = {0, 0, 0, 0}, m1 = {0, 0, 0, 0};
 #pragma unroll
                     for (int st = 0; st < 16; st += 2) {
                         m0 = __builtin_amdgcn_mfma_f64_16x16x4f64(mv[st], bv[st], m0, 0, 0, 0);
@@ -1203,9 +1182,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                 const double v = x[qoff + (cb + min(c, wbk - 1)) * sr];
                 tv[st] = (qok && c < wbk) ? v : 0.0;
             }
-            double4_s acc[4];   // [16 rows rg]: lane (q = l15, row = kq + 4 v)
+            double4_t acc[4];   // [16 rows rg]: lane (q = l15, row = kq + 4 v)
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) acc[rg] = double4_s{0, 0, 0, 0};
+            for (int rg = 0; rg < 4; ++rg) acc[rg] = double4_t{0, 0, 0, 0};
             bool ok = true;
             // X_k (this wave's 16 right-hand sides, rows 4 st + kq) as soon as it is there; lazy: a block that is not the
             // one right before this one first watches ONE value, then goes on to the full poll (normally satisfied at once)
@@ -1267,9 +1246,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
 #pragma unroll
                 for (int v = 0; v < 4; ++v) tv[4 * rg + v] -= acc[rg][v];
             // P = inv(L_jj) T' (row group rg needs k <= 16 rg + 15) -- X_jb itself for the first block column
-            double4_s out[4];
+            double4_t out[4];
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) out[rg] = double4_s{0, 0, 0, 0};
+            for (int rg = 0; rg < 4; ++rg) out[rg] = double4_t{0, 0, 0, 0};
 #pragma unroll
             for (int st = 0; st < 16; ++st)
 #pragma unroll
@@ -1290,9 +1269,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                     return;
                 }
                 BLK_STAMP(0);
-                double4_s m0[4], m1[4];
+                double4_t m0[4], m1[4];
 #pragma unroll
-                for (int rg = 0; rg < 4; ++rg) m0[rg] = m1[rg] = double4_s{0, 0, 0, 0};
+                for (int rg = 0; rg < 4; ++rg) m0[rg] = m1[rg] = double4_t{0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 16; st += 2)
 #pragma unroll
@@ -1359,11 +1338,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
         const int q0 = pass * kRhsM;
         const int nq = min(kRhsM, nrhs - q0);
         const int nfn = (nq + 15) >> 4;                 // 16-wide fragments of right-hand sides in use
-        double4_s acc[4][2];                            // [fragment of right-hand sides][fragment of rows]
+        double4_t acc[4][2];                            // [fragment of right-hand sides][fragment of rows]
 #pragma unroll
         for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
-            for (int rf = 0; rf < 2; ++rf) acc[nf][rf] = double4_s{0, 0, 0, 0};
+            for (int rf = 0; rf < 2; ++rf) acc[nf][rf] = double4_t{0, 0, 0, 0};
         double lvA[2][16], lvB[2][16];
         load_l(0, lvA);
         // one block column: stage X_jb (armed buffer -> LDS), start the loads of the next one, multiply
@@ -2605,11 +2584,11 @@ __global__ __launch_bounds__(kThreads, QG == 4 ? 1 : 2) void k_bsolve_block_mrhs
             const int c = e & 63, q = e >> 6;
             TSM(c, q) = (c < wbk && q < nq) ? x[(int64_t)(q0 + q) * ldx + D.c0 + cb + c] : 0.0;
         }
-        double4_s acc[4][QG];   // [16 columns][16 right-hand sides]: lane (q = l15, c = kq + 4 v)
+        double4_t acc[4][QG];   // [16 columns][16 right-hand sides]: lane (q = l15, c = kq + 4 v)
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < QG; ++b) acc[a][b] = double4_s{0, 0, 0, 0};
+            for (int b = 0; b < QG; ++b) acc[a][b] = double4_t{0, 0, 0, 0};
         // operand pointers of this lane: column c = 16 cg + l15 of the block (clamped), right-hand side 16 qg + l15
         const double* __restrict__ acol[4];
         const double* __restrict__ xcol[QG];
@@ -2779,9 +2758,9 @@ __global__ __launch_bounds__(kThreads, QG == 4 ? 1 : 2) void k_bsolve_block_mrhs
         if (chain) {
             // X_blk = inv(L_bb)' T on the matrix cores: X[c][q] = sum_k inv(L_bb)[k][c] T[k][q]; Dg[c][k] holds
             // inv(L_bb)[k][c] (zero for k < c).  Wave = 16 columns; the result replaces T behind a barrier.
-            double4_s out[QG];
+            double4_t out[QG];
 #pragma unroll
-            for (int qg = 0; qg < QG; ++qg) out[qg] = double4_s{0, 0, 0, 0};
+            for (int qg = 0; qg < QG; ++qg) out[qg] = double4_t{0, 0, 0, 0};
             for (int st = 4 * wave; st < kTile / 4; ++st) {   // (k < 16 wave: the inverse is zero there)
                 const double a = Dg[(16 * wave + l15) * kLdDiag + 4 * st + kq];
 #pragma unroll
@@ -2895,9 +2874,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
             const double v = brow[(int64_t)min(c, wbk - 1) * r];
             lb[st] = (kin && c < wbk) ? v : 0.0;
         }
-        double4_s am[4];
+        double4_t am[4];
 #pragma unroll
-        for (int cg = 0; cg < 4; ++cg) am[cg] = double4_s{0, 0, 0, 0};
+        for (int cg = 0; cg < 4; ++cg) am[cg] = double4_t{0, 0, 0, 0};
 #pragma unroll
         for (int st = 0; st < 16; ++st)
 #pragma unroll
@@ -2918,11 +2897,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
             const int c = e & 63, q = e >> 6;
             TSM(c, q) = (c < wbk && q < nq) ? x[(int64_t)(q0 + q) * ldx + D.c0 + cb + c] : 0.0;
         }
-        double4_s acc[4][QG];   // [16 columns][16 right-hand sides]: lane (q = l15, c = kq + 4 v)
+        double4_t acc[4][QG];   // [16 columns][16 right-hand sides]: lane (q = l15, c = kq + 4 v)
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < QG; ++b) acc[a][b] = double4_s{0, 0, 0, 0};
+            for (int b = 0; b < QG; ++b) acc[a][b] = double4_t{0, 0, 0, 0};
         // operand pointers of this lane: column c = 16 cg + l15 of the block (clamped), right-hand side 16 qg + l15
         const double* __restrict__ acol[4];
         const double* __restrict__ xcol[QG];
@@ -3151,9 +3130,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                     }
                 };
                 // P = inv(L_jj)' T: X[c'][q] = sum_{c >= c'} inv(L_jj)[c][c'] T[c][q]
-                double4_s out[4];
+                double4_t out[4];
 #pragma unroll
-                for (int cg = 0; cg < 4; ++cg) out[cg] = double4_s{0, 0, 0, 0};
+                for (int cg = 0; cg < 4; ++cg) out[cg] = double4_t{0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 16; ++st)
 #pragma unroll
@@ -3177,9 +3156,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                         return;
                     }
                     BLK_STAMP(0);
-                    double4_s m0[4], m1[4];
+                    double4_t m0[4], m1[4];
 #pragma unroll
-                    for (int cg = 0; cg < 4; ++cg) m0[cg] = m1[cg] = double4_s{0, 0, 0, 0};
+                    for (int cg = 0; cg < 4; ++cg) m0[cg] = m1[cg] = double4_t{0, 0, 0, 0};
 #pragma unroll
                     for (int st = 0; st < 16; st += 2)
 #pragma unroll
@@ -3362,9 +3341,9 @@ __global__ __launch_bounds__(64, 4) void k_bsolve_tiny_mrhs(const SnDesc* __rest
         const double* __restrict__ acol = G + (int64_t)min(l15, w - 1) * r;
         for (int q0 = 64 * (int)blockIdx.y; q0 < nrhs; q0 += 64 * (int)gridDim.y) {
             const int nq = min(64, nrhs - q0), nqg = (nq + 15) >> 4;
-            double4_s acc[4];
+            double4_t acc[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) acc[g] = double4_s{0, 0, 0, 0};
+            for (int g = 0; g < 4; ++g) acc[g] = double4_t{0, 0, 0, 0};
             const double* __restrict__ xcol[4];
             bool bok[4];
 #pragma unroll
@@ -3401,14 +3380,14 @@ __global__ __launch_bounds__(64, 4) void k_bsolve_tiny_mrhs(const SnDesc* __rest
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 if (g >= nqg) continue;
-                double4_s t;
+                double4_t t;
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int c = kq + 4 * v;
                     const double y = xcol[g][D.c0 + min(c, w - 1)];
                     t[v] = (c < w && bok[g]) ? y - acc[g][v] : 0.0;
                 }
-                double4_s out = {0, 0, 0, 0};
+                double4_t out = {0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 4; ++st) out = __builtin_amdgcn_mfma_f64_16x16x4f64(ainv[st], t[st], out, 0, 0, 0);
 #pragma unroll

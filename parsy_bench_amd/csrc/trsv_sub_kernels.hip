@@ -25,11 +25,11 @@
 
 #include <algorithm>
 
+#include "device_util.hpp"
 #include "kernels.hpp"
 
 namespace parsy {
 
-typedef double double4_s __attribute__((ext_vector_type(4)));
 
 // Ablation build (tools/build_variant.sh subabl -DPARSY_SUBABL; wrong results): PARSY_SUB_ABL=mask drops parts of a
 // member's work -- 1: the stores of x, 2: the outside rows (flush / gather), 4: the products of the rows below and their
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void k_solve_sub_mrhs(const SubMember* __restr
     const unsigned lq8 = 8u * (unsigned)((qok ? l15 : 0) * sq);
     const int trash = T.ncols + T.nout, nsl = trash + 1;
     SubPre cur, nxt;
-    double4_s Xp = {0, 0, 0, 0};   // the member before: its x is stored a member late (below)
+    double4_t Xp = {0, 0, 0, 0};   // the member before: its x is stored a member late (below)
     int pc0 = 0, pw = 0;
     SubMember Mc = members[T.m0];
     SubMember Mn = members[min(T.m0 + 1, T.m1 - 1)];   // (descriptors: two members ahead, operands: one)
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void k_solve_sub_mrhs(const SubMember* __restr
         SUB_STAMP(8 + 8 * (m - T.m0) + 2);
         // x_s = b_s - (what the members before subtracted); the slots go back to the stack as zeros (a sibling's subtree
         // uses them next) -- lanes of rows past the member's width write to the padding slot
-        double4_s X;
+        double4_t X;
         {
             double* sl[4];
             double a[4];
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void k_solve_sub_mrhs(const SubMember* __restr
 #pragma unroll
         for (int ch = 0; ch < kSubPre; ++ch) {
             if (ch < nch) {
-                double4_s D = {0, 0, 0, 0};
+                double4_t D = {0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 4; ++st) D = __builtin_amdgcn_mfma_f64_16x16x4f64(cur.a[ch][st], X[st], D, 0, 0, 0);
 #pragma unroll
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void k_solve_sub_mrhs(const SubMember* __restr
 #pragma unroll
                 for (int st = 0; st < 4; ++st) an[st] = sub_ldg(G, (unsigned)min(4 * st + kq, w - 1) * ld8 + k8);
                 swn = slots[(int64_t)(Mc.so + chn) * 4 + kq];
-                double4_s D = {0, 0, 0, 0};
+                double4_t D = {0, 0, 0, 0};
 #pragma unroll
                 for (int st = 0; st < 4; ++st) D = __builtin_amdgcn_mfma_f64_16x16x4f64(a[st], X[st], D, 0, 0, 0);
 #pragma unroll
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void k_bsolve_sub_mrhs(const SubMember* __rest
     double* __restrict__ xq = x + (int64_t)q0 * sq;
     const unsigned lq8 = 8u * (unsigned)((qok ? l15 : 0) * sq);
     SubPre cur, nxt;
-    double4_s Xp = {0, 0, 0, 0};   // (stored a member late: as in the forward kernel)
+    double4_t Xp = {0, 0, 0, 0};   // (stored a member late: as in the forward kernel)
     int pc0 = 0, pw = 0;
     SubMember Mc = members[T.m1 - 1];
     SubMember Mn = members[max(T.m1 - 2, T.m0)];
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256) void k_bsolve_sub_mrhs(const SubMember* __rest
         if (m > T.m0) sub_load<true>(Mn, L, xq, lq8, slots, sr, l15, kq, nxt, abl);
         const int w = Mc.w, r = Mc.r;
         // t = y_s - L21' x(below)  (rows past the panel's read the padding slot: 0; columns past w are dropped below)
-        double4_s A = {0, 0, 0, 0};
+        double4_t A = {0, 0, 0, 0};
         const int nch = SUB_ABL(4 | 32) ? 0 : (r - w + 15) >> 4;
 #pragma unroll
         for (int ch = 0; ch < kSubPre; ++ch) {
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void k_bsolve_sub_mrhs(const SubMember* __rest
         if (!SUB_ABL(8)) sub_inv4(Ls, Iv, l15, kq);
         __builtin_amdgcn_wave_barrier();
         const double ainv = SUB_ABL(8) ? 1.0 : Iv[16 * (l15 >> 2) + 4 * kq + (l15 & 3)];   // inv(L_bb)'[i][k] = inv(L_bb)[k][i]
-        double4_s X;
+        double4_t X;
 #pragma unroll
         for (int v = 0; v < 4; ++v) X[v] = (4 * v + kq < w && qok) ? cur.b[v] - A[v] : 0.0;
         // x_s = inv(L11') t, from the last 4-column block up
