@@ -359,6 +359,57 @@ int parsy_selinv_host(parsy_plan* plan, const double* lValues, double* z, double
  * ordering) column whose diagonal entry is not positive and finite, *logdet = NaN; < 0: error. */
 int parsy_logdet_device(parsy_plan* plan, const double* d_lValues, double* logdet, void* stream);
 
+/* ---- Gradients with respect to the values of A ---------------------------------------------------------------------
+ * Conventions.  `values` is what parsy_factor_device takes: the lower triangle of P A P' in A2 order, nnzA entries; entry
+ * q sits at the permuted position (i_q, j_q), i_q >= j_q.  SYMMETRIC PARAMETERISATION: a stored off-diagonal value stands
+ * for both A_ij and A_ji, so every gradient with respect to values[q] counts both occurrences: w_q = 2 when i_q != j_q,
+ * w_q = 1 on the diagonal.  Vectors (x, lambda) are in the caller's ordering under parsy_plan_set_perm (identity by
+ * default), column-major with a leading dimension, exactly as parsy_residual_device takes X.  Outputs `g` hold nnzA
+ * doubles in A2 order.  Every sum runs in a fixed order with no atomics: results are bitwise reproducible from call to
+ * call.  The device calls refuse host-only and solve-only plans, NULL pointers and bad sizes with parsy_last_error set
+ * and the outputs untouched; they take no part in the factorization's or the solves' state, so they may run on a plan
+ * whatever else is open on it.  Like every call on a plan they belong on ONE stream per plan: the staging workspace of
+ * parsy_pattern_outer_device and the partials of parsy_trace_inverse_device are per plan and not synchronised, so two
+ * such calls of one plan on different streams must be ordered by the caller.  A plan that never calls them allocates nothing for them; the first device call uploads
+ * the pattern's coordinates (8 nnzA bytes) and adds them, and any workspace, to the plan's device_bytes. */
+/* The pattern of A as the plan sees it: row[q] = i_q, col[q] = j_q (permuted coordinates), dst[q] = the offset of the
+ * entry in lValues / Z (where the factorization scatters values[q]).  Any pointer may be NULL; returns nnzA (< 0: error).
+ * Host-only plans too. */
+int64_t parsy_plan_pattern(const parsy_plan* plan, int32_t* row, int32_t* col, int64_t* dst);
+typedef struct parsy_grad_info {
+    int64_t entries;           /* nnzA */
+    int64_t offdiag_entries;   /* of those, i_q != j_q */
+    int64_t device_bytes;      /* coordinates + workspaces held (0 before the first device call) */
+    int32_t last_lanes;        /* lanes per entry of the last parsy_pattern_outer_device call: 0 none yet, 1 the direct
+                                * kernel, 8 / 16 / 32 / 64 the many-right-hand-side kernel */
+} parsy_grad_info;
+int parsy_grad_get_info(parsy_plan* plan, parsy_grad_info* info);   /* host-only plans too */
+/* g[q] = beta g[q] + alpha S_q,  S_q = sum_k lambda[i,k] x[j,k] + lambda[j,k] x[i,k]  (i != j),
+ *                                S_q = sum_k lambda[i,k] x[i,k]                       (i == j):
+ * S_q = d(lambda' A x) / d values[q].  With lambda = A^-1 w and alpha = -1 this is the gradient of w' x, x = A^-1 b,
+ * with respect to the values.  With beta == 0, g is not read (it may hold NaN).  Two kernels, chosen per call: fewer
+ * right-hand sides than PARSY_GRAD_MRHS_MIN (default 5, read at every call) take one thread per entry; from there on
+ * the vectors are staged with the right-hand sides of a row contiguous (workspace of 2 n pitch doubles, pitch = nrhs
+ * rounded up to 8, grown on demand) and 8 / 16 / 32 / 64 lanes share an entry.  Asynchronous on `stream`. */
+int parsy_pattern_outer_device(parsy_plan* plan, const double* d_lambda, int ldl, const double* d_x, int ldx, int nrhs,
+                               double alpha, double beta, double* d_g, void* stream);
+/* g[q] = beta g[q] + alpha w_q Z[dst[q]] for Z as parsy_selinv_device leaves it; PARSY_PATTERN_PLAIN in flags sets
+ * w_q = 1 (the entries of (P A P')^-1 themselves).  alpha = 1, beta = 0 gives d log det A / d values, bit for bit a copy
+ * or a doubling of Z's entries.  Asynchronous on `stream`. */
+#define PARSY_PATTERN_PLAIN 1
+int parsy_inverse_pattern_device(parsy_plan* plan, const double* d_z, double alpha, double beta, int flags, double* d_g,
+                                 void* stream);
+/* out[m] = tr(A^-1 B_m) = sum_q w_q Z[dst[q]] B_m[q], m < nb, for symmetric matrices B_m on A's pattern given as the
+ * columns (leading dimension ldb >= nnzA) of d_bvalues in A2 order: the derivative of log det A along B_m.  out: host,
+ * nb doubles; the call synchronises `stream`.  Two passes with fixed ranges and a fixed tree. */
+int parsy_trace_inverse_device(parsy_plan* plan, const double* d_z, const double* d_bvalues, int64_t ldb, int nb,
+                               double* out, void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  z as parsy_selinv_host returns it. */
+int parsy_pattern_outer_host(parsy_plan* plan, const double* lambda, int ldl, const double* x, int ldx, int nrhs,
+                             double alpha, double beta, double* g, double* seconds);
+int parsy_inverse_pattern_host(parsy_plan* plan, const double* z, double alpha, double beta, int flags, double* g,
+                               double* seconds);
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

@@ -88,7 +88,18 @@ EXPORTED_SYMBOLS = [
     "parsy_plan_set_perm", "parsy_residual_device", "parsy_solve_spd_device", "parsy_solve_spd_host",
     "parsy_selinv_get_info", "parsy_selinv_check", "parsy_selinv_device", "parsy_inverse_diag_device",
     "parsy_selinv_host", "parsy_logdet_device",
+    "parsy_plan_pattern", "parsy_grad_get_info", "parsy_pattern_outer_device", "parsy_inverse_pattern_device",
+    "parsy_trace_inverse_device", "parsy_pattern_outer_host", "parsy_inverse_pattern_host",
 ]
+
+
+class GradInfo(C.Structure):
+    _fields_ = [
+        ("entries", C.c_int64), ("offdiag_entries", C.c_int64), ("device_bytes", C.c_int64), ("last_lanes", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class SelinvInfo(C.Structure):
@@ -192,6 +203,14 @@ def _declare(lib):
     lib.parsy_inverse_diag_device.argtypes = [vp, vp, vp, vp]
     lib.parsy_selinv_host.argtypes = [vp, vp, vp, vp, vp]
     lib.parsy_logdet_device.argtypes = [vp, vp, vp, vp]
+    lib.parsy_plan_pattern.restype = C.c_int64
+    lib.parsy_plan_pattern.argtypes = [vp, vp, vp, vp]
+    lib.parsy_grad_get_info.argtypes = [vp, vp]
+    lib.parsy_pattern_outer_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
+    lib.parsy_inverse_pattern_device.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, vp, vp]
+    lib.parsy_trace_inverse_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp, vp]
+    lib.parsy_pattern_outer_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
+    lib.parsy_inverse_pattern_host.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -326,6 +326,70 @@ class Plan:
             raise RuntimeError("parsy_logdet_device failed: " + N.last_error())
         return out.value, int(rc)
 
+    # gradients with respect to the values of A (A2 order; symmetric parameterisation: include/parsy_amd.h) --------
+    def pattern(self) -> dict:
+        """The pattern of A as the plan sees it, per A2 entry: row, col (permuted coordinates, row >= col) and dst
+        (its offset in lValues / Z)."""
+        n = int(self.sym.nnzA)
+        out = {"row": np.zeros(n, dtype=np.int32), "col": np.zeros(n, dtype=np.int32), "dst": np.zeros(n, dtype=np.int64)}
+        if N.lib().parsy_plan_pattern(self._h, N.ptr(out["row"]), N.ptr(out["col"]), N.ptr(out["dst"])) != n:
+            raise RuntimeError("parsy_plan_pattern failed: " + N.last_error())
+        return out
+
+    @property
+    def grad_info(self) -> dict:
+        """entries, offdiag_entries, device_bytes (0 before the first device call), last_lanes (lanes per entry of the
+        last pattern_outer call: 0 none yet, 1 the direct kernel, 8 / 16 / 32 / 64)."""
+        gi = N.GradInfo()
+        if N.lib().parsy_grad_get_info(self._h, C.byref(gi)) != 0:
+            raise RuntimeError("parsy_grad_get_info failed: " + N.last_error())
+        return gi.as_dict()
+
+    def pattern_outer_device(self, d_lam: int, ldl: int, d_x: int, ldx: int, nrhs: int, d_g: int, alpha: float = 1.0,
+                             beta: float = 0.0, stream: int = 0) -> None:
+        """g[q] = beta g[q] + alpha sum_k (lam[i,k] x[j,k] + lam[j,k] x[i,k]) (one term on the diagonal), vectors in the
+        plan's ordering (set_perm)."""
+        if N.lib().parsy_pattern_outer_device(self._h, d_lam or None, ldl, d_x or None, ldx, nrhs, alpha, beta,
+                                              d_g or None, stream) != 0:
+            raise RuntimeError("parsy_pattern_outer_device failed: " + N.last_error())
+
+    def pattern_outer(self, lam, x, alpha: float = 1.0) -> np.ndarray:
+        """Host arrays (n,) or (n, nrhs) in, the sampled product (nnzA, A2 order) out."""
+        Lm = np.asfortranarray(np.asarray(lam, dtype=np.float64).reshape(self.sym.n, -1))
+        X = np.asfortranarray(np.asarray(x, dtype=np.float64).reshape(self.sym.n, -1))
+        if Lm.shape != X.shape:
+            raise ValueError(f"pattern_outer: lam is {Lm.shape}, x is {X.shape}")
+        g = np.empty(int(self.sym.nnzA), dtype=np.float64)
+        if N.lib().parsy_pattern_outer_host(self._h, Lm.ctypes.data_as(C.c_void_p), self.sym.n,
+                                            X.ctypes.data_as(C.c_void_p), self.sym.n, X.shape[1], alpha, 0.0, N.ptr(g),
+                                            None) != 0:
+            raise RuntimeError("parsy_pattern_outer_host failed: " + N.last_error())
+        return g
+
+    def inverse_pattern_device(self, d_z: int, d_g: int, alpha: float = 1.0, beta: float = 0.0, plain: bool = False,
+                               stream: int = 0) -> None:
+        """g[q] = beta g[q] + alpha w_q Z[dst[q]] (w_q = 2 off the diagonal unless plain)."""
+        if N.lib().parsy_inverse_pattern_device(self._h, d_z or None, alpha, beta, 1 if plain else 0, d_g or None,
+                                                stream) != 0:
+            raise RuntimeError("parsy_inverse_pattern_device failed: " + N.last_error())
+
+    def inverse_pattern(self, z, plain: bool = False) -> np.ndarray:
+        """z as selinv() returns it; d log det A / d values (plain: the entries of (P A P')^-1) in A2 order."""
+        zz = _f64(z)
+        if zz.size != int(self.sym.xsize):
+            raise ValueError(f"inverse_pattern: z has {zz.size} entries, xsize = {int(self.sym.xsize)}")
+        g = np.empty(int(self.sym.nnzA), dtype=np.float64)
+        if N.lib().parsy_inverse_pattern_host(self._h, N.ptr(zz), 1.0, 0.0, 1 if plain else 0, N.ptr(g), None) != 0:
+            raise RuntimeError("parsy_inverse_pattern_host failed: " + N.last_error())
+        return g
+
+    def trace_inverse_device(self, d_z: int, d_bvalues: int, ldb: int, nb: int, stream: int = 0) -> np.ndarray:
+        """tr(A^-1 B_m), m < nb, for the columns of d_bvalues (A2-ordered values on A's pattern); synchronises."""
+        out = np.zeros(max(nb, 1), dtype=np.float64)
+        if N.lib().parsy_trace_inverse_device(self._h, d_z or None, d_bvalues or None, ldb, nb, N.ptr(out), stream) != 0:
+            raise RuntimeError("parsy_trace_inverse_device failed: " + N.last_error())
+        return out[:nb]
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "errors.hpp"
+#include "grad.hpp"
 #include "hip_check.hpp"
 #include "plan_fwd.hpp"
 #include "refine.hpp"
@@ -224,6 +225,7 @@ void plan_free(parsy_plan* pl) {
     }
     refine_free(pl);
     selinv_free(pl);
+    grad_free(pl);
     delete pl;
 }
 

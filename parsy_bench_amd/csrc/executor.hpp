@@ -13,6 +13,7 @@
 namespace parsy {
 struct RefineState;
 struct SelinvState;
+struct GradState;
 }
 
 struct parsy_plan {
@@ -90,6 +91,7 @@ struct parsy_plan {
     int profiled_runs = 0;
     parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
     parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
+    parsy::GradState* grad = nullptr;       // gradients with respect to A's values (grad.hpp): made by the first such call
 };
 
 namespace parsy {

@@ -36,6 +36,8 @@ constexpr int kRefinePartials = 1024;   // workgroups of k_sym_residual (grid-st
 
 void refine_free(parsy_plan* pl);
 int plan_set_perm(parsy_plan* pl, const int* perm);
+// the device copy of that ordering, uploaded on first use (*out null: identity)
+int plan_perm_device(parsy_plan* pl, const int** out);
 int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
                   double* d_r, int ldr, int nrhs, double* berr, hipStream_t stream);
 int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L, const double* d_b, int ldb, double* d_x,

@@ -338,12 +338,8 @@ int ensure_workspace(parsy_plan* pl, int nrhs) {
         R.colstate_cap = nrhs;
         pl->device_bytes += bytes(nrhs);
     }
-    if (!R.perm.empty() && !R.d_perm) {
-        PARSY_HIP(hipMalloc((void**)&R.d_perm, R.perm.size() * 4));
-        PARSY_HIP(hipMemcpy(R.d_perm, R.perm.data(), R.perm.size() * 4, hipMemcpyHostToDevice));
-        pl->device_bytes += (int64_t)R.perm.size() * 4;
-    }
-    return 0;
+    const int* perm = nullptr;
+    return plan_perm_device(pl, &perm);
 }
 
 // r = pb - A z and the partial maxima of every column's backward error; returns the number of partials (< 0: error)
@@ -445,6 +441,19 @@ int plan_set_perm(parsy_plan* pl, const int* perm) {
         R.d_perm = nullptr;
     }
     R.perm.swap(p);
+    return 0;
+}
+
+int plan_perm_device(parsy_plan* pl, const int** out) {
+    *out = nullptr;
+    RefineState* R = pl->refine;
+    if (!R || R->perm.empty()) return 0;
+    if (!R->d_perm) {
+        PARSY_HIP(hipMalloc((void**)&R->d_perm, R->perm.size() * 4));
+        PARSY_HIP(hipMemcpy(R->d_perm, R->perm.data(), R->perm.size() * 4, hipMemcpyHostToDevice));
+        pl->device_bytes += (int64_t)R->perm.size() * 4;
+    }
+    *out = R->d_perm;
     return 0;
 }
 

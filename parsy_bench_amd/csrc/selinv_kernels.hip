@@ -503,20 +503,6 @@ int ensure_selinv(parsy_plan* pl) {
     return 0;
 }
 
-// the caller's ordering from parsy_plan_set_perm (the refinement state's copy; null: identity)
-int perm_device(parsy_plan* pl, const int** out) {
-    *out = nullptr;
-    RefineState* R = pl->refine;
-    if (!R || R->perm.empty()) return 0;
-    if (!R->d_perm) {
-        PARSY_HIP(hipMalloc((void**)&R->d_perm, R->perm.size() * 4));
-        PARSY_HIP(hipMemcpy(R->d_perm, R->perm.data(), R->perm.size() * 4, hipMemcpyHostToDevice));
-        pl->device_bytes += (int64_t)R->perm.size() * 4;
-    }
-    *out = R->d_perm;
-    return 0;
-}
-
 }  // namespace
 
 void selinv_free(parsy_plan* pl) {
@@ -563,7 +549,7 @@ int plan_inverse_diag(parsy_plan* pl, const double* d_z, double* d_diag, hipStre
     if (check_plan(pl, "parsy_inverse_diag_device") != 0) return -1;
     PARSY_HIP(hipSetDevice(pl->device));
     const int* perm = nullptr;
-    if (ensure_diag(pl) != 0 || perm_device(pl, &perm) != 0) return -1;
+    if (ensure_diag(pl) != 0 || plan_perm_device(pl, &perm) != 0) return -1;
     const int n = pl->S.n;
     if (n > 0)
         hipLaunchKernelGGL(k_selinv_diag, dim3((n + kSThreads - 1) / kSThreads), dim3(kSThreads), 0, stream, d_z,
