@@ -1,4 +1,5 @@
-// C ABI, device part: plan API and the drop-in operators (include/parsy_amd.h §1, §2).
+// C ABI, device part: plan API and the drop-in operators (include/parsy_amd.h §1, §2); the host-buffer entry points
+// (parsy_*_host) are in capi_hostcalls.hip.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -6,9 +7,7 @@
 #include <cstring>
 #include <map>
 #include <algorithm>
-#include <atomic>
 #include <mutex>
-#include <thread>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -118,6 +117,31 @@ void loud(const char* who) {
     std::fprintf(stderr, "[parsy_amd] %s failed: %s\n", who, parsy_last_error());
 }
 
+// The plan of `key`, made by build() on first use (null: build failed, nothing is cached).
+template <class Build>
+parsy_plan* cached_plan(const CacheKey& key, Build build) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = g_plans.find(key);
+    if (it != g_plans.end()) return it->second;
+    parsy_plan* pl = build();
+    if (pl) g_plans[key] = pl;
+    return pl;
+}
+
+// Supernodal etree straight from L's pattern: the parent of a supernode is the supernode of its first below-diagonal row.
+void tree_from_pattern(int n, int supNo, const int* super, const size_t* Li_ptr, const int* Li, std::vector<int>& col2sup,
+                       std::vector<int>& sparent) {
+    col2sup.assign((size_t)n, 0);
+    sparent.assign((size_t)supNo, -1);
+    for (int s = 0; s < supNo; ++s)
+        for (int k = super[s]; k < super[s + 1]; ++k) col2sup[k] = s;
+    for (int s = 0; s < supNo; ++s) {
+        const int w = super[s + 1] - super[s];
+        const size_t b = Li_ptr[super[s]], e = Li_ptr[super[s + 1]];
+        if (e - b > (size_t)w) sparent[s] = col2sup[Li[b + w]];
+    }
+}
+
 parsy_plan* cached_chol_plan(int n, int supNo, const int* blockSet, const size_t* lC,
                              const size_t* Li_ptr, const int* lR, const int* aTree,
                              const int* col2Sup, const int* cT, const int* rT, const int* c,
@@ -130,14 +154,9 @@ parsy_plan* cached_chol_plan(int n, int supNo, const int* blockSet, const size_t
     h = fnv(h, Li_ptr, sizeof(size_t) * (n + 1));
     h = fnv(h, lC, sizeof(size_t) * (n + 1));
     h = fnv(h, aTree, sizeof(int) * supNo);
-    CacheKey key{blockSet, lR, c, h, n, supNo, 0};
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) return it->second;
-    parsy_plan* pl = parsy_plan_create(n, supNo, blockSet, lC, Li_ptr, lR, aTree, col2Sup, cT, rT, c, r,
-                                       pick_device());
-    if (pl) g_plans[key] = pl;
-    return pl;
+    return cached_plan(CacheKey{blockSet, lR, c, h, n, supNo, 0}, [&] {
+        return parsy_plan_create(n, supNo, blockSet, lC, Li_ptr, lR, aTree, col2Sup, cT, rT, c, r, pick_device());
+    });
 }
 
 // the PRUNE operator: no etree, no upper pattern; the supernodal etree comes from L's pattern
@@ -153,37 +172,27 @@ parsy_plan* cached_chol_plan_prune(int n, int supNo, const int* blockSet, const 
     h = fnv(h, lC, sizeof(size_t) * (n + 1));
     h = fnv(h, prunePtr, sizeof(int) * (supNo + 1));
     h = fnv(h, pruneSet, sizeof(int) * prunePtr[supNo]);
-    CacheKey key{blockSet, lR, c, h, n, supNo, 2};
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) return it->second;
-    const int dev = pick_device();
-    if (dev >= parsy_device_count()) {
-        set_last_error("cholesky_left_par_05_prune: no usable HIP device " + std::to_string(dev) +
-                       " (this library has no CPU fallback)");
-        return nullptr;
-    }
-    std::vector<int> col2sup(n), sparent(supNo, -1);
-    for (int s = 0; s < supNo; ++s)
-        for (int k = blockSet[s]; k < blockSet[s + 1]; ++k) col2sup[k] = s;
-    for (int s = 0; s < supNo; ++s) {
-        const int w = blockSet[s + 1] - blockSet[s];
-        const size_t b = Li_ptr[blockSet[s]], e = Li_ptr[blockSet[s + 1]];
-        if (e - b > (size_t)w) sparent[s] = col2sup[lR[b + w]];
-    }
-    parsy::PatternRef P;
-    P.n = n;
-    P.nsuper = supNo;
-    P.super = blockSet;
-    P.col2sup = col2sup.data();
-    P.sparent = sparent.data();
-    P.i_ptr = Li_ptr;
-    P.s = lR;
-    P.prunePtr = prunePtr;
-    P.pruneSet = pruneSet;
-    parsy_plan* pl = parsy::plan_build(P, lC, c, r, dev);
-    if (pl) g_plans[key] = pl;
-    return pl;
+    return cached_plan(CacheKey{blockSet, lR, c, h, n, supNo, 2}, [&]() -> parsy_plan* {
+        const int dev = pick_device();
+        if (dev >= parsy_device_count()) {
+            set_last_error("cholesky_left_par_05_prune: no usable HIP device " + std::to_string(dev) +
+                           " (this library has no CPU fallback)");
+            return nullptr;
+        }
+        std::vector<int> col2sup, sparent;
+        tree_from_pattern(n, supNo, blockSet, Li_ptr, lR, col2sup, sparent);
+        parsy::PatternRef P;
+        P.n = n;
+        P.nsuper = supNo;
+        P.super = blockSet;
+        P.col2sup = col2sup.data();
+        P.sparent = sparent.data();
+        P.i_ptr = Li_ptr;
+        P.s = lR;
+        P.prunePtr = prunePtr;
+        P.pruneSet = pruneSet;
+        return parsy::plan_build(P, lC, c, r, dev);
+    });
 }
 
 parsy_plan* cached_solve_plan(int n, int supNo, const size_t* Lp, const int* Li, const size_t* Li_ptr,
@@ -193,35 +202,44 @@ parsy_plan* cached_solve_plan(int n, int supNo, const size_t* Lp, const int* Li,
     h = fnv(h, Li, sizeof(int) * Li_ptr[n]);
     h = fnv(h, Li_ptr, sizeof(size_t) * (n + 1));
     h = fnv(h, Lp, sizeof(size_t) * (n + 1));
-    CacheKey key{sup2col, Li, Lp, h, n, supNo, 1};
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) return it->second;
-    // supernodal etree straight from L's pattern: the parent of a supernode is the
-    // supernode of its first below-diagonal row.
-    std::vector<int> col2sup(n), sparent(supNo, -1);
-    for (int s = 0; s < supNo; ++s)
-        for (int k = sup2col[s]; k < sup2col[s + 1]; ++k) col2sup[k] = s;
-    for (int s = 0; s < supNo; ++s) {
-        const int w = sup2col[s + 1] - sup2col[s];
-        const size_t b = Li_ptr[sup2col[s]], e = Li_ptr[sup2col[s + 1]];
-        if (e - b > (size_t)w) sparent[s] = col2sup[Li[b + w]];
+    return cached_plan(CacheKey{sup2col, Li, Lp, h, n, supNo, 1}, [&]() -> parsy_plan* {
+        std::vector<int> col2sup, sparent;
+        tree_from_pattern(n, supNo, sup2col, Li_ptr, Li, col2sup, sparent);
+        parsy::PatternRef P;
+        P.n = n;
+        P.nsuper = supNo;
+        P.super = sup2col;
+        P.col2sup = col2sup.data();
+        P.sparent = sparent.data();
+        P.i_ptr = Li_ptr;
+        P.s = Li;
+        if (parsy_device_count() < 1) {
+            set_last_error("no usable HIP device: the BCSC solve has no CPU fallback in this library");
+            return nullptr;
+        }
+        return parsy::plan_build(P, Lp, nullptr, nullptr, pick_device());
+    });
+}
+
+// The body the three Cholesky operators share: the plan is held for the call (the staging buffers, flags and status of a
+// cached plan belong to one call at a time), the factorization runs on host buffers, timing[0..2] = wall time since t0,
+// 0, device time.  false (loudly): no plan or the call failed; otherwise *status is parsy_factor_status.
+bool dropin_factor(const char* who, parsy_plan* pl, const double* values, double* lValues, double* timing, double t0,
+                   int* status) {
+    double dev_s = 0;
+    std::unique_lock<std::mutex> use;
+    if (pl) use = std::unique_lock<std::mutex>(pl->use_mu);
+    if (!pl || parsy_factor_host(pl, values, lValues, &dev_s) != 0) {
+        loud(who);
+        return false;
     }
-    parsy::PatternRef P;
-    P.n = n;
-    P.nsuper = supNo;
-    P.super = sup2col;
-    P.col2sup = col2sup.data();
-    P.sparent = sparent.data();
-    P.i_ptr = Li_ptr;
-    P.s = Li;
-    if (parsy_device_count() < 1) {
-        set_last_error("no usable HIP device: the BCSC solve has no CPU fallback in this library");
-        return nullptr;
+    if (timing) {
+        timing[0] = now_s() - t0;
+        timing[1] = 0.0;
+        timing[2] = dev_s;
     }
-    parsy_plan* pl = parsy::plan_build(P, Lp, nullptr, nullptr, pick_device());
-    if (pl) g_plans[key] = pl;
-    return pl;
+    *status = parsy_factor_status(pl);
+    return true;
 }
 
 int dropin_solve(const char* who, int n, size_t* Lp, int* Li, double* Lx, size_t* Li_ptr,
@@ -577,7 +595,7 @@ int parsy_plan_profile(parsy_plan* pl, int enable) {
     if (!pl) return -1;
     pl->profile = enable != 0;
     if (enable == 2) {  // reset the accumulators
-        for (int k = 0; k < 10; ++k) pl->kind_ms[k] = 0, pl->kind_launches[k] = 0;
+        for (int k = 0; k < PARSY_PROFILE_KINDS; ++k) pl->kind_ms[k] = 0, pl->kind_launches[k] = 0;
         pl->profiled_runs = 0;
         pl->level_ms.clear();
     }
@@ -588,7 +606,7 @@ int parsy_plan_profile_collect(parsy_plan* pl) { return pl ? parsy::plan_collect
 
 int parsy_plan_profile_get(parsy_plan* pl, double* kind_ms, int* kind_launches, int* runs) {
     if (!pl) return -1;
-    for (int k = 0; k < 10; ++k) {  // PARSY_PROFILE_KINDS entries each
+    for (int k = 0; k < PARSY_PROFILE_KINDS; ++k) {
         if (kind_ms) kind_ms[k] = pl->kind_ms[k];
         if (kind_launches) kind_launches[k] = pl->kind_launches[k];
     }
@@ -605,198 +623,6 @@ int parsy_plan_profile_levels(parsy_plan* pl, double* main_ms, double* side_ms) 
         if (side_ms) side_ms[l] = b < pl->level_ms.size() ? pl->level_ms[b] : 0.0;
     }
     return nl;
-}
-
-// The bands of levels of the pipelined host factorization and, per band, the runs of lValues that are final once
-// the band is complete (a piece is final after the chain launch of its own level: everything that updates it comes
-// from lower levels and is applied before that launch).  Pieces are in column order = lValues order, so consecutive
-// pieces of one band are one run; runs separated by less than 128 K doubles are merged (the gap is copied early and
-// again with its own band: harmless).  Built once per plan.
-static void build_download_bands(parsy_plan* pl) {
-    const parsy::Schedule& S = pl->S;
-    const int nl = S.cnlevels, np = (int)S.csn.size();
-    // band boundaries: a band ends with the level at which another eighth of the factor's bytes has become final
-    // (few bands = few, long runs: every copy from device to pageable host memory has a fixed cost), the last band
-    // with the last level
-    {
-        std::vector<double> bytes((size_t)nl, 0.0);
-        for (int p = 0; p < np; ++p) bytes[(size_t)S.level_of[(size_t)p]] += 8.0 * S.csn[(size_t)p].w * S.csn[(size_t)p].ld;   // (ld = rows of the supernode)
-        const double total = 8.0 * (double)S.xsize;
-        pl->h_band_level.clear();
-        double run = 0, next = total / 8;
-        for (int l = 0; l < nl; ++l) {
-            run += bytes[(size_t)l];
-            if (l == nl - 1 || run >= next) {
-                pl->h_band_level.push_back(l);
-                while (next <= run) next += total / 8;
-            }
-        }
-    }
-    const size_t nb = pl->h_band_level.size();
-    pl->h_band_runs.assign(nb, {});
-    std::vector<int> band_of((size_t)nl, 0);
-    for (size_t b = 0, l = 0; b < nb; ++b)
-        for (; (int)l <= pl->h_band_level[b]; ++l) band_of[l] = (int)b;
-    const int64_t gap = 131072;
-    for (int p = 0; p < np; ++p) {
-        const parsy::SnDesc& C = S.csn[(size_t)p];
-        const parsy::SnDesc& R = S.sn[(size_t)S.csn_real[(size_t)p]];
-        // (a piece's columns are whole columns of its supernode's panel)
-        const int64_t a = R.px + (int64_t)C.rbias * R.r, e = R.px + (int64_t)(C.rbias + C.w) * R.r;
-        auto& runs = pl->h_band_runs[(size_t)band_of[(size_t)S.level_of[(size_t)p]]];
-        if (!runs.empty() && a - (runs.back().first + runs.back().second) <= gap && a >= runs.back().first)
-            runs.back().second = std::max(runs.back().second, e - runs.back().first);
-        else
-            runs.push_back({a, e - a});
-    }
-}
-
-int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, double* seconds) {
-    if (!pl || !values || !lValues) {
-        set_last_error("parsy_factor_host: null argument");
-        return -1;
-    }
-    if (pl->device < 0) {
-        set_last_error("parsy_factor_host: plan has no device");
-        return -1;
-    }
-    const parsy::Schedule& S = pl->S;
-    PARSY_HIP(hipSetDevice(pl->device));
-    if (!pl->h_values_dev) PARSY_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8));
-    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
-    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
-    // Small factors: kernels, then one download.  Large ones (PARSY_HOST_PIPELINE=0: never): the download of every
-    // band of levels runs BEHIND the kernels of the levels above it -- a worker thread copies the runs of lValues
-    // that a band has made final while this thread's stream goes on (Flan-class: 19.4 GB at PCIe speed take as long
-    // as the kernels; one after the other the call was 0.78 s).
-    // (read per call: the tests switch it; PARSY_HOST_PIPELINE=2 takes the pipelined path whatever the size)
-    const char* pe = std::getenv("PARSY_HOST_PIPELINE");
-    const bool pipeline_on = !(pe && pe[0] == '0'), pipeline_forced = pe && pe[0] == '2';
-    if (!pipeline_on || (!pipeline_forced && S.xsize * 8 < (int64_t)256 << 20) || pl->profile || S.cnlevels < 1) {
-        if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
-        PARSY_HIP(hipDeviceSynchronize());
-        if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-        PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
-        return 0;
-    }
-    if (!pl->h_ready) {
-        // streams, bands and events are made into locals and handed to the plan only when all of them exist: a setup
-        // that failed half-way must not leave a plan that "pipelines" over no band at all (and downloads nothing)
-        hipStream_t hs = nullptr, hc = nullptr;
-        std::vector<hipEvent_t> evs;
-        auto undo = [&] {
-            for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-            if (hs) (void)hipStreamDestroy(hs);
-            if (hc) (void)hipStreamDestroy(hc);
-            pl->h_band_level.clear();
-            pl->h_band_runs.clear();
-            (void)hipGetLastError();
-        };
-        bool ok = hipStreamCreateWithFlags(&hs, hipStreamNonBlocking) == hipSuccess &&
-                  hipStreamCreateWithFlags(&hc, hipStreamNonBlocking) == hipSuccess;
-        if (ok) {
-            build_download_bands(pl);
-            evs.resize(pl->h_band_level.size(), nullptr);
-            for (hipEvent_t& e : evs)
-                if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                    e = nullptr;
-                    ok = false;
-                }
-            ok = ok && !evs.empty();
-        }
-        if (!ok) {   // the plain form: kernels, then one download
-            evs.erase(std::remove(evs.begin(), evs.end(), (hipEvent_t) nullptr), evs.end());
-            undo();
-            if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
-            PARSY_HIP(hipDeviceSynchronize());
-            if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-            PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
-            return 0;
-        }
-        pl->h_stream = hs;
-        pl->h_copy = hc;
-        pl->h_band_ev = evs;
-        pl->h_ready = true;
-    }
-    const size_t nb = pl->h_band_level.size();
-    std::atomic<int> recorded{0};
-    std::atomic<int> failed{0};
-    double* const dL = pl->h_L_dev;
-    const int device = pl->device;
-    std::thread worker([&, dL, device] {
-        if (hipSetDevice(device) != hipSuccess) {
-            failed = 1;
-            return;
-        }
-        for (size_t b = 0; b < nb; ++b) {
-            while (recorded.load(std::memory_order_acquire) <= (int)b && !failed.load()) std::this_thread::yield();
-            if (failed.load()) return;
-            if (hipEventSynchronize(pl->h_band_ev[b]) != hipSuccess) {
-                failed = 1;
-                return;
-            }
-            for (const auto& r : pl->h_band_runs[b])
-                if (hipMemcpyAsync(lValues + r.first, dL + r.first, (size_t)r.second * 8, hipMemcpyDeviceToHost, pl->h_copy) !=
-                    hipSuccess) {
-                    failed = 1;
-                    return;
-                }
-            if (hipStreamSynchronize(pl->h_copy) != hipSuccess) {
-                failed = 1;
-                return;
-            }
-        }
-    });
-    int rc = parsy::plan_factor_begin(pl, pl->h_values_dev, dL, pl->h_stream, true);
-    size_t b = 0;
-    for (int lev = 0; rc == 0 && lev < S.cnlevels; ++lev) {
-        rc = parsy::plan_factor_levels(pl, lev, lev + 1, dL, pl->h_stream);
-        if (rc == 0 && b < nb && pl->h_band_level[b] == lev) {
-            if (hipEventRecord(pl->h_band_ev[b], pl->h_stream) != hipSuccess) rc = -1;
-            ++b;
-            recorded.store((int)b, std::memory_order_release);
-        }
-    }
-    if (rc == 0) rc = parsy::plan_factor_end(pl, pl->h_stream);
-    if (rc != 0) {
-        failed = 1;
-        worker.join();
-        parsy::plan_factor_abort(pl, pl->h_stream);
-        return -1;
-    }
-    const hipError_t es = hipStreamSynchronize(pl->h_stream);
-    worker.join();
-    if (es != hipSuccess || failed.load()) {
-        set_last_error("parsy_factor_host: the pipelined download failed");
-        return -1;
-    }
-    if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-    return 0;
-}
-
-int parsy_solve_host(parsy_plan* pl, const double* lValues, double* x, int nrhs, int ldx,
-                     double* seconds) {
-    if (!pl || !lValues || !x) {
-        set_last_error("parsy_solve_host: null argument");
-        return -1;
-    }
-    if (pl->device < 0) {
-        set_last_error("parsy_solve_host: plan has no device");
-        return -1;
-    }
-    const parsy::Schedule& S = pl->S;
-    PARSY_HIP(hipSetDevice(pl->device));
-    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
-    const int64_t need = (int64_t)ldx * nrhs;
-    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
-    if (parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-    PARSY_HIP(hipDeviceSynchronize());
-    if (parsy_solve_status(pl) != 0) return -1;  // (x stays untouched: it would not be the solution)
-    if (seconds) *seconds = parsy_last_solve_ms(pl) * 1e-3;
-    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
-    return 0;
 }
 
 int parsy_backsolve_device(parsy_plan* pl, const double* d_lValues, double* d_x, int nrhs, int ldx,
@@ -840,39 +666,6 @@ int parsy_rhs_ones_device(parsy_plan* pl, const double* d_lValues, double* d_b, 
     return 0;
 }
 
-int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs, int ldx, int forward,
-                      double* seconds) {
-    if (!pl || !lValues || !x) {
-        set_last_error("parsy_solve2_host: null argument");
-        return -1;
-    }
-    if (pl->device < 0) {
-        set_last_error("parsy_solve2_host: plan has no device");
-        return -1;
-    }
-    const parsy::Schedule& S = pl->S;
-    PARSY_HIP(hipSetDevice(pl->device));
-    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
-    const int64_t need = (int64_t)ldx * nrhs;
-    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
-    double sec = 0;
-    if (forward) {
-        if (parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-        PARSY_HIP(hipDeviceSynchronize());
-        if (parsy_solve_status(pl) != 0) return -1;
-        sec += parsy_last_solve_ms(pl) * 1e-3;
-    }
-    if (parsy::plan_backsolve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr) != 0) return -1;
-    PARSY_HIP(hipDeviceSynchronize());
-    if (parsy_solve_status(pl) != 0) return -1;
-    sec += parsy_last_solve_ms(pl) * 1e-3;
-    if (seconds) *seconds = sec;
-    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 int parsy_plan_set_perm(parsy_plan* pl, const int* perm) {
     if (!pl) {
         set_last_error("parsy_plan_set_perm: null plan");
@@ -900,56 +693,6 @@ int parsy_solve_spd_device(parsy_plan* pl, const double* d_values, const double*
                                      (hipStream_t)stream);
 }
 
-int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lValues, const double* b, int ldb,
-                         double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds) {
-    if (!pl || !values || !lValues || !b || !x) {
-        set_last_error("parsy_solve_spd_host: null argument");
-        return -1;
-    }
-    if (pl->device < 0) {
-        set_last_error("parsy_solve_spd_host: plan was built without a device (device < 0)");
-        return -1;
-    }
-    const parsy::Schedule& S = pl->S;
-    if (nrhs < 1 || ldb < S.n || ldx < S.n) {
-        set_last_error("parsy_solve_spd_host: need nrhs >= 1 and leading dimensions >= n");
-        return -1;
-    }
-    PARSY_HIP(hipSetDevice(pl->device));
-    if (!pl->h_values_dev) PARSY_HIP(hipMalloc((void**)&pl->h_values_dev, std::max<int64_t>(S.nnzA, 1) * 8));
-    if (!pl->h_L_dev) PARSY_HIP(hipMalloc((void**)&pl->h_L_dev, std::max<int64_t>(S.xsize, 1) * 8));
-    const int64_t need = std::max<int64_t>((int64_t)S.n * nrhs, 1);
-    PARSY_HIP(parsy::grow_device(pl->h_x_dev, pl->h_x_len, need));
-    const size_t row = (size_t)S.n * 8;
-    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
-    if (S.n > 0) PARSY_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    PARSY_HIP(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        set_last_error("parsy_solve_spd_host: hipEventCreate failed");
-        return -1;
-    }
-    (void)hipEventRecord(e0, nullptr);
-    int rc = parsy::plan_solve_refined(pl, pl->h_values_dev, pl->h_L_dev, pl->h_x_dev, S.n, pl->h_x_dev, S.n, nrhs,
-                                       max_steps, steps, berr, nullptr);
-    float ms = 0;
-    if (rc == 0 && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                    hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
-        set_last_error("parsy_solve_spd_host: timing the call failed");
-        rc = -1;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != 0) return -1;
-    // (max_steps == 0 without steps / berr: nothing synchronised inside the call, so the solves' status is read here)
-    if (parsy_solve_status(pl) != 0) return -1;
-    if (seconds) *seconds = ms * 1e-3;
-    if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 void parsy_dropin_reset(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_plans) parsy::plan_free(kv.second);
@@ -971,19 +714,8 @@ bool cholesky_left_par_05(int n, int* c, int* r, double* values, size_t* lC, int
         return false;
     }
     parsy_plan* pl = cached_chol_plan(n, supNo, blockSet, lC, Li_ptr, lR, aTree, col2Sup, cT, rT, c, r);
-    double dev_s = 0;
-    std::unique_lock<std::mutex> use;
-    if (pl) use = std::unique_lock<std::mutex>(pl->use_mu);
-    if (!pl || parsy_factor_host(pl, values, lValues, &dev_s) != 0) {
-        loud(who);
-        return false;
-    }
-    if (timing) {
-        timing[0] = now_s() - t0;
-        timing[1] = 0.0;
-        timing[2] = dev_s;
-    }
-    return parsy_factor_status(pl) == 0;
+    int st = 0;
+    return dropin_factor(who, pl, values, lValues, timing, t0, &st) && st == 0;
 }
 
 bool cholesky_left_par_05_prune(int n, int* c, int* r, double* values, size_t* lC, int* lR, size_t* Li_ptr,
@@ -1005,19 +737,8 @@ bool cholesky_left_par_05_prune(int n, int* c, int* r, double* values, size_t* l
         return false;
     }
     parsy_plan* pl = cached_chol_plan_prune(n, supNo, blockSet, lC, Li_ptr, lR, prunePtr, pruneSet, c, r);
-    double dev_s = 0;
-    std::unique_lock<std::mutex> use;
-    if (pl) use = std::unique_lock<std::mutex>(pl->use_mu);
-    if (!pl || parsy_factor_host(pl, values, lValues, &dev_s) != 0) {
-        loud(who);
-        return false;
-    }
-    if (timing) {
-        timing[0] = now_s() - t0;
-        timing[1] = 0.0;
-        timing[2] = dev_s;
-    }
-    return parsy_factor_status(pl) == 0;
+    int st = 0;
+    return dropin_factor(who, pl, values, lValues, timing, t0, &st) && st == 0;
 }
 
 bool cholesky_left_par_waveFront(int n, int* c, int* r, double* values, size_t* lC, int* lR,
@@ -1033,19 +754,8 @@ bool cholesky_left_par_waveFront(int n, int* c, int* r, double* values, size_t* 
         return false;
     }
     parsy_plan* pl = cached_chol_plan(n, supNo, blockSet, lC, Li_ptr, lR, aTree, col2Sup, cT, rT, c, r);
-    double dev_s = 0;
-    std::unique_lock<std::mutex> use;
-    if (pl) use = std::unique_lock<std::mutex>(pl->use_mu);
-    if (!pl || parsy_factor_host(pl, values, lValues, &dev_s) != 0) {
-        loud(who);
-        return false;
-    }
-    if (timing) {
-        timing[0] = now_s() - t0;
-        timing[1] = 0.0;
-        timing[2] = dev_s;
-    }
-    const int st = parsy_factor_status(pl);
+    int st = 0;
+    if (!dropin_factor(who, pl, values, lValues, timing, t0, &st)) return false;
     if (st != 0)
         std::fprintf(stderr, "[parsy_amd] %s: non-positive pivot at column %d (the reference ignores LAPACK's info here)\n",
                      who, st);

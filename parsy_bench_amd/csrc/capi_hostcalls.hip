@@ -1,0 +1,404 @@
+// C ABI, the host-buffer entry points (parsy_*_host): host arrays in, the device calls of the plan, host arrays out.
+// No kernel lives here.  A's values, the factor and the right-hand sides are staged in buffers that live as long as the
+// plan (h_values_dev, h_L_dev, h_x_dev; the selected inverse in SelinvState::h_z / h_diag); the gradient calls stage in
+// buffers of their own, freed on return.  A call owns the staging buffers while it runs: one host-buffer call per plan
+// at a time (the drop-in operators hold the plan's use_mu for that).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/parsy_amd.h"
+#include "errors.hpp"
+#include "hip_check.hpp"
+#include "executor.hpp"
+#include "plan_util.hpp"
+#include "refine.hpp"
+#include "selinv.hpp"
+
+using parsy::set_last_error;
+
+namespace {
+
+// The refusal of the factorization and the plain solves ("plan has no device"; the other calls refuse through check_plan).
+int check_device(const parsy_plan* pl, const char* who) {
+    if (pl->device >= 0) return 0;
+    set_last_error(std::string(who) + ": plan has no device");
+    return -1;
+}
+
+// The plan-lifetime staging buffers a call uses, on the device the caller has selected: the factor's always, A's values
+// on request (both made once), the right-hand sides' grown to x_len doubles (0: not used, left as it is).
+hipError_t stage(parsy_plan* pl, bool values, int64_t x_len) {
+    const parsy::Schedule& S = pl->S;
+    hipError_t e = parsy::grow_device(pl->h_L_dev, pl->h_L_len, std::max<int64_t>(S.xsize, 1));
+    if (e == hipSuccess && values) e = parsy::grow_device(pl->h_values_dev, pl->h_values_len, std::max<int64_t>(S.nnzA, 1));
+    if (e == hipSuccess) e = parsy::grow_device(pl->h_x_dev, pl->h_x_len, x_len);
+    return e;
+}
+
+// The bands of levels of the pipelined host factorization and, per band, the runs of lValues that are final once
+// the band is complete (a piece is final after the chain launch of its own level: everything that updates it comes
+// from lower levels and is applied before that launch).  Pieces are in column order = lValues order, so consecutive
+// pieces of one band are one run; runs separated by less than 128 K doubles are merged (the gap is copied early and
+// again with its own band: harmless).  Built once per plan.
+void build_download_bands(parsy_plan* pl) {
+    const parsy::Schedule& S = pl->S;
+    const int nl = S.cnlevels, np = (int)S.csn.size();
+    // band boundaries: a band ends with the level at which another eighth of the factor's bytes has become final
+    // (few bands = few, long runs: every copy from device to pageable host memory has a fixed cost), the last band
+    // with the last level
+    {
+        std::vector<double> bytes((size_t)nl, 0.0);
+        for (int p = 0; p < np; ++p) bytes[(size_t)S.level_of[(size_t)p]] += 8.0 * S.csn[(size_t)p].w * S.csn[(size_t)p].ld;   // (ld = rows of the supernode)
+        const double total = 8.0 * (double)S.xsize;
+        pl->h_band_level.clear();
+        double run = 0, next = total / 8;
+        for (int l = 0; l < nl; ++l) {
+            run += bytes[(size_t)l];
+            if (l == nl - 1 || run >= next) {
+                pl->h_band_level.push_back(l);
+                while (next <= run) next += total / 8;
+            }
+        }
+    }
+    const size_t nb = pl->h_band_level.size();
+    pl->h_band_runs.assign(nb, {});
+    std::vector<int> band_of((size_t)nl, 0);
+    for (size_t b = 0, l = 0; b < nb; ++b)
+        for (; (int)l <= pl->h_band_level[b]; ++l) band_of[l] = (int)b;
+    const int64_t gap = 131072;
+    for (int p = 0; p < np; ++p) {
+        const parsy::SnDesc& C = S.csn[(size_t)p];
+        const parsy::SnDesc& R = S.sn[(size_t)S.csn_real[(size_t)p]];
+        // (a piece's columns are whole columns of its supernode's panel)
+        const int64_t a = R.px + (int64_t)C.rbias * R.r, e = R.px + (int64_t)(C.rbias + C.w) * R.r;
+        auto& runs = pl->h_band_runs[(size_t)band_of[(size_t)S.level_of[(size_t)p]]];
+        if (!runs.empty() && a - (runs.back().first + runs.back().second) <= gap && a >= runs.back().first)
+            runs.back().second = std::max(runs.back().second, e - runs.back().first);
+        else
+            runs.push_back({a, e - a});
+    }
+}
+
+// The streams, bands and events of the pipelined download, made on its first use.  They are made into locals and handed
+// to the plan only when all of them exist: a setup that failed half-way must not leave a plan that "pipelines" over no
+// band at all (and downloads nothing).  false: the caller takes the plain form.
+bool ensure_pipeline(parsy_plan* pl) {
+    if (pl->h_ready) return true;
+    hipStream_t hs = nullptr, hc = nullptr;
+    std::vector<hipEvent_t> evs;
+    bool ok = hipStreamCreateWithFlags(&hs, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&hc, hipStreamNonBlocking) == hipSuccess;
+    if (ok) {
+        build_download_bands(pl);
+        evs.resize(pl->h_band_level.size(), nullptr);
+        for (hipEvent_t& e : evs)
+            if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+                e = nullptr;
+                ok = false;
+            }
+        ok = ok && !evs.empty();
+    }
+    if (!ok) {
+        for (hipEvent_t e : evs)
+            if (e) (void)hipEventDestroy(e);
+        if (hs) (void)hipStreamDestroy(hs);
+        if (hc) (void)hipStreamDestroy(hc);
+        pl->h_band_level.clear();
+        pl->h_band_runs.clear();
+        (void)hipGetLastError();
+        return false;
+    }
+    pl->h_stream = hs;
+    pl->h_copy = hc;
+    pl->h_band_ev = evs;
+    pl->h_ready = true;
+    return true;
+}
+
+// parsy_solve_host / parsy_solve2_host: L and x to the device, the chosen directions with the status read after each,
+// x back.  x stays untouched when a status is bad: it would not be the solution.
+int solve_staged(parsy_plan* pl, const char* who, const double* lValues, double* x, int nrhs, int ldx, bool forward,
+                 bool backward, double* seconds) {
+    if (!pl || !lValues || !x) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (check_device(pl, who) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    const int64_t need = (int64_t)ldx * nrhs;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, need));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
+    double sec = 0;
+    auto run = [&](bool back) -> int {
+        const int rc = back ? parsy::plan_backsolve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr)
+                            : parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr);
+        if (rc != 0) return -1;
+        PARSY_HIP(hipDeviceSynchronize());
+        if (parsy_solve_status(pl) != 0) return -1;
+        if (seconds) sec += parsy_last_solve_ms(pl) * 1e-3;   // (the plan's own solve events)
+        return 0;
+    };
+    if (forward && run(false) != 0) return -1;
+    if (backward && run(true) != 0) return -1;
+    if (seconds) *seconds = sec;
+    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Device buffers of one gradient host call, freed when it returns, and the call's timer.
+struct Scratch {
+    std::vector<void*> bufs;
+    parsy::EventTimer timer;
+    ~Scratch() {
+        for (void* p : bufs) (void)hipFree(p);
+    }
+    double* upload(const double* h, int64_t len, bool copy) {
+        double* d = nullptr;
+        if (hipMalloc((void**)&d, (size_t)std::max<int64_t>(len, 1) * 8) != hipSuccess) return nullptr;
+        bufs.push_back(d);
+        if (copy && len > 0 && hipMemcpy(d, h, (size_t)len * 8, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, double* seconds) {
+    const char* who = "parsy_factor_host";
+    if (!pl || !values || !lValues) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (check_device(pl, who) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, true, 0));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    // Small factors take the plain form: kernels, then one download.  Large ones (PARSY_HOST_PIPELINE=0: never): the
+    // download of every band of levels runs BEHIND the kernels of the levels above it -- a worker thread copies the runs
+    // of lValues that a band has made final while this thread's stream goes on (Flan-class: 19.4 GB at PCIe speed take as
+    // long as the kernels; one after the other the call was 0.78 s).
+    // (read per call: the tests switch it; PARSY_HOST_PIPELINE=2 takes the pipelined path whatever the size)
+    const char* pe = std::getenv("PARSY_HOST_PIPELINE");
+    const bool pipeline_on = !(pe && pe[0] == '0'), pipeline_forced = pe && pe[0] == '2';
+    if (!pipeline_on || (!pipeline_forced && S.xsize * 8 < (int64_t)256 << 20) || pl->profile || S.cnlevels < 1 ||
+        !ensure_pipeline(pl)) {
+        if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
+        PARSY_HIP(hipDeviceSynchronize());
+        if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
+        PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    const size_t nb = pl->h_band_level.size();
+    std::atomic<int> recorded{0};
+    std::atomic<int> failed{0};
+    double* const dL = pl->h_L_dev;
+    const int device = pl->device;
+    std::thread worker([&, dL, device] {
+        if (hipSetDevice(device) != hipSuccess) {
+            failed = 1;
+            return;
+        }
+        for (size_t b = 0; b < nb; ++b) {
+            while (recorded.load(std::memory_order_acquire) <= (int)b && !failed.load()) std::this_thread::yield();
+            if (failed.load()) return;
+            if (hipEventSynchronize(pl->h_band_ev[b]) != hipSuccess) {
+                failed = 1;
+                return;
+            }
+            for (const auto& r : pl->h_band_runs[b])
+                if (hipMemcpyAsync(lValues + r.first, dL + r.first, (size_t)r.second * 8, hipMemcpyDeviceToHost, pl->h_copy) !=
+                    hipSuccess) {
+                    failed = 1;
+                    return;
+                }
+            if (hipStreamSynchronize(pl->h_copy) != hipSuccess) {
+                failed = 1;
+                return;
+            }
+        }
+    });
+    int rc = parsy::plan_factor_begin(pl, pl->h_values_dev, dL, pl->h_stream, true);
+    size_t b = 0;
+    for (int lev = 0; rc == 0 && lev < S.cnlevels; ++lev) {
+        rc = parsy::plan_factor_levels(pl, lev, lev + 1, dL, pl->h_stream);
+        if (rc == 0 && b < nb && pl->h_band_level[b] == lev) {
+            if (hipEventRecord(pl->h_band_ev[b], pl->h_stream) != hipSuccess) rc = -1;
+            ++b;
+            recorded.store((int)b, std::memory_order_release);
+        }
+    }
+    if (rc == 0) rc = parsy::plan_factor_end(pl, pl->h_stream);
+    if (rc != 0) {
+        failed = 1;
+        worker.join();
+        parsy::plan_factor_abort(pl, pl->h_stream);
+        return -1;
+    }
+    const hipError_t es = hipStreamSynchronize(pl->h_stream);
+    worker.join();
+    if (es != hipSuccess || failed.load()) {
+        set_last_error(std::string(who) + ": the pipelined download failed");
+        return -1;
+    }
+    if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
+    return 0;
+}
+
+int parsy_solve_host(parsy_plan* pl, const double* lValues, double* x, int nrhs, int ldx, double* seconds) {
+    return solve_staged(pl, "parsy_solve_host", lValues, x, nrhs, ldx, true, false, seconds);
+}
+
+int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs, int ldx, int forward,
+                      double* seconds) {
+    return solve_staged(pl, "parsy_solve2_host", lValues, x, nrhs, ldx, forward != 0, true, seconds);
+}
+
+int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lValues, const double* b, int ldb,
+                         double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds) {
+    const char* who = "parsy_solve_spd_host";
+    if (!pl || !values || !lValues || !b || !x) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    if (nrhs < 1 || ldb < S.n || ldx < S.n) {
+        set_last_error(std::string(who) + ": need nrhs >= 1 and leading dimensions >= n");
+        return -1;
+    }
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, true, std::max<int64_t>((int64_t)S.n * nrhs, 1)));
+    const size_t row = (size_t)S.n * 8;
+    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice));
+    parsy::EventTimer timer;
+    if (!timer.start()) {
+        set_last_error(std::string(who) + ": hipEventCreate failed");
+        return -1;
+    }
+    if (parsy::plan_solve_refined(pl, pl->h_values_dev, pl->h_L_dev, pl->h_x_dev, S.n, pl->h_x_dev, S.n, nrhs, max_steps,
+                                  steps, berr, nullptr) != 0)
+        return -1;
+    double sec = 0;
+    if (!timer.stop(&sec)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    // (max_steps == 0 without steps / berr: nothing synchronised inside the call, so the solves' status is read here)
+    if (parsy_solve_status(pl) != 0) return -1;
+    if (seconds) *seconds = sec;
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int parsy_selinv_host(parsy_plan* pl, const double* lValues, double* z, double* diag, double* seconds) {
+    const char* who = "parsy_selinv_host";
+    if (!pl || !lValues || !z) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsIdle) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    parsy::SelinvState& X = parsy::selinv_state(pl);
+    if (hipSetDevice(pl->device) != hipSuccess) {
+        set_last_error(std::string(who) + ": hipSetDevice failed");
+        return -1;
+    }
+    if (stage(pl, false, 0) != hipSuccess ||
+        parsy::grow_device(X.h_z, X.h_z_len, std::max<int64_t>(S.xsize, 1)) != hipSuccess ||
+        parsy::grow_device(X.h_diag, X.h_diag_len, std::max<int64_t>(S.n, 1)) != hipSuccess) {
+        set_last_error(std::string(who) + ": hipMalloc failed");
+        return -1;
+    }
+    if (hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        set_last_error(std::string(who) + ": upload failed");
+        return -1;
+    }
+    parsy::EventTimer timer;
+    if (!timer.start()) {
+        set_last_error(std::string(who) + ": hipEventCreate failed");
+        return -1;
+    }
+    if (parsy_selinv_device(pl, pl->h_L_dev, X.h_z, nullptr) != 0) return -1;
+    if (diag && parsy_inverse_diag_device(pl, X.h_z, X.h_diag, nullptr) != 0) return -1;
+    if (!timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    if (hipMemcpy(z, X.h_z, (size_t)S.xsize * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (diag && S.n > 0 && hipMemcpy(diag, X.h_diag, (size_t)S.n * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_last_error(std::string(who) + ": download failed");
+        return -1;
+    }
+    return 0;
+}
+
+int parsy_pattern_outer_host(parsy_plan* pl, const double* lam, int ldl, const double* x, int ldx, int nrhs, double alpha,
+                             double beta, double* g, double* seconds) {
+    const char* who = "parsy_pattern_outer_host";
+    if (!pl || !lam || !x || !g) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsA) != 0) return -1;
+    const int n = pl->S.n;
+    if (nrhs < 1 || ldl < n || ldx < n) {
+        set_last_error(std::string(who) + ": need nrhs >= 1 and leading dimensions >= n");
+        return -1;
+    }
+    PARSY_HIP(hipSetDevice(pl->device));
+    Scratch sc;
+    const int64_t nnz = pl->S.nnzA;
+    double* d_lam = sc.upload(lam, (int64_t)ldl * (nrhs - 1) + n, true);
+    double* d_x = sc.upload(x, (int64_t)ldx * (nrhs - 1) + n, true);
+    double* d_g = sc.upload(g, nnz, beta != 0.0);
+    if (!d_lam || !d_x || !d_g || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_pattern_outer_device(pl, d_lam, ldl, d_x, ldx, nrhs, alpha, beta, d_g, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds) || (nnz > 0 && hipMemcpy(g, d_g, (size_t)nnz * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_last_error(std::string(who) + ": download failed");
+        return -1;
+    }
+    return 0;
+}
+
+int parsy_inverse_pattern_host(parsy_plan* pl, const double* z, double alpha, double beta, int flags, double* g,
+                               double* seconds) {
+    const char* who = "parsy_inverse_pattern_host";
+    if (!pl || !z || !g) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsA) != 0) return -1;
+    PARSY_HIP(hipSetDevice(pl->device));
+    Scratch sc;
+    const int64_t nnz = pl->S.nnzA;
+    double* d_z = sc.upload(z, pl->S.xsize, true);
+    double* d_g = sc.upload(g, nnz, beta != 0.0);
+    if (!d_z || !d_g || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_inverse_pattern_device(pl, d_z, alpha, beta, flags, d_g, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds) || (nnz > 0 && hipMemcpy(g, d_g, (size_t)nnz * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_last_error(std::string(who) + ": download failed");
+        return -1;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 #include "grad.hpp"
 #include "hip_check.hpp"
 #include "plan_fwd.hpp"
+#include "plan_util.hpp"
 #include "refine.hpp"
 #include "selinv.hpp"
 
@@ -17,17 +18,47 @@ namespace parsy {
 
 const Schedule& plan_schedule(const parsy_plan* plan) { return plan->S; }
 
+int check_plan(const parsy_plan* pl, const char* who, PlanNeeds needs) {
+    const std::string w(who);
+    if (pl->device < 0) return set_last_error(w + ": plan was built without a device (device < 0)"), -1;
+    if (needs == kNeedsDevice) return 0;
+    if (pl->solve_only) return set_last_error(w + ": plan was built from L's pattern only (no A pattern)"), -1;
+    if (needs == kNeedsA) return 0;
+    if (pl->sn_mask_set || pl->piece_mask_set)
+        return set_last_error(w + ": plan is restricted by parsy_plan_set_active / _set_active_pieces"), -1;
+    if (pl->factor_open) return set_last_error(w + ": a factorization is still open (parsy_factor_begin)"), -1;
+    if (pl->levels_open) return set_last_error(w + ": a solve in steps of levels is still open"), -1;
+    return 0;
+}
+
+EventTimer::~EventTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+}
+
+bool EventTimer::start() {
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return false;
+    (void)hipEventRecord(e0, nullptr);   // (a failure shows in stop(): the elapsed time cannot be read)
+    return true;
+}
+
+bool EventTimer::stop(double* seconds) {
+    float ms = 0;
+    if (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+        hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
+        return false;
+    if (seconds) *seconds = ms * 1e-3;
+    return true;
+}
+
+// a pattern or launch array of the plan: the plan owns the block (freed with the plan, or with the launch arrays)
 template <typename T>
 static int upload(parsy_plan* pl, const std::vector<T>& v, const T*& dptr, bool launch_array) {
-    dptr = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    void* d = nullptr;
-    PARSY_HIP(hipMalloc(&d, bytes));
-    (launch_array ? pl->launch_owned : pl->owned).push_back(d);
-    if (!v.empty()) PARSY_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    pl->device_bytes += (int64_t)bytes;
-    dptr = (const T*)d;
-    return 0;
+    T* d = nullptr;
+    const int rc = upload_counted(d, v, pl->device_bytes);
+    if (d) (launch_array ? pl->launch_owned : pl->owned).push_back(d);
+    dptr = rc == 0 ? d : nullptr;
+    return rc;
 }
 
 int plan_upload_launches(parsy_plan* pl) {
@@ -604,7 +635,7 @@ int plan_collect_profile(parsy_plan* pl) {
         const int k = pl->pev_kind[i];
         if (pl->pev_ms.size() <= i) pl->pev_ms.resize(i + 1, 0.f);
         pl->pev_ms[i] = ms;
-        if (k >= 0 && k < 10) {
+        if (k >= 0 && k < PARSY_PROFILE_KINDS) {
             pl->kind_ms[k] += ms;
             pl->kind_launches[k] += 1;
         }
@@ -758,19 +789,6 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
     if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, S.n, nrhs, false, stream);
     pl->solve_ldq = 0;
     return solve_end(pl, stream);
-}
-
-hipError_t grow_device(double*& buf, int64_t& len, int64_t need) {
-    if (len >= need) return hipSuccess;
-    if (buf) {
-        const hipError_t e = hipFree(buf);
-        if (e != hipSuccess) return e;
-    }
-    buf = nullptr;
-    len = 0;
-    const hipError_t e = hipMalloc((void**)&buf, (size_t)need * sizeof(double));
-    if (e == hipSuccess) len = need;
-    return e;
 }
 
 }  // namespace parsy

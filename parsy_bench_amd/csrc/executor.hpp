@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/parsy_amd.h"
 #include "kernels.hpp"
 #include "schedule.hpp"
 
@@ -43,11 +44,13 @@ struct parsy_plan {
     bool one_off = false, one_off_back = false;   // a direction whose buffers could not be allocated: level launches from then on
     const int* solve_status_word = nullptr;   // where the last solve left its status (null: dp.sinfo)
 
-    // buffers of the host-convenience calls
+    // buffers of the host-buffer calls (capi_hostcalls.hip) and their lengths in doubles: A's values, the factor, the
+    // right-hand sides; they live as long as the plan and are not counted in device_bytes
     double* h_values_dev = nullptr;
     double* h_L_dev = nullptr;
     double* h_x_dev = nullptr;
-    // host-buffer factorization with the download behind the kernels (capi_exec.hip, parsy_factor_host): its own
+    int64_t h_values_len = 0, h_L_len = 0, h_x_len = 0;
+    // host-buffer factorization with the download behind the kernels (parsy_factor_host): its own
     // streams, one event per band of levels, the (offset, length) runs of lValues that are final after each band
     hipStream_t h_stream = nullptr, h_copy = nullptr;
     std::vector<hipEvent_t> h_band_ev;
@@ -56,7 +59,6 @@ struct parsy_plan {
     int levels_nrhs = 0;
     std::vector<int> h_band_level;                                    // last level of every band
     std::vector<std::vector<std::pair<int64_t, int64_t>>> h_band_runs;
-    int64_t h_x_len = 0;
 
     // side stream of the TILES_EARLY launches + the events that order it against the main stream
     hipStream_t side_stream = nullptr;
@@ -86,8 +88,8 @@ struct parsy_plan {
     std::vector<int> pev_count;     // per mark: work items of the launch
     std::vector<float> pev_ms;      // per mark: elapsed time in the last collected run (diagnostics)
     std::vector<double> level_ms;   // accumulated ms per (level << 1 | side)
-    double kind_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int kind_launches[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double kind_ms[PARSY_PROFILE_KINDS] = {};
+    int kind_launches[PARSY_PROFILE_KINDS] = {};
     int profiled_runs = 0;
     parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
     parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
@@ -113,7 +115,5 @@ int plan_backsolve(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, i
 int plan_solve_levels(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream, int lev0,
                       int lev1, int flags);
 int plan_collect_profile(parsy_plan* plan);
-// buf (len doubles) made at least `need` doubles long; the contents are not kept
-hipError_t grow_device(double*& buf, int64_t& len, int64_t need);
 
 }  // namespace parsy

@@ -20,6 +20,7 @@
 #include "errors.hpp"
 #include "hip_check.hpp"
 #include "executor.hpp"
+#include "plan_util.hpp"
 #include "grad.hpp"
 #include "refine.hpp"
 
@@ -150,14 +151,6 @@ __global__ void k_trace_final(const double* __restrict__ part, int nparts, int n
     out[m] = s;
 }
 
-// The refusals common to the calls (as the refinement and selected-inversion calls refuse).
-int check_plan(parsy_plan* pl, const char* who) {
-    std::string w(who);
-    if (pl->device < 0) return set_last_error(w + ": plan was built without a device (device < 0)"), -1;
-    if (pl->solve_only) return set_last_error(w + ": plan was built from L's pattern only (no A pattern)"), -1;
-    return 0;
-}
-
 int ensure_host_pattern(parsy_plan* pl, const char* who) {
     if (!pl->grad) pl->grad = new GradState;
     GradState& G = *pl->grad;
@@ -173,27 +166,11 @@ int ensure_device_pattern(parsy_plan* pl, const char* who) {
     GradState& G = *pl->grad;
     PARSY_HIP(hipSetDevice(pl->device));
     if (G.d_row) return 0;
-    const size_t b = std::max<size_t>(G.P.row.size(), 1) * sizeof(int32_t);
-    PARSY_HIP(hipMalloc((void**)&G.d_row, b));
-    PARSY_HIP(hipMalloc((void**)&G.d_col, b));
-    if (!G.P.row.empty()) {
-        PARSY_HIP(hipMemcpy(G.d_row, G.P.row.data(), G.P.row.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        PARSY_HIP(hipMemcpy(G.d_col, G.P.col.data(), G.P.col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    G.pattern_bytes = 2 * (int64_t)b;
+    if (upload_counted(G.d_row, G.P.row, G.pattern_bytes) != 0 || upload_counted(G.d_col, G.P.col, G.pattern_bytes) != 0)
+        return -1;
     pl->device_bytes += G.pattern_bytes;
     std::vector<int32_t>().swap(G.P.row);   // (the host copy has served; the counts stay)
     std::vector<int32_t>().swap(G.P.col);
-    return 0;
-}
-
-// buf made at least `need` doubles long (contents not kept), its bytes counted in the plan's device_bytes
-int grow_counted(parsy_plan* pl, double*& buf, int64_t& len, int64_t need) {
-    if (len >= need) return 0;
-    pl->device_bytes -= len * 8;
-    const hipError_t e = grow_device(buf, len, need);
-    pl->device_bytes += len * 8;
-    PARSY_HIP(e);
     return 0;
 }
 
@@ -216,7 +193,7 @@ void grad_free(parsy_plan* pl) {
 int plan_pattern_outer(parsy_plan* pl, const double* d_lam, int ldl, const double* d_x, int ldx, int nrhs, double alpha,
                        double beta, double* d_g, hipStream_t stream) {
     const char* who = "parsy_pattern_outer_device";
-    if (check_plan(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsA) != 0) return -1;
     const int n = pl->S.n;
     if (nrhs < 1 || ldl < n || ldx < n)
         return set_last_error(std::string(who) + ": need nrhs >= 1 and leading dimensions >= n"), -1;
@@ -267,7 +244,7 @@ int plan_pattern_outer(parsy_plan* pl, const double* d_lam, int ldl, const doubl
 int plan_inverse_pattern(parsy_plan* pl, const double* d_z, double alpha, double beta, int flags, double* d_g,
                          hipStream_t stream) {
     const char* who = "parsy_inverse_pattern_device";
-    if (check_plan(pl, who) != 0 || ensure_device_pattern(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsA) != 0 || ensure_device_pattern(pl, who) != 0) return -1;
     GradState& G = *pl->grad;
     const int64_t nnz = pl->S.nnzA;
     if (nnz == 0) return 0;
@@ -280,7 +257,7 @@ int plan_inverse_pattern(parsy_plan* pl, const double* d_z, double alpha, double
 int plan_trace_inverse(parsy_plan* pl, const double* d_z, const double* d_b, int64_t ldb, int nb, double* out,
                        hipStream_t stream) {
     const char* who = "parsy_trace_inverse_device";
-    if (check_plan(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsA) != 0) return -1;
     const int64_t nnz = pl->S.nnzA;
     if (nb < 1 || nb > 65535 || ldb < nnz)
         return set_last_error(std::string(who) + ": need 1 <= nb <= 65535 and ldb >= nnz(A)"), -1;
@@ -301,37 +278,6 @@ int plan_trace_inverse(parsy_plan* pl, const double* d_z, const double* d_b, int
 }  // namespace parsy
 
 using parsy::set_last_error;
-
-namespace {
-
-// device buffers of one host-convenience call, freed when it returns
-struct Scratch {
-    std::vector<void*> bufs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch() {
-        for (void* p : bufs) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    double* upload(const double* h, int64_t len, bool copy) {
-        double* d = nullptr;
-        if (hipMalloc((void**)&d, (size_t)std::max<int64_t>(len, 1) * 8) != hipSuccess) return nullptr;
-        bufs.push_back(d);
-        if (copy && len > 0 && hipMemcpy(d, h, (size_t)len * 8, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    }
-    bool start() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, nullptr) == hipSuccess; }
-    bool stop(double* seconds) {
-        float ms = 0;
-        if (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-            hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-            return false;
-        if (seconds) *seconds = ms * 1e-3;
-        return true;
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -377,62 +323,6 @@ int parsy_trace_inverse_device(parsy_plan* pl, const double* d_z, const double* 
         return -1;
     }
     return parsy::plan_trace_inverse(pl, d_z, d_bvalues, ldb, nb, out, (hipStream_t)stream);
-}
-
-int parsy_pattern_outer_host(parsy_plan* pl, const double* lam, int ldl, const double* x, int ldx, int nrhs, double alpha,
-                             double beta, double* g, double* seconds) {
-    const char* who = "parsy_pattern_outer_host";
-    if (!pl || !lam || !x || !g) {
-        set_last_error(std::string(who) + ": null argument");
-        return -1;
-    }
-    if (parsy::check_plan(pl, who) != 0) return -1;
-    const int n = pl->S.n;
-    if (nrhs < 1 || ldl < n || ldx < n) {
-        set_last_error(std::string(who) + ": need nrhs >= 1 and leading dimensions >= n");
-        return -1;
-    }
-    PARSY_HIP(hipSetDevice(pl->device));
-    Scratch sc;
-    const int64_t nnz = pl->S.nnzA;
-    double* d_lam = sc.upload(lam, (int64_t)ldl * (nrhs - 1) + n, true);
-    double* d_x = sc.upload(x, (int64_t)ldx * (nrhs - 1) + n, true);
-    double* d_g = sc.upload(g, nnz, beta != 0.0);
-    if (!d_lam || !d_x || !d_g || !sc.start()) {
-        set_last_error(std::string(who) + ": device buffers could not be made");
-        return -1;
-    }
-    if (parsy::plan_pattern_outer(pl, d_lam, ldl, d_x, ldx, nrhs, alpha, beta, d_g, nullptr) != 0) return -1;
-    if (!sc.stop(seconds) || (nnz > 0 && hipMemcpy(g, d_g, (size_t)nnz * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_last_error(std::string(who) + ": download failed");
-        return -1;
-    }
-    return 0;
-}
-
-int parsy_inverse_pattern_host(parsy_plan* pl, const double* z, double alpha, double beta, int flags, double* g,
-                               double* seconds) {
-    const char* who = "parsy_inverse_pattern_host";
-    if (!pl || !z || !g) {
-        set_last_error(std::string(who) + ": null argument");
-        return -1;
-    }
-    if (parsy::check_plan(pl, who) != 0) return -1;
-    PARSY_HIP(hipSetDevice(pl->device));
-    Scratch sc;
-    const int64_t nnz = pl->S.nnzA;
-    double* d_z = sc.upload(z, pl->S.xsize, true);
-    double* d_g = sc.upload(g, nnz, beta != 0.0);
-    if (!d_z || !d_g || !sc.start()) {
-        set_last_error(std::string(who) + ": device buffers could not be made");
-        return -1;
-    }
-    if (parsy::plan_inverse_pattern(pl, d_z, alpha, beta, flags, d_g, nullptr) != 0) return -1;
-    if (!sc.stop(seconds) || (nnz > 0 && hipMemcpy(g, d_g, (size_t)nnz * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_last_error(std::string(who) + ": download failed");
-        return -1;
-    }
-    return 0;
 }
 
 }  // extern "C"

@@ -27,9 +27,9 @@ struct RefineState {
     // workspace: pb, z, r (n x nrhs each, leading dimension n) and the per-column state
     double* ws = nullptr;
     int64_t ws_len = 0;       // doubles of ws
-    void* colstate = nullptr; // berr bits partials (kPartials x nrhs u64), berr, lstres (nrhs doubles), active, steps (nrhs ints), ctl[2]
+    char* colstate = nullptr; // berr bits partials (kPartials x nrhs u64), berr, lstres (nrhs doubles), active, steps (nrhs ints), ctl[2]
+    int64_t colstate_len = 0; // bytes of colstate
     int colstate_cap = 0;     // right-hand sides colstate is made for
-    int64_t ws_bytes = 0;     // ws + colstate: their share of the plan's device_bytes
 };
 
 constexpr int kRefinePartials = 1024;   // workgroups of k_sym_residual (grid-stride over the rows) = partials per column

@@ -17,6 +17,7 @@
 #include "errors.hpp"
 #include "hip_check.hpp"
 #include "executor.hpp"
+#include "plan_util.hpp"
 #include "kernels.hpp"
 #include "refine.hpp"
 
@@ -227,7 +228,7 @@ struct ColState {
 
 ColState col_state(RefineState& R, int cap) {
     ColState c;
-    char* p = (char*)R.colstate;
+    char* p = R.colstate;
     c.part = (u64*)p;
     p += (size_t)kRefinePartials * cap * sizeof(u64);
     c.berr = (double*)p;
@@ -245,18 +246,6 @@ ColState col_state(RefineState& R, int cap) {
 RefineState& state(parsy_plan* pl) {
     if (!pl->refine) pl->refine = new RefineState;
     return *pl->refine;
-}
-
-// The refusals common to the calls (the plan's own state); `who` names the call in the message.
-int check_plan(parsy_plan* pl, const char* who) {
-    std::string w(who);
-    if (pl->device < 0) return set_last_error(w + ": plan was built without a device (device < 0)"), -1;
-    if (pl->solve_only) return set_last_error(w + ": plan was built from L's pattern only (no A pattern)"), -1;
-    if (pl->sn_mask_set || pl->piece_mask_set)
-        return set_last_error(w + ": plan is restricted by parsy_plan_set_active / _set_active_pieces"), -1;
-    if (pl->factor_open) return set_last_error(w + ": a factorization is still open (parsy_factor_begin)"), -1;
-    if (pl->levels_open) return set_last_error(w + ": a solve in steps of levels is still open"), -1;
-    return 0;
 }
 
 // Both triangles of P A P' as CSR, on first use.  (row, col) of an A2 entry q is recovered from where the factorization
@@ -301,15 +290,12 @@ int ensure_pattern(parsy_plan* pl) {
     const double mean = n > 0 ? (double)nf / n : 0;
     R.group = mean > 24 ? 32 : mean > 12 ? 16 : mean > 6 ? 8 : 4;
     PARSY_HIP(hipSetDevice(pl->device));
-    const size_t brp = (size_t)(n + 1) * 8, bci = ci.size() * 4, bvf = ci.size() * 8;
-    PARSY_HIP(hipMalloc((void**)&R.d_rp, brp));
-    PARSY_HIP(hipMalloc((void**)&R.d_ci, bci));
-    PARSY_HIP(hipMalloc((void**)&R.d_src, bci));
-    PARSY_HIP(hipMalloc((void**)&R.d_vf, bvf));
-    PARSY_HIP(hipMemcpy(R.d_rp, rp.data(), brp, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(R.d_ci, ci.data(), bci, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(R.d_src, src.data(), bci, hipMemcpyHostToDevice));
-    R.pattern_bytes = (int64_t)(brp + 2 * bci + bvf);
+    int64_t bytes = 0;
+    if (upload_counted(R.d_rp, rp, bytes) != 0 || upload_counted(R.d_ci, ci, bytes) != 0 ||
+        upload_counted(R.d_src, src, bytes) != 0)
+        return -1;
+    PARSY_HIP(hipMalloc((void**)&R.d_vf, ci.size() * 8));
+    R.pattern_bytes = bytes + (int64_t)ci.size() * 8;
     pl->device_bytes += R.pattern_bytes;
     return 0;
 }
@@ -319,24 +305,12 @@ int ensure_workspace(parsy_plan* pl, int nrhs) {
     RefineState& R = state(pl);
     const int64_t need = 3 * (int64_t)pl->S.n * nrhs;
     PARSY_HIP(hipSetDevice(pl->device));
-    if (R.ws_len < need) {
-        if (R.ws) PARSY_HIP(hipFree(R.ws));
-        pl->device_bytes -= R.ws_len * 8;
-        R.ws = nullptr;
-        R.ws_len = 0;
-        PARSY_HIP(hipMalloc((void**)&R.ws, (size_t)need * 8));
-        R.ws_len = need;
-        pl->device_bytes += need * 8;
-    }
+    if (grow_counted(pl, R.ws, R.ws_len, need) != 0) return -1;
     if (R.colstate_cap < nrhs) {
-        const auto bytes = [](int cap) { return (int64_t)cap * (kRefinePartials * 8 + 8 + 8 + 4 + 4) + 8; };
-        if (R.colstate) PARSY_HIP(hipFree(R.colstate));
-        pl->device_bytes -= R.colstate_cap ? bytes(R.colstate_cap) : 0;
-        R.colstate = nullptr;
         R.colstate_cap = 0;
-        PARSY_HIP(hipMalloc(&R.colstate, (size_t)bytes(nrhs)));
+        if (grow_counted(pl, R.colstate, R.colstate_len, (int64_t)nrhs * (kRefinePartials * 8 + 8 + 8 + 4 + 4) + 8) != 0)
+            return -1;
         R.colstate_cap = nrhs;
-        pl->device_bytes += bytes(nrhs);
     }
     const int* perm = nullptr;
     return plan_perm_device(pl, &perm);
@@ -413,7 +387,7 @@ void refine_free(parsy_plan* pl) {
     if (!R) return;
     if (pl->device >= 0) {
         for (void* p : {(void*)R->d_perm, (void*)R->d_rp, (void*)R->d_ci, (void*)R->d_src, (void*)R->d_vf, (void*)R->ws,
-                        R->colstate})
+                        (void*)R->colstate})
             if (p) (void)hipFree(p);
     }
     delete R;
@@ -460,7 +434,7 @@ int plan_perm_device(parsy_plan* pl, const int** out) {
 int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
                   double* d_r, int ldr, int nrhs, double* berr, hipStream_t stream) {
     const char* who = "parsy_residual_device";
-    if (check_plan(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsIdle) != 0) return -1;
     const int n = pl->S.n;
     if (nrhs < 1 || nrhs > 65535 || ldx < n || ldb < n || (d_r && ldr < n))
         return set_last_error(std::string(who) + ": need 1 <= nrhs <= 65535 and leading dimensions >= n"), -1;
@@ -495,7 +469,7 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
 int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L, const double* d_b, int ldb, double* d_x,
                        int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, hipStream_t stream) {
     const char* who = "parsy_solve_spd_device";
-    if (check_plan(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsIdle) != 0) return -1;
     const int n = pl->S.n;
     if (nrhs < 1 || nrhs > 65535 || ldx < n || ldb < n || max_steps < 0)
         return set_last_error(std::string(who) + ": need 1 <= nrhs <= 65535, max_steps >= 0 and leading dimensions >= n"), -1;

@@ -26,31 +26,11 @@
 #include "errors.hpp"
 #include "hip_check.hpp"
 #include "executor.hpp"
+#include "plan_util.hpp"
 #include "refine.hpp"
 #include "selinv.hpp"
 
 namespace parsy {
-
-struct SelinvState {
-    bool map_ready = false;
-    SelinvSchedule X;
-    SelinvSplit sp;
-    int64_t *d_cb = nullptr, *d_mo = nullptr;
-    int32_t* d_gmap = nullptr;
-    SelinvBc* d_bcs = nullptr;
-    int32_t* d_tasks = nullptr;
-    int64_t task_cap = 0;            // (descriptor, tile) pairs d_tasks holds
-    double* d_scr = nullptr;         // level scratch: T, Y and partial slots (64 x 64 doubles each)
-    int64_t scr_slots = 0;
-    int64_t map_bytes = 0, scr_bytes = 0;
-    bool used = false;               // a call has enqueued work that reads the descriptors / scratch
-    // log-determinant and diagonal: per column the offset of its diagonal entry, the reduction's partials and result
-    int64_t* d_doff = nullptr;
-    double* d_lpart = nullptr;       // kLogParts sums, kLogParts first bad columns (as doubles), then the result pair
-    int64_t diag_bytes = 0;
-    // buffers of parsy_selinv_host
-    double *h_z = nullptr, *h_diag = nullptr;
-};
 
 namespace {
 
@@ -412,35 +392,9 @@ __global__ void k_logdet_final(double* __restrict__ part, int nparts) {
     part[2 * kLogParts + 1] = bad + 1.0;
 }
 
-SelinvState& state(parsy_plan* pl) {
-    if (!pl->selinv) pl->selinv = new SelinvState;
-    return *pl->selinv;
-}
-
-// The refusals common to the calls (as the refinement calls refuse).
-int check_plan(parsy_plan* pl, const char* who) {
-    std::string w(who);
-    if (pl->device < 0) return set_last_error(w + ": plan was built without a device (device < 0)"), -1;
-    if (pl->solve_only) return set_last_error(w + ": plan was built from L's pattern only (no A pattern)"), -1;
-    if (pl->sn_mask_set || pl->piece_mask_set)
-        return set_last_error(w + ": plan is restricted by parsy_plan_set_active / _set_active_pieces"), -1;
-    if (pl->factor_open) return set_last_error(w + ": a factorization is still open (parsy_factor_begin)"), -1;
-    if (pl->levels_open) return set_last_error(w + ": a solve in steps of levels is still open"), -1;
-    return 0;
-}
-
-template <class T>
-int upload(T*& d, const std::vector<T>& h, int64_t& bytes) {
-    const size_t b = std::max<size_t>(h.size(), 1) * sizeof(T);
-    PARSY_HIP(hipMalloc((void**)&d, b));
-    if (!h.empty()) PARSY_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    bytes += (int64_t)b;
-    return 0;
-}
-
 // per column the offset of its diagonal entry, and the log-determinant's partials
 int ensure_diag(parsy_plan* pl) {
-    SelinvState& X = state(pl);
+    SelinvState& X = selinv_state(pl);
     if (X.d_doff) return 0;
     const Schedule& S = pl->S;
     std::vector<int64_t> doff((size_t)S.n);
@@ -448,7 +402,7 @@ int ensure_diag(parsy_plan* pl) {
         for (int q = 0; q < S.sn[s].w; ++q) doff[S.sn[s].c0 + q] = S.sn[s].px + (int64_t)q * S.sn[s].r + q;
     PARSY_HIP(hipSetDevice(pl->device));
     int64_t bytes = 0;
-    if (upload(X.d_doff, doff, bytes) != 0) return -1;
+    if (upload_counted(X.d_doff, doff, bytes) != 0) return -1;
     PARSY_HIP(hipMalloc((void**)&X.d_lpart, (2 * kLogParts + 2) * sizeof(double)));
     bytes += (2 * kLogParts + 2) * sizeof(double);
     X.diag_bytes = bytes;
@@ -458,14 +412,14 @@ int ensure_diag(parsy_plan* pl) {
 
 // the host schedule, the map on the device, and the split under the current threshold (descriptors, scratch)
 int ensure_selinv(parsy_plan* pl) {
-    SelinvState& X = state(pl);
+    SelinvState& X = selinv_state(pl);
     PARSY_HIP(hipSetDevice(pl->device));
     if (!X.map_ready) {
         std::string what;
         if (!build_selinv(pl->S, X.X, what)) return set_last_error("parsy_selinv_device: " + what), -1;
         int64_t bytes = 0;
-        if (upload(X.d_cb, X.X.cb, bytes) != 0 || upload(X.d_mo, X.X.mo, bytes) != 0 ||
-            upload(X.d_gmap, X.X.gmap, bytes) != 0)
+        if (upload_counted(X.d_cb, X.X.cb, bytes) != 0 || upload_counted(X.d_mo, X.X.mo, bytes) != 0 ||
+            upload_counted(X.d_gmap, X.X.gmap, bytes) != 0)
             return -1;
         PARSY_HIP(hipMalloc((void**)&X.d_bcs, std::max(X.X.nbc, 1) * sizeof(SelinvBc)));
         bytes += std::max(X.X.nbc, 1) * sizeof(SelinvBc);
@@ -488,22 +442,17 @@ int ensure_selinv(parsy_plan* pl) {
             PARSY_HIP(hipMemcpy(X.d_bcs, X.sp.bcs.data(), X.sp.bcs.size() * sizeof(SelinvBc), hipMemcpyHostToDevice));
         if (!X.sp.tasks.empty())
             PARSY_HIP(hipMemcpy(X.d_tasks, X.sp.tasks.data(), X.sp.tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (X.sp.scratch_slots > X.scr_slots) {
-            if (X.d_scr) PARSY_HIP(hipFree(X.d_scr));
-            X.d_scr = nullptr;
-            pl->device_bytes -= X.scr_bytes;
-            X.scr_bytes = 0;
-            X.scr_slots = 0;
-            PARSY_HIP(hipMalloc((void**)&X.d_scr, (size_t)X.sp.scratch_slots * kSlot * sizeof(double)));
-            X.scr_slots = X.sp.scratch_slots;
-            X.scr_bytes = X.scr_slots * kSlot * (int64_t)sizeof(double);
-            pl->device_bytes += X.scr_bytes;
-        }
+        if (grow_counted(pl, X.d_scr, X.scr_len, X.sp.scratch_slots * kSlot) != 0) return -1;
     }
     return 0;
 }
 
 }  // namespace
+
+SelinvState& selinv_state(parsy_plan* pl) {
+    if (!pl->selinv) pl->selinv = new SelinvState;
+    return *pl->selinv;
+}
 
 void selinv_free(parsy_plan* pl) {
     SelinvState* X = pl->selinv;
@@ -519,7 +468,7 @@ void selinv_free(parsy_plan* pl) {
 
 int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stream) {
     const char* who = "parsy_selinv_device";
-    if (check_plan(pl, who) != 0) return -1;
+    if (check_plan(pl, who, kNeedsIdle) != 0) return -1;
     const int64_t xs = pl->S.xsize;
     if (d_z < d_L + xs && d_L < d_z + xs) return set_last_error(std::string(who) + ": d_z overlaps d_lValues"), -1;
     if (ensure_selinv(pl) != 0) return -1;
@@ -546,7 +495,7 @@ int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stre
 }
 
 int plan_inverse_diag(parsy_plan* pl, const double* d_z, double* d_diag, hipStream_t stream) {
-    if (check_plan(pl, "parsy_inverse_diag_device") != 0) return -1;
+    if (check_plan(pl, "parsy_inverse_diag_device", kNeedsIdle) != 0) return -1;
     PARSY_HIP(hipSetDevice(pl->device));
     const int* perm = nullptr;
     if (ensure_diag(pl) != 0 || plan_perm_device(pl, &perm) != 0) return -1;
@@ -559,7 +508,7 @@ int plan_inverse_diag(parsy_plan* pl, const double* d_z, double* d_diag, hipStre
 }
 
 int plan_logdet(parsy_plan* pl, const double* d_L, double* logdet, hipStream_t stream) {
-    if (check_plan(pl, "parsy_logdet_device") != 0) return -1;
+    if (check_plan(pl, "parsy_logdet_device", kNeedsIdle) != 0) return -1;
     PARSY_HIP(hipSetDevice(pl->device));
     if (ensure_diag(pl) != 0) return -1;
     SelinvState& X = *pl->selinv;
@@ -606,7 +555,7 @@ int parsy_selinv_get_info(parsy_plan* pl, parsy_selinv_info* info) {
     info->tiled_block_columns = sp.ntiled;
     info->launches = sp.launches;
     info->flops = X->flops;
-    info->device_bytes = pl->selinv ? pl->selinv->map_bytes + pl->selinv->scr_bytes : 0;
+    info->device_bytes = pl->selinv ? pl->selinv->map_bytes + pl->selinv->scr_len * 8 : 0;
     return 0;
 }
 
@@ -632,56 +581,6 @@ int parsy_logdet_device(parsy_plan* pl, const double* d_lValues, double* logdet,
         return -1;
     }
     return parsy::plan_logdet(pl, d_lValues, logdet, (hipStream_t)stream);
-}
-
-int parsy_selinv_host(parsy_plan* pl, const double* lValues, double* z, double* diag, double* seconds) {
-    if (!pl || !lValues || !z) {
-        set_last_error("parsy_selinv_host: null argument");
-        return -1;
-    }
-    if (parsy::check_plan(pl, "parsy_selinv_host") != 0) return -1;
-    const parsy::Schedule& S = pl->S;
-    parsy::SelinvState& X = parsy::state(pl);
-    if (hipSetDevice(pl->device) != hipSuccess) {
-        set_last_error("parsy_selinv_host: hipSetDevice failed");
-        return -1;
-    }
-    const size_t xb = (size_t)std::max<int64_t>(S.xsize, 1) * 8, nb = (size_t)std::max(S.n, 1) * 8;
-    if ((!pl->h_L_dev && hipMalloc((void**)&pl->h_L_dev, xb) != hipSuccess) ||
-        (!X.h_z && hipMalloc((void**)&X.h_z, xb) != hipSuccess) ||
-        (!X.h_diag && hipMalloc((void**)&X.h_diag, nb) != hipSuccess)) {
-        set_last_error("parsy_selinv_host: hipMalloc failed");
-        return -1;
-    }
-    if (hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        set_last_error("parsy_selinv_host: upload failed");
-        return -1;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        set_last_error("parsy_selinv_host: hipEventCreate failed");
-        return -1;
-    }
-    (void)hipEventRecord(e0, nullptr);
-    int rc = parsy::plan_selinv(pl, pl->h_L_dev, X.h_z, nullptr);
-    if (rc == 0 && diag) rc = parsy::plan_inverse_diag(pl, X.h_z, X.h_diag, nullptr);
-    float ms = 0;
-    if (rc == 0 && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                    hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
-        set_last_error("parsy_selinv_host: timing the call failed");
-        rc = -1;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != 0) return -1;
-    if (seconds) *seconds = ms * 1e-3;
-    if (hipMemcpy(z, X.h_z, (size_t)S.xsize * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        (diag && S.n > 0 && hipMemcpy(diag, X.h_diag, (size_t)S.n * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
-        set_last_error("parsy_selinv_host: download failed");
-        return -1;
-    }
-    return 0;
 }
 
 }  // extern "C"
