@@ -327,6 +327,51 @@ int parsy_solve_spd_device(parsy_plan* plan, const double* d_values, const doubl
 int parsy_solve_spd_host(parsy_plan* plan, const double* values, const double* lValues, const double* b, int ldb,
                          double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds);
 
+/* ---- Forward error bounds and a condition estimate of the SPD solve ---------------------------------------------
+ * The companions of the backward error above, as LAPACK has them: dporfs's FERR, a bound on
+ * ||x - x_true||_inf / ||x||_inf for every right-hand side, and dpocon's reciprocal condition number.  Both rest on
+ * Higham's 1-norm estimator (dlacn2), run on the device for all columns at once with the factor as the operator:
+ *   FERR_q  = est || |A^-1| w_q ||_inf / ||x_q||_inf,  w = |r| + nz eps (|A||x| + |b|)  (nz = most entries of a row + 1,
+ *             eps = 2^-53, dporfs's safe1 added where |A||x| + |b| <= safe2),
+ *   RCOND   = 1 / (||A||_1 est ||A^-1||_1)  (0 when the estimate is 0).
+ * Every column advances in lockstep through many-right-hand-side solves: a call enqueues at most 11 forward + backward
+ * solve pairs whatever nrhs is (dlacn2's 1 + 1 + 4 x 2 + 1 applications), and synchronises `stream` once per pair.  A
+ * column that finishes early rides along with a zero operand.  Given the same solve results the estimates are bitwise
+ * reproducible (fixed reduction orders, no float atomics).  An estimate is a lower bound of the quantity it estimates,
+ * in practice within a factor 3 of it and usually exact to rounding.
+ * STALE FACTOR: the operator of both estimates is (L L')^-1, the inverse of the matrix that was FACTORED; anorm, the
+ * residual r and the weights w come from `values`.  When `values` differ from the factored values, FERR bounds the
+ * error only as far as (L L')^-1 stands for A^-1 (to first order in the difference), and RCOND is
+ * 1 / (||A||_1 ||(L L')^-1||_1): the numbers describe the factored matrix.
+ * A non-finite estimate is returned as NaN with return value 0.  Refused, with parsy_last_error set and the outputs
+ * untouched: what the refinement calls refuse, nrhs > 65535, and a solve whose hand-off wait timed out.  The first call
+ * allocates its workspace (two n x nrhs vectors, a byte per entry for the saved signs, the column states) and adds it to
+ * the plan's device_bytes. */
+typedef struct parsy_cond_info {
+    int32_t applications;   /* solve pairs (forward + backward) the last bounds / rcond call enqueued */
+    int32_t columns;        /* right-hand sides of that call (1 for rcond) */
+    int64_t device_bytes;   /* workspace held by this feature (0 before the first device call) */
+} parsy_cond_info;
+int parsy_cond_get_info(parsy_plan* plan, parsy_cond_info* info);      /* host-only plans too */
+/* BERR and FERR of a given X (caller's ordering, as parsy_residual_device takes it).  ferr / berr: host, nrhs entries,
+ * either may be NULL (both NULL is refused).  Synchronises stream. */
+int parsy_error_bounds_device(parsy_plan* plan, const double* d_values, const double* d_lValues, const double* d_x,
+                              int ldx, const double* d_b, int ldb, int nrhs, double* ferr, double* berr, void* stream);
+/* parsy_solve_spd_device with FERR of the returned X (taken from the vectors the refinement ends with: no second
+ * permutation in).  ferr == NULL: exactly parsy_solve_spd_device. */
+int parsy_solve_spd_bounds_device(parsy_plan* plan, const double* d_values, const double* d_lValues, const double* d_b,
+                                  int ldb, double* d_x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr,
+                                  double* ferr, void* stream);
+int parsy_solve_spd_bounds_host(parsy_plan* plan, const double* values, const double* lValues, const double* b, int ldb,
+                                double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* ferr,
+                                double* seconds);
+/* dpocon: *anorm = ||A||_1 of `values`, *rcond = 1 / (anorm * est ||(L L')^-1||_1).  Either may be NULL, not both (with
+ * rcond NULL no solve is enqueued).  Host pointers; synchronises stream. */
+int parsy_rcond_device(parsy_plan* plan, const double* d_values, const double* d_lValues, double* anorm, double* rcond,
+                       void* stream);
+int parsy_rcond_host(parsy_plan* plan, const double* values, const double* lValues, double* anorm, double* rcond,
+                     double* seconds);
+
 /* ---- Selected inversion: entries of A^-1 on the pattern of L, and log det A -------------------------------------
  * Z = (P A P')^-1 on the stored pattern of L by the Takahashi recurrences, level by level from the root of the tree of
  * the block columns (at most 64 columns of a supernode each).  Two kernel paths: a tiled one (FP64 MFMA, one workgroup

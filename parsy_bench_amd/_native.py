@@ -90,7 +90,16 @@ EXPORTED_SYMBOLS = [
     "parsy_selinv_host", "parsy_logdet_device",
     "parsy_plan_pattern", "parsy_grad_get_info", "parsy_pattern_outer_device", "parsy_inverse_pattern_device",
     "parsy_trace_inverse_device", "parsy_pattern_outer_host", "parsy_inverse_pattern_host",
+    "parsy_cond_get_info", "parsy_error_bounds_device", "parsy_solve_spd_bounds_device", "parsy_solve_spd_bounds_host",
+    "parsy_rcond_device", "parsy_rcond_host",
 ]
+
+
+class CondInfo(C.Structure):
+    _fields_ = [("applications", C.c_int32), ("columns", C.c_int32), ("device_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GradInfo(C.Structure):
@@ -196,6 +205,12 @@ def _declare(lib):
     lib.parsy_residual_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.parsy_solve_spd_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.parsy_solve_spd_host.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_cond_get_info.argtypes = [vp, vp]
+    lib.parsy_error_bounds_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_solve_spd_bounds_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.parsy_solve_spd_bounds_host.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.parsy_rcond_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.parsy_rcond_host.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.parsy_selinv_get_info.argtypes = [vp, vp]
     lib.parsy_selinv_check.restype = C.c_longlong
     lib.parsy_selinv_check.argtypes = [vp]

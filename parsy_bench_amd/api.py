@@ -262,10 +262,11 @@ class Plan:
             raise RuntimeError("parsy_solve_spd_device failed: " + N.last_error())
         return steps, berr
 
-    def solve_refined(self, values, lValues, b, max_steps: int = 5):
+    def solve_refined(self, values, lValues, b, max_steps: int = 5, bounds: bool = False):
         """x with A x = b for the ORIGINAL matrix (caller's ordering, like solve_spd), refined on the device against
         `values` (A2 order; they may differ from the values lValues was factored from).  On first use the plan takes
-        sym.Perm as its ordering.  Returns (x, {"steps", "berr", "seconds"})."""
+        sym.Perm as its ordering.  Returns (x, {"steps", "berr", "seconds"}); bounds=True adds "ferr", the forward error
+        bound of every column (parsy_solve_spd_bounds_host)."""
         if not getattr(self, "_perm_set", False):
             self.set_perm(self.sym.Perm)
             self._perm_set = True
@@ -278,12 +279,66 @@ class Plan:
         steps = np.zeros(nrhs, dtype=np.int32)
         berr = np.zeros(nrhs, dtype=np.float64)
         sec = C.c_double(0)
+        if bounds:
+            ferr = np.zeros(nrhs, dtype=np.float64)
+            if N.lib().parsy_solve_spd_bounds_host(self._h, N.ptr(vals), N.ptr(lv), B.ctypes.data_as(C.c_void_p),
+                                                   self.sym.n, X.ctypes.data_as(C.c_void_p), self.sym.n, nrhs, max_steps,
+                                                   N.ptr(steps), N.ptr(berr), N.ptr(ferr), C.byref(sec)) != 0:
+                raise RuntimeError("parsy_solve_spd_bounds_host failed: " + N.last_error())
+            x = X[:, 0].copy() if one else np.ascontiguousarray(X)
+            return x, {"steps": steps, "berr": berr, "seconds": sec.value, "ferr": ferr}
         if N.lib().parsy_solve_spd_host(self._h, N.ptr(vals), N.ptr(lv), B.ctypes.data_as(C.c_void_p), self.sym.n,
                                         X.ctypes.data_as(C.c_void_p), self.sym.n, nrhs, max_steps, N.ptr(steps),
                                         N.ptr(berr), C.byref(sec)) != 0:
             raise RuntimeError("parsy_solve_spd_host failed: " + N.last_error())
         x = X[:, 0].copy() if one else np.ascontiguousarray(X)
         return x, {"steps": steps, "berr": berr, "seconds": sec.value}
+
+    # forward error bounds (dporfs's FERR) and the reciprocal condition number (dpocon) ---------------------------
+    @property
+    def cond_info(self) -> dict:
+        """applications (solve pairs of the last bounds / rcond call), columns, device_bytes (0 before the first call)."""
+        ci = N.CondInfo()
+        if N.lib().parsy_cond_get_info(self._h, C.byref(ci)) != 0:
+            raise RuntimeError("parsy_cond_get_info failed: " + N.last_error())
+        return ci.as_dict()
+
+    def error_bounds_device(self, d_values: int, d_lValues: int, d_x: int, ldx: int, d_b: int, ldb: int, nrhs: int,
+                            stream: int = 0):
+        """(ferr, berr) of a given X (the plan's ordering, as residual_device takes it): the forward error bound and the
+        componentwise backward error of every column."""
+        ferr = np.zeros(max(nrhs, 0), dtype=np.float64)
+        berr = np.zeros(max(nrhs, 0), dtype=np.float64)
+        if N.lib().parsy_error_bounds_device(self._h, d_values or None, d_lValues or None, d_x or None, ldx, d_b or None,
+                                             ldb, nrhs, N.ptr(ferr), N.ptr(berr), stream) != 0:
+            raise RuntimeError("parsy_error_bounds_device failed: " + N.last_error())
+        return ferr, berr
+
+    def solve_spd_bounds_device(self, d_values: int, d_lValues: int, d_b: int, ldb: int, d_x: int, ldx: int, nrhs: int,
+                                max_steps: int = 5, stream: int = 0):
+        """solve_spd_device with the forward error bound of the returned X: (steps, berr, ferr)."""
+        steps = np.zeros(nrhs, dtype=np.int32)
+        berr = np.zeros(nrhs, dtype=np.float64)
+        ferr = np.zeros(nrhs, dtype=np.float64)
+        if N.lib().parsy_solve_spd_bounds_device(self._h, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps,
+                                                 N.ptr(steps), N.ptr(berr), N.ptr(ferr), stream) != 0:
+            raise RuntimeError("parsy_solve_spd_bounds_device failed: " + N.last_error())
+        return steps, berr, ferr
+
+    def rcond_device(self, d_values: int, d_lValues: int, stream: int = 0):
+        """(rcond, anorm): 1 / (||A||_1 est ||(L L')^-1||_1) and ||A||_1 of the values (dpocon)."""
+        an, rc = C.c_double(0), C.c_double(0)
+        if N.lib().parsy_rcond_device(self._h, d_values or None, d_lValues or None, C.byref(an), C.byref(rc), stream) != 0:
+            raise RuntimeError("parsy_rcond_device failed: " + N.last_error())
+        return rc.value, an.value
+
+    def rcond(self, values, lValues):
+        """Host arrays in: (rcond, anorm, device_seconds)."""
+        vals, lv = _f64(values), _f64(lValues)
+        an, rc, sec = C.c_double(0), C.c_double(0), C.c_double(0)
+        if N.lib().parsy_rcond_host(self._h, N.ptr(vals), N.ptr(lv), C.byref(an), C.byref(rc), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_rcond_host failed: " + N.last_error())
+        return rc.value, an.value, sec.value
 
     # selected inversion: entries of A^-1 on the pattern of L, and log det A ------------------------------------
     @property

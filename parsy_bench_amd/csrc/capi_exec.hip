@@ -19,6 +19,7 @@
 #include "executor.hpp"
 #include "inspector.hpp"
 #include "refine.hpp"
+#include "cond.hpp"
 
 using parsy::set_last_error;
 
@@ -685,12 +686,37 @@ int parsy_residual_device(parsy_plan* pl, const double* d_values, const double* 
 
 int parsy_solve_spd_device(parsy_plan* pl, const double* d_values, const double* d_lValues, const double* d_b, int ldb,
                            double* d_x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, void* stream) {
+    return parsy_solve_spd_bounds_device(pl, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps, steps, berr, nullptr,
+                                         stream);
+}
+
+int parsy_solve_spd_bounds_device(parsy_plan* pl, const double* d_values, const double* d_lValues, const double* d_b, int ldb,
+                                  double* d_x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* ferr,
+                                  void* stream) {
     if (!pl || !d_values || !d_lValues || !d_b || !d_x) {
-        set_last_error("parsy_solve_spd_device: null argument");
+        set_last_error(std::string(ferr ? "parsy_solve_spd_bounds_device" : "parsy_solve_spd_device") + ": null argument");
         return -1;
     }
-    return parsy::plan_solve_refined(pl, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps, steps, berr,
+    return parsy::plan_solve_refined(pl, d_values, d_lValues, d_b, ldb, d_x, ldx, nrhs, max_steps, steps, berr, ferr,
                                      (hipStream_t)stream);
+}
+
+int parsy_error_bounds_device(parsy_plan* pl, const double* d_values, const double* d_lValues, const double* d_x, int ldx,
+                              const double* d_b, int ldb, int nrhs, double* ferr, double* berr, void* stream) {
+    if (!pl || !d_values || !d_lValues || !d_x || !d_b || (!ferr && !berr)) {
+        set_last_error("parsy_error_bounds_device: null argument (ferr and berr may not both be NULL)");
+        return -1;
+    }
+    return parsy::plan_error_bounds(pl, d_values, d_lValues, d_x, ldx, d_b, ldb, nrhs, ferr, berr, (hipStream_t)stream);
+}
+
+int parsy_rcond_device(parsy_plan* pl, const double* d_values, const double* d_lValues, double* anorm, double* rcond,
+                       void* stream) {
+    if (!pl || !d_values || !d_lValues || (!anorm && !rcond)) {
+        set_last_error("parsy_rcond_device: null argument (anorm and rcond may not both be NULL)");
+        return -1;
+    }
+    return parsy::plan_rcond(pl, d_values, d_lValues, anorm, rcond, (hipStream_t)stream);
 }
 
 void parsy_dropin_reset(void) {

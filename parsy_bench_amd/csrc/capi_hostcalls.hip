@@ -18,6 +18,7 @@
 #include "executor.hpp"
 #include "plan_util.hpp"
 #include "refine.hpp"
+#include "cond.hpp"
 #include "selinv.hpp"
 
 using parsy::set_last_error;
@@ -266,7 +267,13 @@ int parsy_solve2_host(parsy_plan* pl, const double* lValues, double* x, int nrhs
 
 int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lValues, const double* b, int ldb,
                          double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* seconds) {
-    const char* who = "parsy_solve_spd_host";
+    return parsy_solve_spd_bounds_host(pl, values, lValues, b, ldb, x, ldx, nrhs, max_steps, steps, berr, nullptr, seconds);
+}
+
+int parsy_solve_spd_bounds_host(parsy_plan* pl, const double* values, const double* lValues, const double* b, int ldb,
+                                double* x, int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* ferr,
+                                double* seconds) {
+    const char* who = ferr ? "parsy_solve_spd_bounds_host" : "parsy_solve_spd_host";
     if (!pl || !values || !lValues || !b || !x) {
         set_last_error(std::string(who) + ": null argument");
         return -1;
@@ -289,7 +296,7 @@ int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lVa
         return -1;
     }
     if (parsy::plan_solve_refined(pl, pl->h_values_dev, pl->h_L_dev, pl->h_x_dev, S.n, pl->h_x_dev, S.n, nrhs, max_steps,
-                                  steps, berr, nullptr) != 0)
+                                  steps, berr, ferr, nullptr) != 0)
         return -1;
     double sec = 0;
     if (!timer.stop(&sec)) {
@@ -300,6 +307,35 @@ int parsy_solve_spd_host(parsy_plan* pl, const double* values, const double* lVa
     if (parsy_solve_status(pl) != 0) return -1;
     if (seconds) *seconds = sec;
     if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int parsy_rcond_host(parsy_plan* pl, const double* values, const double* lValues, double* anorm, double* rcond,
+                     double* seconds) {
+    const char* who = "parsy_rcond_host";
+    if (!pl || !values || !lValues || (!anorm && !rcond)) {
+        set_last_error(std::string(who) + ": null argument (anorm and rcond may not both be NULL)");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, true, 0));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    parsy::EventTimer timer;
+    if (!timer.start()) {
+        set_last_error(std::string(who) + ": hipEventCreate failed");
+        return -1;
+    }
+    double an = 0, rc = 0;
+    if (parsy::plan_rcond(pl, pl->h_values_dev, pl->h_L_dev, &an, rcond ? &rc : nullptr, nullptr) != 0) return -1;
+    if (!timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    if (anorm) *anorm = an;
+    if (rcond) *rcond = rc;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "cond.hpp"
 #include "errors.hpp"
 #include "grad.hpp"
 #include "hip_check.hpp"
@@ -257,6 +258,7 @@ void plan_free(parsy_plan* pl) {
     refine_free(pl);
     selinv_free(pl);
     grad_free(pl);
+    cond_free(pl);
     delete pl;
 }
 

@@ -15,6 +15,7 @@ namespace parsy {
 struct RefineState;
 struct SelinvState;
 struct GradState;
+struct CondState;
 }
 
 struct parsy_plan {
@@ -94,6 +95,7 @@ struct parsy_plan {
     parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
     parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
     parsy::GradState* grad = nullptr;       // gradients with respect to A's values (grad.hpp): made by the first such call
+    parsy::CondState* cond = nullptr;       // forward error bounds / condition estimate (cond.hpp): made by the first such call
 };
 
 namespace parsy {

@@ -20,33 +20,19 @@
 #include "plan_util.hpp"
 #include "kernels.hpp"
 #include "refine.hpp"
+#include "cond.hpp"
 
 namespace parsy {
 
 namespace {
 
-constexpr int kRThreads = 256;
-using u64 = unsigned long long;
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-    const int lo = __shfl_xor((int)(unsigned)v, m), hi = __shfl_xor((int)(unsigned)(v >> 32), m);
-    return ((u64)(unsigned)hi << 32) | (u64)(unsigned)lo;
-}
+constexpr int kRThreads = kRefineThreads;
 
 __device__ __forceinline__ u64 berr_bits(double b, double rr, double den, double safe1, double safe2) {
     // dporfs: den > safe2 ? |r| / den : (|r| + safe1) / (den + safe1); den = |b| + sum |a||z|
     const double d = fabs(b) + den;
     const double ratio = d > safe2 ? fabs(rr) / d : (fabs(rr) + safe1) / (d + safe1);
     return (u64)__double_as_longlong(ratio);
-}
-
-// One wave's max, then the workgroup's across its four waves; lane 0 of wave w leaves its value in sm[w].
-__device__ __forceinline__ u64 block_max(u64 v, u64* sm) {
-    for (int o = 32; o; o >>= 1) v = max(v, shfl_xor_u64(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return max(max(sm[0], sm[1]), max(sm[2], sm[3]));
 }
 
 // 1-4 right-hand sides (z, pb, r column-major, leading dimension n): G lanes per row split its entries (lane g takes
@@ -219,12 +205,12 @@ __global__ __launch_bounds__(kRThreads) void k_refine_state(const u64* __restric
 
 dim3 grid_nq(int n, int nrhs) { return dim3((unsigned)((n + kRThreads - 1) / kRThreads), (unsigned)nrhs); }
 
-// the per-column state inside colstate (refine.hpp)
-struct ColState {
-    u64* part;
-    double *berr, *lstres;
-    int *active, *steps, *ctl;
-};
+RefineState& state(parsy_plan* pl) {
+    if (!pl->refine) pl->refine = new RefineState;
+    return *pl->refine;
+}
+
+}  // namespace
 
 ColState col_state(RefineState& R, int cap) {
     ColState c;
@@ -243,14 +229,9 @@ ColState col_state(RefineState& R, int cap) {
     return c;
 }
 
-RefineState& state(parsy_plan* pl) {
-    if (!pl->refine) pl->refine = new RefineState;
-    return *pl->refine;
-}
-
 // Both triangles of P A P' as CSR, on first use.  (row, col) of an A2 entry q is recovered from where the factorization
 // scatters it: a_dst[q] = px + (col - c0) * r + (position of row in the supernode's row list).
-int ensure_pattern(parsy_plan* pl) {
+int refine_ensure_pattern(parsy_plan* pl) {
     RefineState& R = state(pl);
     if (R.d_rp) return 0;
     const Schedule& S = pl->S;
@@ -301,7 +282,7 @@ int ensure_pattern(parsy_plan* pl) {
 }
 
 // pb, z, r (n x nrhs) and the per-column state, grown on demand; the perm's device copy
-int ensure_workspace(parsy_plan* pl, int nrhs) {
+int refine_ensure_workspace(parsy_plan* pl, int nrhs) {
     RefineState& R = state(pl);
     const int64_t need = 3 * (int64_t)pl->S.n * nrhs;
     PARSY_HIP(hipSetDevice(pl->device));
@@ -317,7 +298,7 @@ int ensure_workspace(parsy_plan* pl, int nrhs) {
 }
 
 // r = pb - A z and the partial maxima of every column's backward error; returns the number of partials (< 0: error)
-int residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* r, int nrhs, u64* part,
+int refine_residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* r, int nrhs, u64* part,
                      hipStream_t stream) {
     RefineState& R = *pl->refine;
     const int n = pl->S.n;
@@ -357,7 +338,7 @@ int residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* 
     return nb;
 }
 
-int gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream) {
+int refine_gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream) {
     RefineState& R = *pl->refine;
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(8192, (R.nnz_full + kRThreads - 1) / kRThreads));
     hipLaunchKernelGGL(k_refine_gather_values, dim3((unsigned)nb), dim3(kRThreads), 0, stream, d_values, R.d_src, R.d_vf,
@@ -368,7 +349,7 @@ int gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream) {
 
 // forward + backward solve of the permuted system in place on x (leading dimension n); every solve's status word is
 // folded into ctl[1] on the device
-int solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* ctl, hipStream_t stream) {
+int refine_solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* ctl, hipStream_t stream) {
     const int n = pl->S.n;
     if (plan_solve(pl, d_L, x, nrhs, n, stream) != 0) return -1;
     hipLaunchKernelGGL(k_refine_note_status, dim3(1), dim3(64), 0, stream,
@@ -380,7 +361,24 @@ int solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* c
     return 0;
 }
 
-}  // namespace
+int refine_permute_in(parsy_plan* pl, const double* src, int64_t ld, double* dst, double* dst2, int nrhs,
+                      hipStream_t stream) {
+    const int n = pl->S.n;
+    if (n > 0)
+        hipLaunchKernelGGL(k_refine_permute_in, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, src, ld, pl->refine->d_perm,
+                           dst, dst2, n);
+    PARSY_HIP(hipGetLastError());
+    return 0;
+}
+
+int refine_report_berr(parsy_plan* pl, int nb, int nrhs, hipStream_t stream) {
+    RefineState& R = *pl->refine;
+    const ColState c = col_state(R, R.colstate_cap);
+    hipLaunchKernelGGL(k_refine_state, dim3(nrhs), dim3(kRThreads), 0, stream, c.part, nb, c.berr, c.lstres, c.active,
+                       c.steps, 0, 1, c.ctl);
+    PARSY_HIP(hipGetLastError());
+    return 0;
+}
 
 void refine_free(parsy_plan* pl) {
     RefineState* R = pl->refine;
@@ -438,19 +436,19 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
     const int n = pl->S.n;
     if (nrhs < 1 || nrhs > 65535 || ldx < n || ldb < n || (d_r && ldr < n))
         return set_last_error(std::string(who) + ": need 1 <= nrhs <= 65535 and leading dimensions >= n"), -1;
-    if (ensure_pattern(pl) != 0 || ensure_workspace(pl, nrhs) != 0) return -1;
+    if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, nrhs) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
     double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
-    if (gather_values(pl, d_values, stream) != 0) return -1;
+    if (refine_gather_values(pl, d_values, stream) != 0) return -1;
     if (n > 0) {
         hipLaunchKernelGGL(k_refine_permute_in, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, d_x, (int64_t)ldx, R.d_perm,
                            z, (double*)nullptr, n);
         hipLaunchKernelGGL(k_refine_permute_in, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, d_b, (int64_t)ldb, R.d_perm,
                            pb, (double*)nullptr, n);
     }
-    const int nb = residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
+    const int nb = refine_residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
     if (nb < 0) return -1;
     if (d_r && n > 0)
         hipLaunchKernelGGL(k_refine_permute_out, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, r, R.d_perm, d_r,
@@ -467,15 +465,15 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
 }
 
 int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L, const double* d_b, int ldb, double* d_x,
-                       int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, hipStream_t stream) {
-    const char* who = "parsy_solve_spd_device";
+                       int ldx, int nrhs, int max_steps, int32_t* steps, double* berr, double* ferr, hipStream_t stream) {
+    const char* who = ferr ? "parsy_solve_spd_bounds_device" : "parsy_solve_spd_device";
     if (check_plan(pl, who, kNeedsIdle) != 0) return -1;
     const int n = pl->S.n;
     if (nrhs < 1 || nrhs > 65535 || ldx < n || ldb < n || max_steps < 0)
         return set_last_error(std::string(who) + ": need 1 <= nrhs <= 65535, max_steps >= 0 and leading dimensions >= n"), -1;
     if (d_x == d_b && ldx != ldb) return set_last_error(std::string(who) + ": d_x == d_b needs ldx == ldb"), -1;
-    const bool residuals = max_steps > 0 || steps || berr;
-    if ((residuals && ensure_pattern(pl) != 0) || ensure_workspace(pl, nrhs) != 0) return -1;
+    const bool residuals = max_steps > 0 || steps || berr || ferr;
+    if ((residuals && refine_ensure_pattern(pl) != 0) || refine_ensure_workspace(pl, nrhs) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
     double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
@@ -484,13 +482,13 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
     if (n > 0)
         hipLaunchKernelGGL(k_refine_permute_in, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, d_b, (int64_t)ldb, R.d_perm,
                            pb, z, n);
-    if (solve_enqueue(pl, d_L, z, nrhs, c.ctl, stream) != 0) return -1;
+    if (refine_solve_enqueue(pl, d_L, z, nrhs, c.ctl, stream) != 0) return -1;
     if (residuals) {
-        if (gather_values(pl, d_values, stream) != 0) return -1;
+        if (refine_gather_values(pl, d_values, stream) != 0) return -1;
         hipLaunchKernelGGL(k_refine_init, dim3((nrhs + 255) / 256), dim3(256), 0, stream, c.lstres, c.active, c.steps, nrhs);
         for (;;) {
             PARSY_HIP(hipMemsetAsync(c.ctl, 0, sizeof(int), stream));
-            const int nb = residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
+            const int nb = refine_residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
             if (nb < 0) return -1;
             hipLaunchKernelGGL(k_refine_state, dim3(nrhs), dim3(kRThreads), 0, stream, c.part, nb, c.berr, c.lstres,
                                c.active, c.steps, max_steps, 0, c.ctl);
@@ -504,10 +502,12 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
                        -1;
             if (ctl[0] == 0) break;
             // the columns that go on: z += (L L')^-1 r (every column rides along in the solves; frozen ones are not updated)
-            if (solve_enqueue(pl, d_L, r, nrhs, c.ctl, stream) != 0) return -1;
+            if (refine_solve_enqueue(pl, d_L, r, nrhs, c.ctl, stream) != 0) return -1;
             hipLaunchKernelGGL(k_refine_update, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, z, r, c.active, n);
         }
     }
+    // (before X is written: a solve of the bounds that timed out leaves every output untouched)
+    if (ferr && cond_bounds_phase(pl, who, d_L, nrhs, ferr, stream) != 0) return -1;
     if (n > 0)
         hipLaunchKernelGGL(k_refine_permute_out, grid_nq(n, nrhs), dim3(kRThreads), 0, stream, z, R.d_perm, d_x,
                            (int64_t)ldx, n);
