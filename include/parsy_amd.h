@@ -455,6 +455,48 @@ int parsy_pattern_outer_host(parsy_plan* plan, const double* lambda, int ldl, co
 int parsy_inverse_pattern_host(parsy_plan* plan, const double* z, double alpha, double beta, int flags, double* g,
                                double* seconds);
 
+/* ---- The factor as an operator: products with L and L', Gaussian samples ------------------------------------------
+ * With the plan's ordering P (parsy_plan_set_perm: perm[new] = old, identity when unset) and G = P' L we have G G' = A, so
+ * x = mu + G z draws from N(mu, A), x = mu + G^-T z from N(mu, A^-1), G^-1 (x - mu) whitens and ||G^-1 r||^2 is the
+ * Mahalanobis form.  One entry point applies the four operators to the nrhs columns of X (column-major, leading
+ * dimension ldx >= n) in the caller's ordering:
+ *     PARSY_OP_G      Y = beta Y + alpha P' L X          PARSY_OP_GT      Y = beta Y + alpha L' P X
+ *     PARSY_OP_GINV   Y = beta Y + alpha L^-1 P X        PARSY_OP_GINVT   Y = beta Y + alpha P' L^-T X
+ * With beta == 0, Y is not read (it may hold NaN).  Only the first n rows of each column of Y are written; X is not
+ * changed; X and Y must be different arrays.  d_lValues may hold any values on the pattern of L; the strict upper
+ * triangle of a supernode's diagonal block is never read.
+ * The two products are kernels of their own with no floating-point atomics: a call repeated gives the same bits, and
+ * column q of a call with nrhs columns is bitwise what the call with that column alone gives, for any leading
+ * dimensions.  They pass over lValues once per block of block_columns right-hand sides and hold a workspace of
+ * workspace_bytes for one block, the transpose of the row lists (row -> its positions in lR) and their task lists on the
+ * device; all of it is made by the first device call and counted in the plan's device_bytes.
+ * The two inverse operators permute into an n x nrhs workspace, run parsy_solve_device / parsy_backsolve_device on it
+ * unchanged and write out; their status is the solves' (parsy_solve_status after the stream is synchronised).
+ * Refusals (parsy_last_error names each; nothing is written): a NULL argument, nrhs < 1, ldx < n or ldy < n, op outside
+ * 0 .. 3, X and Y the same array, a host-only plan.  One stream per plan, as for every call on a plan. */
+enum { PARSY_OP_G = 0, PARSY_OP_GT = 1, PARSY_OP_GINV = 2, PARSY_OP_GINVT = 3 };
+int parsy_factor_apply_device(parsy_plan* plan, const double* d_lValues, int op, const double* d_x, int ldx, int nrhs,
+                              double alpha, double beta, double* d_y, int ldy, void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  Synchronous; for the inverse operators a
+ * bad solve status fails the call and leaves y untouched. */
+int parsy_factor_apply_host(parsy_plan* plan, const double* lValues, int op, const double* x, int ldx, int nrhs,
+                            double alpha, double beta, double* y, int ldy, double* seconds);
+typedef struct parsy_apply_info {
+    int32_t rows;              /* n */
+    int32_t max_occurrences;   /* most panels a row appears in */
+    int64_t occurrences;       /* entries of the row lists (ssize) */
+    int32_t block_columns;     /* right-hand sides per pass over lValues */
+    int32_t last_op;           /* op of the last device call (-1: none yet) */
+    int32_t last_launches;     /* kernels it enqueued (besides the solve's own for the inverse operators) */
+    int32_t reserved;
+    int64_t workspace_bytes;   /* workspace of the products for one block of right-hand sides (known on the host) */
+    int64_t device_bytes;      /* index, task lists and workspaces held (0 before the first device call) */
+} parsy_apply_info;
+int parsy_factor_apply_get_info(parsy_plan* plan, parsy_apply_info* info);          /* host-only plans too */
+/* The transpose of the row lists: the positions k of lR with lR[k] == row are pos[ptr[row]] .. pos[ptr[row + 1] - 1],
+ * ascending; ptr holds n + 1 entries, pos ssize.  Host-only plans too. */
+int parsy_factor_apply_row_index(const parsy_plan* plan, int64_t* ptr, int64_t* pos);
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

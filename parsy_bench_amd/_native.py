@@ -92,7 +92,19 @@ EXPORTED_SYMBOLS = [
     "parsy_trace_inverse_device", "parsy_pattern_outer_host", "parsy_inverse_pattern_host",
     "parsy_cond_get_info", "parsy_error_bounds_device", "parsy_solve_spd_bounds_device", "parsy_solve_spd_bounds_host",
     "parsy_rcond_device", "parsy_rcond_host",
+    "parsy_factor_apply_device", "parsy_factor_apply_host", "parsy_factor_apply_get_info", "parsy_factor_apply_row_index",
 ]
+
+
+class ApplyInfo(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int32), ("max_occurrences", C.c_int32), ("occurrences", C.c_int64), ("block_columns", C.c_int32),
+        ("last_op", C.c_int32), ("last_launches", C.c_int32), ("reserved", C.c_int32), ("workspace_bytes", C.c_int64),
+        ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class CondInfo(C.Structure):
@@ -226,6 +238,10 @@ def _declare(lib):
     lib.parsy_trace_inverse_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int, vp, vp]
     lib.parsy_pattern_outer_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp]
     lib.parsy_inverse_pattern_host.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, vp, vp]
+    lib.parsy_factor_apply_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp]
+    lib.parsy_factor_apply_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp]
+    lib.parsy_factor_apply_get_info.argtypes = [vp, vp]
+    lib.parsy_factor_apply_row_index.argtypes = [vp, vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -445,6 +445,81 @@ class Plan:
             raise RuntimeError("parsy_trace_inverse_device failed: " + N.last_error())
         return out[:nb]
 
+    # the factor as an operator: G = P' L with G G' = A (include/parsy_amd.h) ------------------------------------------
+    OPS = {"G": 0, "GT": 1, "GINV": 2, "GINVT": 3}
+
+    @staticmethod
+    def _op(op) -> int:
+        return Plan.OPS[op] if isinstance(op, str) else int(op)
+
+    @property
+    def apply_info(self) -> dict:
+        """rows, occurrences (ssize), max_occurrences (most panels a row appears in), block_columns (right-hand sides per
+        pass over lValues), workspace_bytes (of the products, known on the host), device_bytes (0 before the first device
+        call), last_op (-1: none yet), last_launches."""
+        ai = N.ApplyInfo()
+        if N.lib().parsy_factor_apply_get_info(self._h, C.byref(ai)) != 0:
+            raise RuntimeError("parsy_factor_apply_get_info failed: " + N.last_error())
+        return ai.as_dict()
+
+    def apply_row_index(self):
+        """(ptr int64[n + 1], pos int64[ssize]): the positions k of the row lists with s[k] == row are
+        pos[ptr[row]:ptr[row + 1]], ascending."""
+        ptr = np.zeros(self.sym.n + 1, dtype=np.int64)
+        pos = np.zeros(int(self.sym.ssize), dtype=np.int64)
+        if N.lib().parsy_factor_apply_row_index(self._h, N.ptr(ptr), N.ptr(pos)) != 0:
+            raise RuntimeError("parsy_factor_apply_row_index failed: " + N.last_error())
+        return ptr, pos
+
+    def factor_apply_device(self, d_lValues: int, op, d_x: int, ldx: int, nrhs: int, d_y: int, ldy: int,
+                            alpha: float = 1.0, beta: float = 0.0, stream: int = 0) -> None:
+        """Y = beta Y + alpha op(X), op in "G" (P' L), "GT" (L' P), "GINV" (L^-1 P), "GINVT" (P' L^-T) or 0 .. 3, under the
+        plan's ordering (set_perm); X and Y column-major device arrays, not the same one."""
+        if N.lib().parsy_factor_apply_device(self._h, d_lValues or None, self._op(op), d_x or None, ldx, nrhs, alpha, beta,
+                                             d_y or None, ldy, stream) != 0:
+            raise RuntimeError("parsy_factor_apply_device failed: " + N.last_error())
+
+    def factor_apply(self, lValues, x, op, alpha: float = 1.0, y=None, beta: float = 0.0):
+        """Host arrays (n,) or (n, nrhs) in: (beta y + alpha op(x), device_seconds), shaped like x; y is not changed."""
+        x = np.asarray(x, dtype=np.float64)
+        one = x.ndim == 1
+        n = self.sym.n
+        X = np.asfortranarray(x.reshape(n, -1))
+        nrhs = X.shape[1]
+        if y is None:
+            if beta != 0.0:
+                raise ValueError("factor_apply: beta != 0 needs y")
+            Y = np.zeros((n, nrhs), order="F")
+        else:
+            Y = np.array(np.asarray(y, dtype=np.float64).reshape(n, -1), order="F", copy=True)
+            if Y.shape != X.shape:
+                raise ValueError(f"factor_apply: x is {X.shape}, y is {Y.shape}")
+        lv = _f64(lValues)
+        sec = C.c_double(0)
+        if N.lib().parsy_factor_apply_host(self._h, N.ptr(lv), self._op(op), X.ctypes.data_as(C.c_void_p), max(n, 1), nrhs,
+                                           alpha, beta, Y.ctypes.data_as(C.c_void_p), max(n, 1), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_factor_apply_host failed: " + N.last_error())
+        return (Y[:, 0].copy() if one else np.ascontiguousarray(Y)), sec.value
+
+    def sample(self, lValues, z, mean=None, kind: str = "precision"):
+        """x = mean + G^-T z, a draw from N(mean, A^-1) for standard normal z (kind="precision": A is a precision
+        matrix), or x = mean + G z from N(mean, A) (kind="covariance"); one call with alpha = beta = 1.  z and mean are
+        (n,) or (n, nrhs) in the caller's ordering; on first use the plan takes sym.Perm as its ordering, as
+        solve_refined does.  The library draws nothing itself: the same z gives the same x."""
+        if kind not in ("precision", "covariance"):
+            raise ValueError('sample: kind must be "precision" or "covariance"')
+        if not getattr(self, "_perm_set", False):
+            self.set_perm(self.sym.Perm)
+            self._perm_set = True
+        op = "GINVT" if kind == "precision" else "G"
+        if mean is None:
+            return self.factor_apply(lValues, z, op)[0]
+        m = np.asarray(mean, dtype=np.float64)
+        zz = np.asarray(z, dtype=np.float64)
+        if m.shape != zz.shape:
+            m = np.broadcast_to(m.reshape(self.sym.n, -1), zz.reshape(self.sym.n, -1).shape).reshape(zz.shape)
+        return self.factor_apply(lValues, zz, op, alpha=1.0, y=m, beta=1.0)[0]
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

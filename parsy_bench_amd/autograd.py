@@ -91,6 +91,41 @@ class SpdSolver:
         """log det A as a 0-dim tensor; differentiable in values."""
         return _LogDet.apply(values, self, self._factor(values))
 
+    def sample(self, values, n_samples: int = 1, mean=None, kind: str = "precision", z=None, generator=None):
+        """Draws from N(mean, A^-1) (kind="precision": x = mean + G^-T z) or N(mean, A) (kind="covariance":
+        x = mean + G z) with the cached factor of `values`, G G' = A; shaped (n,) for n_samples == 1 and (n, n_samples)
+        otherwise.  z (standard normal, shaped like the result) is drawn here with torch.randn(..., generator=generator)
+        on the device when it is not given: the library itself holds no random number generator, and the same z gives the
+        same bits.  NOT differentiable in `values` (differentiating through the factor is out of scope): a gradient flows
+        to `mean` only."""
+        n = self.sym.n
+        if kind not in ("precision", "covariance"):
+            raise ValueError('SpdSolver.sample: kind must be "precision" or "covariance"')
+        if n_samples < 1:
+            raise ValueError("SpdSolver.sample: n_samples must be >= 1")
+        shape = (n,) if n_samples == 1 else (n, n_samples)
+        if z is None:
+            z = torch.randn(shape, dtype=torch.float64, device=self.device, generator=generator)
+        elif z.dtype != torch.float64 or z.device != self.device or tuple(z.shape) != shape:
+            raise ValueError(f"SpdSolver.sample: z must be a float64 tensor of shape {shape} on {self.device}")
+        fact = self._factor(values)
+        Z = _as_columns(z, n)
+        X = torch.empty_like(Z)
+        self.plan.factor_apply_device(fact.L.data_ptr(), "GINVT" if kind == "precision" else "G", Z.data_ptr(), n, n_samples,
+                                      X.data_ptr(), n, stream=self._stream())
+        if kind == "precision":
+            torch.cuda.current_stream(self.device).synchronize()
+            if self.plan.solve_status() != 0:
+                raise RuntimeError("SpdSolver.sample: the backward solve failed: " + api.N.last_error())
+        x = X[0].clone() if n_samples == 1 else X.t().contiguous()
+        if mean is None:
+            return x
+        if mean.dtype != torch.float64 or mean.device != self.device or mean.shape[0] != n or mean.dim() not in (1, 2):
+            raise ValueError(f"SpdSolver.sample: mean must be a float64 tensor of shape ({n},) or ({n}, n_samples) on {self.device}")
+        if mean.dim() == 1 and x.dim() == 2:
+            mean = mean.unsqueeze(1)
+        return mean + x
+
 
 def _as_columns(t, n):
     return t.detach().reshape(n, -1).t().contiguous()

@@ -20,6 +20,7 @@
 #include "inspector.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
+#include "apply.hpp"
 
 using parsy::set_last_error;
 
@@ -717,6 +718,29 @@ int parsy_rcond_device(parsy_plan* pl, const double* d_values, const double* d_l
         return -1;
     }
     return parsy::plan_rcond(pl, d_values, d_lValues, anorm, rcond, (hipStream_t)stream);
+}
+
+int parsy_factor_apply_device(parsy_plan* pl, const double* d_lValues, int op, const double* d_x, int ldx, int nrhs,
+                              double alpha, double beta, double* d_y, int ldy, void* stream) {
+    return parsy::plan_factor_apply(pl, d_lValues, op, d_x, ldx, nrhs, alpha, beta, d_y, ldy, stream);
+}
+
+int parsy_factor_apply_get_info(parsy_plan* pl, parsy_apply_info* info) {
+    if (!pl || !info) {
+        set_last_error("parsy_factor_apply_get_info: null argument");
+        return -1;
+    }
+    if (parsy::apply_ensure_host(pl) != 0) return -1;
+    const parsy::ApplyState& A = *pl->apply;
+    info->rows = pl->S.n;
+    info->occurrences = (int64_t)pl->S.rows.size();
+    info->max_occurrences = A.I.max_occurrences;
+    info->block_columns = parsy::kApplyBlock;
+    info->workspace_bytes = A.ws_need * 8;
+    info->device_bytes = A.index_bytes + (A.ws_len + A.sol_len) * 8;
+    info->last_op = A.last_op;
+    info->last_launches = A.last_launches;
+    return 0;
 }
 
 void parsy_dropin_reset(void) {

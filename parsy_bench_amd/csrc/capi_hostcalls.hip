@@ -20,6 +20,7 @@
 #include "refine.hpp"
 #include "cond.hpp"
 #include "selinv.hpp"
+#include "apply.hpp"
 
 using parsy::set_last_error;
 
@@ -434,6 +435,41 @@ int parsy_inverse_pattern_host(parsy_plan* pl, const double* z, double alpha, do
         set_last_error(std::string(who) + ": download failed");
         return -1;
     }
+    return 0;
+}
+
+int parsy_factor_apply_host(parsy_plan* pl, const double* lValues, int op, const double* x, int ldx, int nrhs, double alpha,
+                            double beta, double* y, int ldy, double* seconds) {
+    const char* who = "parsy_factor_apply_host";
+    if (parsy::apply_check_args(pl, who, lValues, op, x, ldx, nrhs, y, ldy) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    const int n = S.n;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    // X and Y with leading dimension n on the device; Y goes up only when it is read
+    Scratch sc;
+    const int64_t len = (int64_t)n * nrhs;
+    const size_t row = (size_t)n * 8;
+    double* d_x = sc.upload(nullptr, len, false);
+    double* d_y = sc.upload(nullptr, len, false);
+    if (!d_x || !d_y || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (n > 0) {
+        PARSY_HIP(hipMemcpy2D(d_x, row, x, (size_t)ldx * 8, row, nrhs, hipMemcpyHostToDevice));
+        if (beta != 0.0) PARSY_HIP(hipMemcpy2D(d_y, row, y, (size_t)ldy * 8, row, nrhs, hipMemcpyHostToDevice));
+    }
+    if (parsy_factor_apply_device(pl, pl->h_L_dev, op, d_x, std::max(n, 1), nrhs, alpha, beta, d_y, std::max(n, 1), nullptr) != 0)
+        return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    // (y stays untouched when a solve's status is bad: it would not be the result)
+    if ((op == PARSY_OP_GINV || op == PARSY_OP_GINVT) && parsy_solve_status(pl) != 0) return -1;
+    if (n > 0) PARSY_HIP(hipMemcpy2D(y, (size_t)ldy * 8, d_y, row, row, nrhs, hipMemcpyDeviceToHost));
     return 0;
 }
 

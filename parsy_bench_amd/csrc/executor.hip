@@ -6,6 +6,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "apply.hpp"
 #include "cond.hpp"
 #include "errors.hpp"
 #include "grad.hpp"
@@ -259,6 +260,7 @@ void plan_free(parsy_plan* pl) {
     selinv_free(pl);
     grad_free(pl);
     cond_free(pl);
+    apply_free(pl);
     delete pl;
 }
 

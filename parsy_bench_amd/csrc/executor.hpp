@@ -16,6 +16,7 @@ struct RefineState;
 struct SelinvState;
 struct GradState;
 struct CondState;
+struct ApplyState;
 }
 
 struct parsy_plan {
@@ -96,6 +97,7 @@ struct parsy_plan {
     parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
     parsy::GradState* grad = nullptr;       // gradients with respect to A's values (grad.hpp): made by the first such call
     parsy::CondState* cond = nullptr;       // forward error bounds / condition estimate (cond.hpp): made by the first such call
+    parsy::ApplyState* apply = nullptr;     // the factor as an operator (apply.hpp): made by the first such call
 };
 
 namespace parsy {

@@ -1,0 +1,392 @@
+"""The factor as an operator on the device (parsy_factor_apply_device / _host, Plan.sample, SpdSolver.sample): the two
+products against a long double reference with a derived bound, their reproducibility and batch invariance, the operator
+identities on factored matrices, the sampler and the refusals."""
+import numpy as np
+import pytest
+
+from conftest import problem
+from test_gpu_parity import RESID_TOL, SOLVE_TOL
+from test_selinv_gpu import _case, _dev
+from test_selinv_host import edge
+
+pytestmark = pytest.mark.gpu
+
+_SENTINEL = -7.25e300
+_U = 2.0 ** -53
+_PAD = 37          # ld = n + 37
+_TAIL = 11         # Y is allocated 11 entries too long
+NRHS = [1, 3, 8, 16, 17, 64, 70]
+NMAX = 70
+PATTERNS = ["tiny2d", "random", "dense150", "tridiag300", "diag37"]
+_PLANS, _ENTRIES, _REFS = {}, {}, {}
+
+
+def _plan(api, name):
+    """(sym, plan on device 0, values on the pattern of L) per name; no factorization."""
+    if name not in _PLANS:
+        from parsy_bench_amd import inspector as I, matrices as M
+        if name == "random":
+            sym = I.analyze(M.random_spd(300, density=0.03, seed=5), None)
+        elif name in ("dense150", "tridiag300", "diag37"):
+            sym = edge(name)[1]
+        else:
+            sym = problem(name)[2]
+        lv = np.random.default_rng(len(name)).standard_normal(int(sym.xsize))
+        _PLANS[name] = (sym, api.Plan(sym, 0), lv)
+    return _PLANS[name]
+
+
+def _entries(name, sym):
+    """(row, col, off) of every stored entry of L -- row i of a panel holds the columns c <= min(i, w - 1) -- and the
+    offsets of the strict upper triangles of the diagonal blocks, which no product may read."""
+    if name not in _ENTRIES:
+        rows, cols, offs, upper = [], [], [], []
+        s = np.asarray(sym.s)
+        for k in range(sym.nsuper):
+            c0, c1 = int(sym.super[k]), int(sym.super[k + 1])
+            w, pi, px = c1 - c0, int(sym.i_ptr[c0]), int(sym.p[c0])
+            r = int(sym.i_ptr[c1]) - pi
+            ii, cc = np.tril_indices(r, 0, w)
+            rows.append(s[pi + ii].astype(np.int32))
+            cols.append((c0 + cc).astype(np.int32))
+            offs.append(px + cc.astype(np.int64) * r + ii)
+            iu, cu = np.triu_indices(w, 1)
+            upper.append(px + cu.astype(np.int64) * r + iu)
+        _ENTRIES[name] = (np.concatenate(rows), np.concatenate(cols), np.concatenate(offs), np.concatenate(upper))
+    return _ENTRIES[name]
+
+
+def _reference(name, sym, lv, nmax=NMAX):
+    """Once per pattern: W (n x nmax, the operand in the factor's ordering), and for both products the reference in long
+    double (np.add.at over the stored entries), M = sum |l x| and K = the stored entries per output."""
+    if name not in _REFS:
+        row, col, off, _ = _entries(name, sym)
+        n = sym.n
+        W = np.random.default_rng(1000 + n).standard_normal((n, nmax))
+        l = lv[off]
+        ll = l.astype(np.longdouble)
+        out = {"W": W}
+        for op, dst, src in (("G", row, col), ("GT", col, row)):
+            ref = np.zeros((n, nmax), dtype=np.longdouble)
+            M = np.zeros((n, nmax))
+            for q in range(nmax):
+                x = W[src, q]
+                np.add.at(ref[:, q], dst, ll * x)
+                M[:, q] = np.bincount(dst, weights=np.abs(l * x), minlength=n)
+            out[op] = (ref, M, np.bincount(dst, minlength=n).astype(np.float64))
+        _REFS[name] = out
+    return _REFS[name]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+def _is_sentinel(a):
+    return (_bits(a) == np.float64(_SENTINEL).view(np.int64)).all()
+
+
+def _padded(V, ld):
+    """The n x nrhs array V column-major with leading dimension ld, the padding rows holding the sentinel (flat)."""
+    n, nrhs = V.shape
+    flat = np.full(ld * nrhs, _SENTINEL)
+    flat.reshape(nrhs, ld)[:, :n] = V.T
+    return flat
+
+
+def _rows(flat, n, nrhs, ld):
+    return flat[:ld * nrhs].reshape(nrhs, ld)[:, :n].T
+
+
+def _apply(plan, dL, op, dx, ldx, nrhs, dy, ldy, alpha=1.0, beta=0.0):
+    import torch
+    plan.factor_apply_device(dL.data_ptr(), op, dx.data_ptr(), ldx, nrhs, dy.data_ptr(), ldy, alpha=alpha, beta=beta)
+    torch.cuda.synchronize()
+    return dy.cpu().numpy()
+
+
+def _operand(op, W, P):
+    """The caller's X whose product is op(W in the factor's ordering): G takes W itself, GT takes X with P X = W."""
+    if op == "G" or P is None:
+        return W
+    X = np.empty_like(W)
+    X[P] = W
+    return X
+
+
+def _in_factor_order(op, Y, P):
+    """The product in the factor's ordering: G leaves P' (L X), GT leaves L' (P X)."""
+    return Y[P] if op == "G" and P is not None else Y
+
+
+def _check_products(api, name, ordering, nrhs):
+    """Both products of one shape through every check of item 1.  The bound: per output element an fma chain or tree over
+    its K stored entries makes at most K roundings of partial sums that never exceed M = sum |l x|, and rounding the
+    long double reference to compare adds one more: |got - ref| <= (K + 2) 2^-53 M.  (M and K are taken in double: M's own
+    rounding is of relative size K 2^-53 and changes the bound in the second order only.)"""
+    import torch
+    sym, plan, lv = _plan(api, name)
+    R = _reference(name, sym, lv)
+    n, ld = sym.n, sym.n + _PAD
+    P = None if ordering == "identity" else np.asarray(sym.Perm)
+    plan.set_perm(P)
+    try:
+        dL = _dev(lv)
+        rng = np.random.default_rng(nrhs)
+        for op in ("G", "GT"):
+            ref, M, K = (a[:, :nrhs] if a.ndim == 2 else a for a in R[op])
+            xf = _padded(_operand(op, R["W"][:, :nrhs], P), ld)
+            dx = _dev(xf)
+            y = torch.full((ld * nrhs + _TAIL,), _SENTINEL, dtype=torch.float64, device="cuda")
+            got = _apply(plan, dL, op, dx, ld, nrhs, y, ld)
+            Y = _in_factor_order(op, _rows(got, n, nrhs, ld), P)
+            err = np.abs(Y.astype(np.longdouble) - ref).astype(np.float64)
+            bound = (K[:, None] + 2) * _U * M
+            worst = float((err / np.maximum(bound, 1e-300)).max())
+            print(f"{name} {ordering} {op} nrhs={nrhs}: max err / bound = {worst:.3f}")
+            assert (err <= bound).all(), (op, worst)
+            # the inputs and everything beyond row n of a column keep their bits
+            assert np.array_equal(_bits(dx.cpu().numpy()), _bits(xf))
+            assert _is_sentinel(got.reshape(-1)[ld * nrhs:]) and _is_sentinel(got[:ld * nrhs].reshape(nrhs, ld)[:, n:])
+            info = plan.apply_info
+            assert info["last_op"] == api.Plan.OPS[op] and info["last_launches"] >= 2 * -(-nrhs // info["block_columns"])
+            assert info["device_bytes"] > 0
+            # alpha = -1, beta = 0 on a Y full of NaN: bitwise the negation
+            y2 = torch.full((ld * nrhs + _TAIL,), float("nan"), dtype=torch.float64, device="cuda")
+            neg = _apply(plan, dL, op, dx, ld, nrhs, y2, ld, alpha=-1.0, beta=0.0)
+            assert np.array_equal(_bits(_rows(neg, n, nrhs, ld)), _bits(-_rows(got, n, nrhs, ld)))
+            # alpha = 0.5, beta = 2: the bound above and 4 2^-53 (|2 y0| + 0.5 M) for the roundings of the combination
+            y0 = rng.standard_normal((n, nrhs))
+            y3 = _dev(np.concatenate([_padded(y0, ld), np.full(_TAIL, _SENTINEL)]))
+            ab = _apply(plan, dL, op, dx, ld, nrhs, y3, ld, alpha=0.5, beta=2.0)
+            want = 2.0 * _in_factor_order(op, y0, P).astype(np.longdouble) + 0.5 * ref
+            err = np.abs(_in_factor_order(op, _rows(ab, n, nrhs, ld), P).astype(np.longdouble) - want).astype(np.float64)
+            bound2 = bound + 4 * _U * (np.abs(2.0 * _in_factor_order(op, y0, P)) + 0.5 * M)
+            assert (err <= bound2).all(), (op, "alpha, beta", float((err / np.maximum(bound2, 1e-300)).max()))
+            assert _is_sentinel(ab[ld * nrhs:]) and _is_sentinel(ab[:ld * nrhs].reshape(nrhs, ld)[:, n:])
+    finally:
+        plan.set_perm(None)
+
+
+@pytest.mark.parametrize("nrhs", NRHS)
+@pytest.mark.parametrize("ordering", ["identity", "perm"])
+@pytest.mark.parametrize("name", PATTERNS)
+def test_products_against_numpy(api, name, ordering, nrhs):
+    _check_products(api, name, ordering, nrhs)
+
+
+@pytest.mark.parametrize("nrhs", [1, 17, 70])
+@pytest.mark.parametrize("ordering", ["identity", "perm"])
+def test_products_against_numpy_tall_panels(api, ordering, nrhs):
+    """lap30: panels thousands of rows tall, up to 20 occurrences per row, up to 3221 stored entries per row."""
+    _check_products(api, "lap30", ordering, nrhs)
+
+
+def test_products_against_numpy_nd24k(api):
+    """The largest pattern of the suite, 1 and 8 right-hand sides (the reference is made for 8 columns)."""
+    import torch
+    name = "nd24k"
+    sym, plan, lv = _plan(api, name)
+    row, col, off, _ = _entries(name, sym)
+    n, ld = sym.n, sym.n + _PAD
+    W = np.random.default_rng(24).standard_normal((n, 8))
+    dL = _dev(lv)
+    l = lv[off]
+    ll = l.astype(np.longdouble)
+    for op, dst, src in (("G", row, col), ("GT", col, row)):
+        K = np.bincount(dst, minlength=n).astype(np.float64)
+        ref = np.zeros((n, 8), dtype=np.longdouble)
+        M = np.zeros((n, 8))
+        for q in range(8):
+            np.add.at(ref[:, q], dst, ll * W[src, q])
+            M[:, q] = np.bincount(dst, weights=np.abs(l * W[src, q]), minlength=n)
+        for nrhs in (1, 8):
+            dx = _dev(_padded(W[:, :nrhs], ld))
+            y = torch.full((ld * nrhs + _TAIL,), _SENTINEL, dtype=torch.float64, device="cuda")
+            got = _apply(plan, dL, op, dx, ld, nrhs, y, ld)
+            err = np.abs(_rows(got, n, nrhs, ld).astype(np.longdouble) - ref[:, :nrhs]).astype(np.float64)
+            bound = (K[:, None] + 2) * _U * M[:, :nrhs]
+            print(f"{name} {op} nrhs={nrhs}: max err / bound = {float((err / np.maximum(bound, 1e-300)).max()):.3f}")
+            assert (err <= bound).all(), (op, nrhs)
+            assert _is_sentinel(got[ld * nrhs:]) and _is_sentinel(got[:ld * nrhs].reshape(nrhs, ld)[:, n:])
+    del _PLANS[name], _ENTRIES[name]
+    plan.close()
+
+
+@pytest.mark.parametrize("name", ["tiny2d", "random", "dense150", "tridiag300", "diag37", "lap30"])
+def test_reproducible_batch_invariant_and_blind_to_the_upper_triangles(api, name):
+    """Requirements (a) to (c) under sym.Perm: the same call twice, column q of the 70-column call against that column
+    alone with another leading dimension, and the factor with NaN in the strict upper triangle of every diagonal block."""
+    import torch
+    sym, plan, lv = _plan(api, name)
+    n, ld, ld1 = sym.n, sym.n + _PAD, sym.n + 5
+    upper = _entries(name, sym)[3]
+    lv_nan = lv.copy()
+    lv_nan[upper] = np.nan
+    W = np.random.default_rng(7).standard_normal((n, NMAX))
+    xf = _padded(W, ld)
+    plan.set_perm(np.asarray(sym.Perm))
+    try:
+        dL, dLn, dx = _dev(lv), _dev(lv_nan), _dev(xf)
+        for op in ("G", "GT"):
+            def run(L):
+                y = torch.full((ld * NMAX + _TAIL,), _SENTINEL, dtype=torch.float64, device="cuda")
+                return _apply(plan, L, op, dx, ld, NMAX, y, ld)
+            a, b = run(dL), run(dL)
+            assert np.array_equal(_bits(a), _bits(b)), op
+            assert np.array_equal(_bits(dx.cpu().numpy()), _bits(xf))
+            assert _is_sentinel(a[ld * NMAX:]) and _is_sentinel(a[:ld * NMAX].reshape(NMAX, ld)[:, n:])
+            if upper.size:
+                assert np.array_equal(_bits(run(dLn)), _bits(a)), (op, "the strict upper triangle was read")
+            full = _rows(a, n, NMAX, ld)
+            for q in (0, 7, 8, 33, 69):
+                d1 = _dev(_padded(W[:, q:q + 1], ld1))
+                y1 = torch.full((ld1 + _TAIL,), _SENTINEL, dtype=torch.float64, device="cuda")
+                one = _apply(plan, dL, op, d1, ld1, 1, y1, ld1)
+                assert np.array_equal(_bits(one[:n]), _bits(full[:, q])), (op, q)
+                assert _is_sentinel(one[n:])
+    finally:
+        plan.set_perm(None)
+
+
+@pytest.mark.parametrize("name", ["tiny2d", "small3d", "random"])
+def test_operator_identities(api, name):
+    """On a factored matrix under sym.Perm: G G' = A in the caller's ordering, the inverse operators undo the products,
+    and G^-T G^-1 solves A x = b.  Tolerances: tests/test_gpu_parity.py."""
+    import torch
+    A, sym, plan, lv = _case(api, name)
+    n = sym.n
+    Ad = A.to_dense()
+    plan.set_perm(np.asarray(sym.Perm))
+    try:
+        dL = _dev(lv)
+
+        def op(which, V):
+            V = np.asfortranarray(V)
+            k = V.shape[1]
+            dx = _dev(V.T.copy().reshape(-1))
+            y = torch.full((n * k,), _SENTINEL, dtype=torch.float64, device="cuda")
+            out = _apply(plan, dL, which, dx, n, k, y, n).reshape(k, n).T
+            if which in ("GINV", "GINVT"):
+                assert plan.solve_status() == 0
+            return out
+
+        GGt = op("G", op("GT", np.eye(n)))
+        assert np.abs(GGt - Ad).max() <= RESID_TOL * np.abs(Ad).max()
+        X = np.random.default_rng(3).standard_normal((n, 5))
+        scale = SOLVE_TOL * max(1.0, np.abs(X).max())
+        assert np.abs(op("GINV", op("G", X)) - X).max() <= scale
+        assert np.abs(op("GINVT", op("GT", X)) - X).max() <= scale
+        B = np.random.default_rng(4).standard_normal((n, 3))
+        sol = op("GINVT", op("GINV", B))
+        want, _ = plan.solve_spd(lv, B)
+        assert np.abs(sol - want).max() <= SOLVE_TOL * max(1.0, np.abs(want).max())
+    finally:
+        plan.set_perm(None)
+
+
+@pytest.mark.parametrize("kind", ["precision", "covariance"])
+def test_plan_sample(api, kind):
+    """Plan.sample = mean + factor_apply in one call.  kind="covariance" is the product alone and is asserted bit for bit,
+    the repeat included.  kind="precision" runs the existing backward solve, whose kernels add with float atomics and are
+    not bitwise repeatable, so there two calls are compared within the solves' tolerance (tests/test_gpu_parity.py)."""
+    _, sym, _, lv = _case(api, "small3d")
+    plan = api.Plan(sym, 0)
+    n = sym.n
+    rng = np.random.default_rng(11)
+    op = "GINVT" if kind == "precision" else "G"
+    for shape in ((n,), (n, 9)):
+        z, mean = rng.standard_normal(shape), rng.standard_normal(shape)
+        x = plan.sample(lv, z, mean=mean, kind=kind)
+        assert x.shape == shape
+        g, _ = plan.factor_apply(lv, z, op)          # (sample() has made sym.Perm the plan's ordering)
+        if kind == "covariance":
+            assert np.array_equal(_bits(x), _bits(mean + g))      # (beta = alpha = 1: one rounding of mean + g)
+            assert np.array_equal(_bits(plan.sample(lv, z, mean=mean, kind=kind)), _bits(x))
+            assert np.array_equal(_bits(plan.sample(lv, z, kind=kind)), _bits(g))
+        else:
+            tol = SOLVE_TOL * max(1.0, np.abs(g).max())
+            assert np.abs(x - (mean + g)).max() <= tol
+            assert np.abs(plan.sample(lv, z, mean=mean, kind=kind) - x).max() <= tol
+            assert np.abs(plan.sample(lv, z, kind=kind) - g).max() <= tol
+    with pytest.raises(ValueError):
+        plan.sample(lv, np.ones(n), kind="correlation")
+    plan.close()
+
+
+def test_spd_solver_sample():
+    """The same seeded generator twice gives equal tensors: bit for bit for kind="covariance"; kind="precision" goes
+    through the backward solve (float atomics), so there the two draws agree within the solves' tolerance."""
+    import torch
+    from parsy_bench_amd import api, autograd, matrices as M
+    if api.device_count() < 1:
+        pytest.fail("no HIP device visible: the -m gpu tier must run on the GPU box")
+    A = M.random_spd(300, density=0.03, seed=5)
+    solver = autograd.SpdSolver(A)
+    n = A.n
+    values = torch.from_numpy(A.Ax.copy()).to(solver.device).requires_grad_(True)
+    for kind in ("precision", "covariance"):
+        gen = torch.Generator(device=solver.device)
+        gen.manual_seed(5)
+        a = solver.sample(values, n_samples=4, kind=kind, generator=gen)
+        gen.manual_seed(5)
+        b = solver.sample(values, n_samples=4, kind=kind, generator=gen)
+        assert a.shape == (n, 4) and b.shape == (n, 4)
+        if kind == "covariance":
+            assert torch.equal(a, b)
+        else:
+            assert (a - b).abs().max().item() <= SOLVE_TOL * max(1.0, a.abs().max().item())
+        assert solver.sample(values, kind=kind, generator=gen).shape == (n,)
+    assert solver.factor_count == 1
+    # a given z: G G' = A, so G' (G^-T z) = z and G^-1 (G z) = z; here through A (G^-T z) = G z
+    z = torch.randn(n, 3, dtype=torch.float64, device=solver.device)
+    xp, xc = solver.sample(values, 3, kind="precision", z=z), solver.sample(values, 3, kind="covariance", z=z)
+    Ad = torch.from_numpy(A.to_dense()).to(solver.device)
+    scale = max(1.0, xc.abs().max().item()) * Ad.abs().sum(dim=1).max().item()
+    assert (Ad @ xp - xc).abs().max().item() <= SOLVE_TOL * scale
+    # not differentiable in values; the gradient reaches mean with the identity
+    mean = torch.zeros(n, 3, dtype=torch.float64, device=solver.device, requires_grad=True)
+    x = solver.sample(values, 3, mean=mean, kind="precision", z=z)
+    w = torch.randn(n, 3, dtype=torch.float64, device=solver.device)
+    (x * w).sum().backward()
+    assert torch.equal(mean.grad, w)
+    assert values.grad is None
+
+
+def test_refusals(api):
+    """Each refusal by its message; Y still all sentinel; the plan still computes."""
+    import torch
+    from parsy_bench_amd import _native as N
+    sym, plan, lv = _plan(api, "tiny2d")
+    n, nrhs = sym.n, 2
+    dL = _dev(lv)
+    dx = _dev(np.ones(n * nrhs))
+    y = torch.full((n * nrhs + _TAIL,), _SENTINEL, dtype=torch.float64, device="cuda")
+    L, X, Y = dL.data_ptr(), dx.data_ptr(), y.data_ptr()
+    before = plan.apply_info["device_bytes"]
+    cases = [
+        ((0, "G", X, n, nrhs, Y, n), "null argument"),
+        ((L, "G", 0, n, nrhs, Y, n), "null argument"),
+        ((L, "G", X, n, nrhs, 0, n), "null argument"),
+        ((L, "GT", X, n, 0, Y, n), "need nrhs >= 1"),
+        ((L, "GINV", X, n - 1, nrhs, Y, n), "need leading dimensions ldx >= n and ldy >= n"),
+        ((L, "GINVT", X, n, nrhs, Y, n - 1), "need leading dimensions ldx >= n and ldy >= n"),
+        ((L, 4, X, n, nrhs, Y, n), r"op must be one of PARSY_OP_G \.\. PARSY_OP_GINVT"),
+        ((L, -1, X, n, nrhs, Y, n), r"op must be one of PARSY_OP_G \.\. PARSY_OP_GINVT"),
+        ((L, "G", Y, n, nrhs, Y, n), r"x and y are the same array \(in place is not supported\)"),
+    ]
+    for args, message in cases:
+        with pytest.raises(RuntimeError, match="parsy_factor_apply_device: " + message):
+            plan.factor_apply_device(*args)
+        torch.cuda.synchronize()
+        assert _is_sentinel(y.cpu().numpy()), message
+    assert plan.apply_info["device_bytes"] == before
+    hx, hy = np.ones(n), np.full(n, _SENTINEL)
+    assert N.lib().parsy_factor_apply_host(plan._h, N.ptr(lv), 0, N.ptr(hx), n, 0, 1.0, 0.0, N.ptr(hy), n, None) != 0
+    assert N.last_error() == "parsy_factor_apply_host: need nrhs >= 1" and _is_sentinel(hy)
+    # the plan still computes
+    out = _apply(plan, dL, "G", dx, n, nrhs, y, n)
+    assert not _is_sentinel(out[:n * nrhs]) and _is_sentinel(out[n * nrhs:])
+    row, col, off, _ = _entries("tiny2d", sym)
+    want = np.bincount(row, weights=lv[off], minlength=n)
+    assert np.abs(out[:n] - want).max() <= 64 * _U * np.bincount(row, weights=np.abs(lv[off]), minlength=n).max()
