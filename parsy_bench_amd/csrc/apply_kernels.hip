@@ -9,7 +9,7 @@
 //   k_apply_lt_panels<NB>   partial[(segment, column), q] = sum over the segment's rows i >= c of L[i, c] xt[rows[i], q]:
 //                           a wave per task, lane l the rows i = l (mod 64) in ascending order, then a butterfly
 //   k_apply_lt_cols<NB>     Y[k, q] = beta Y + alpha (the column's partials, ascending): a lane per column
-//   k_apply_copy_in / _out  the permutations around the solves of the inverse operators
+//   k_perm_gather / _scatter  (executor.hip) the orderings around the solves of the inverse operators
 //
 // NB (1 .. kApplyBlock) is the number of right-hand sides of the block; it changes how many sums a lane carries, never
 // the order of one: column q of a call is bitwise what the call with that column alone gives.
@@ -20,12 +20,12 @@
 #include <vector>
 
 #include "../../include/parsy_amd.h"
+#include "device_util.hpp"
 #include "errors.hpp"
 #include "hip_check.hpp"
 #include "executor.hpp"
 #include "plan_util.hpp"
 #include "apply.hpp"
-#include "refine.hpp"
 
 namespace parsy {
 
@@ -33,11 +33,6 @@ namespace {
 
 constexpr int kAThreads = 256;
 constexpr int kAWaves = kAThreads / 64;   // tasks of a workgroup of the panel kernels: a wave each
-
-// beta == 0: y is not read (it may hold NaN)
-__device__ __forceinline__ void store_y(double* __restrict__ y, double alpha, double beta, double s) {
-    *y = beta == 0.0 ? alpha * s : fma(beta, *y, alpha * s);
-}
 
 template <int NB>
 __global__ __launch_bounds__(kAThreads) void k_apply_l_panels(const ApplyTaskL* __restrict__ tasks, int64_t ntasks,
@@ -189,25 +184,6 @@ __global__ __launch_bounds__(kAThreads) void k_apply_lt_cols(const ApplyCol* __r
     for (int q = 0; q < NB; ++q) store_y(Y + k + q * ldy, alpha, beta, s[q]);
 }
 
-// ws[k, q] = X[perm[k], q] (ws leading dimension n; perm null: identity)
-__global__ __launch_bounds__(kAThreads) void k_apply_copy_in(const int* __restrict__ perm, const double* __restrict__ X,
-                                                             int64_t ldx, int n, int nrhs, double* __restrict__ ws) {
-    const int k = blockIdx.x * kAThreads + threadIdx.x;
-    if (k >= n) return;
-    const int64_t src = perm ? perm[k] : k;
-    for (int q = blockIdx.y; q < nrhs; q += gridDim.y) ws[k + (int64_t)q * n] = X[src + q * ldx];
-}
-
-// Y[perm[k], q] = beta Y[perm[k], q] + alpha ws[k, q]
-__global__ __launch_bounds__(kAThreads) void k_apply_copy_out(const int* __restrict__ perm, const double* __restrict__ ws,
-                                                              int n, int nrhs, double alpha, double beta,
-                                                              double* __restrict__ Y, int64_t ldy) {
-    const int k = blockIdx.x * kAThreads + threadIdx.x;
-    if (k >= n) return;
-    const int64_t dst = perm ? perm[k] : k;
-    for (int q = blockIdx.y; q < nrhs; q += gridDim.y) store_y(Y + dst + q * ldy, alpha, beta, ws[k + (int64_t)q * n]);
-}
-
 int ensure_device(parsy_plan* pl) {
     if (apply_ensure_host(pl) != 0) return -1;
     ApplyState& A = *pl->apply;
@@ -293,13 +269,11 @@ int plan_factor_apply(parsy_plan* pl, const double* d_L, int op, const double* d
     if (op == PARSY_OP_GINV || op == PARSY_OP_GINVT) {
         if (grow_counted(pl, A.sol, A.sol_len, (int64_t)n * nrhs) != 0) return -1;
         const bool back = op == PARSY_OP_GINVT;
-        const dim3 grid(nblocks, (unsigned)std::min(nrhs, 65535));
-        hipLaunchKernelGGL(k_apply_copy_in, grid, threads, 0, stream, back ? nullptr : perm, d_x, (int64_t)ldx, n, nrhs, A.sol);
+        enqueue_perm_gather(back ? nullptr : perm, d_x, ldx, A.sol, nullptr, n, nrhs, stream);
         PARSY_HIP(hipGetLastError());
         if ((back ? plan_backsolve(pl, d_L, A.sol, nrhs, n, stream) : plan_solve(pl, d_L, A.sol, nrhs, n, stream)) != 0)
             return -1;
-        hipLaunchKernelGGL(k_apply_copy_out, grid, threads, 0, stream, back ? perm : nullptr, A.sol, n, nrhs, alpha, beta, d_y,
-                           (int64_t)ldy);
+        enqueue_perm_scatter(back ? perm : nullptr, A.sol, alpha, beta, d_y, ldy, n, nrhs, stream);
         PARSY_HIP(hipGetLastError());
         A.last_launches = 2;   // (besides the solve's own)
         return 0;

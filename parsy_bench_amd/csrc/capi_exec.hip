@@ -18,6 +18,7 @@
 #include "dist.hpp"
 #include "executor.hpp"
 #include "inspector.hpp"
+#include "plan_util.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
 #include "apply.hpp"

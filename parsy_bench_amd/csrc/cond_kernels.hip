@@ -7,13 +7,13 @@
 // the columns at once; the state of a column (CondCol) lives on the device, and the host reads one word per application:
 // the number of columns that still go on.  A column takes at most 11 applications (1 + 1 + 4 x 2 + 1), so a call
 // enqueues at most 11 solve pairs whatever the number of right-hand sides; a column that has finished keeps a zero
-// operand and a frozen state.  As in refine_kernels.hip every sum runs in a fixed order (a fixed lane split and a fixed
-// butterfly), nothing is accumulated with float atomics, and maxima are reduced as the bit patterns of non-negative
-// doubles (a NaN survives): given the same solve results the estimate is bitwise the same.
+// operand and a frozen state.  The weights are the row sweep of sym_sweep.hpp with the epilogue WeightOut, the
+// residual's own sums; every other sum here also runs in a fixed order, nothing is accumulated with float atomics, and
+// maxima are reduced as the bit patterns of non-negative doubles (a NaN survives): given the same solve results the
+// estimate is bitwise the same.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <string>
 
@@ -23,6 +23,7 @@
 #include "plan_util.hpp"
 #include "kernels.hpp"
 #include "refine.hpp"
+#include "sym_sweep.hpp"
 #include "cond.hpp"
 
 namespace parsy {
@@ -34,99 +35,20 @@ constexpr int kCondMaxApplications = 11;
 
 __device__ __forceinline__ u64 abs_bits(double v) { return (u64)__double_as_longlong(fabs(v)); }
 
-__device__ __forceinline__ double weight_of(double b, double rr, double den, double nzeps, double safe1, double safe2) {
-    // dporfs: |r| + nz eps (|b| + sum |a||z|), + safe1 unless the sum is > safe2
-    const double s = fabs(b) + den;
-    const double w = fabs(rr) + nzeps * s;
-    return s > safe2 ? w : w + safe1;
-}
-
-// The weights of 1-4 columns, k_sym_residual's lane split and sums: G lanes per row, a butterfly; w column-major like z,
-// pb.  zpart[c * gridDim.x + blockIdx.x]: the workgroup's max of |z[:, c]|.
-template <int G, int NR>
-__global__ __launch_bounds__(kCThreads) void k_sym_weight(const int64_t* __restrict__ rp, const int* __restrict__ ci,
-                                                          const double* __restrict__ vf, const double* __restrict__ z,
-                                                          const double* __restrict__ pb, double* __restrict__ w, int n,
-                                                          double nzeps, double safe1, double safe2,
-                                                          u64* __restrict__ zpart) {
-    __shared__ u64 sm[4];
-    const int tid = threadIdx.x, g = tid % G;
-    constexpr int kRows = kCThreads / G;
-    u64 mx[NR];
-#pragma unroll
-    for (int c = 0; c < NR; ++c) mx[c] = 0;
-    for (int64_t row = (int64_t)blockIdx.x * kRows + tid / G; row < n; row += (int64_t)gridDim.x * kRows) {
-        double acc[NR], den[NR];
-#pragma unroll
-        for (int c = 0; c < NR; ++c) acc[c] = den[c] = 0.0;
-        const int64_t e1 = rp[row + 1];
-        for (int64_t e = rp[row] + g; e < e1; e += G) {
-            const double a = vf[e];
-            const int64_t j = ci[e];
-#pragma unroll
-            for (int c = 0; c < NR; ++c) {
-                const double zj = z[j + (int64_t)c * n];
-                acc[c] = fma(a, zj, acc[c]);
-                den[c] = fma(fabs(a), fabs(zj), den[c]);
-            }
-        }
-#pragma unroll
-        for (int o = G / 2; o; o >>= 1)
-#pragma unroll
-            for (int c = 0; c < NR; ++c) {
-                acc[c] += __shfl_xor(acc[c], o);
-                den[c] += __shfl_xor(den[c], o);
-            }
-#pragma unroll
-        for (int c = 0; c < NR; ++c) {
-            const double b = pb[row + (int64_t)c * n];
-            if (g == 0) w[row + (int64_t)c * n] = weight_of(b, b - acc[c], den[c], nzeps, safe1, safe2);
-            mx[c] = max(mx[c], abs_bits(z[row + (int64_t)c * n]));
-        }
+// dporfs's weight of a row, and |z| of the row for the column's max (z is read here, behind the sums)
+struct WeightOut : SweepScale {
+    __device__ __forceinline__ u64 operator()(double* w, bool first, double b, double acc, double den,
+                                              const double* zp) const {
+        // |r| + nz eps (|b| + sum |a||z|), + safe1 unless the sum is > safe2
+        const double s = fabs(b) + den;
+        const double v = fabs(b - acc) + nzeps * s;
+        if (first) *w = s > safe2 ? v : v + safe1;
+        return abs_bits(*zp);
     }
-#pragma unroll
-    for (int c = 0; c < NR; ++c) {
-        const u64 v = block_max(mx[c], sm);
-        if (tid == 0) zpart[(int64_t)c * gridDim.x + blockIdx.x] = v;
-    }
-}
+};
 
-// Many columns: k_sym_residual_mrhs's layout, L lanes per row with one column each on z staged row-major (zt, row stride
-// ldq); pb and w stay column-major.
-template <int L>
-__global__ __launch_bounds__(kCThreads) void k_sym_weight_mrhs(const int64_t* __restrict__ rp, const int* __restrict__ ci,
-                                                               const double* __restrict__ vf, const double* __restrict__ zt,
-                                                               int ldq, const double* __restrict__ pb,
-                                                               double* __restrict__ w, int n, int nrhs, double nzeps,
-                                                               double safe1, double safe2, u64* __restrict__ zpart) {
-    __shared__ u64 sm[4][64];
-    const int tid = threadIdx.x, lq = tid % L;
-    const int q = (int)blockIdx.y * L + lq;
-    const bool on = q < nrhs;
-    constexpr int kRows = kCThreads / L;
-    u64 mx = 0;
-    for (int64_t row = (int64_t)blockIdx.x * kRows + tid / L; row < n; row += (int64_t)gridDim.x * kRows) {
-        if (!on) continue;
-        double acc = 0.0, den = 0.0;
-        const int64_t e1 = rp[row + 1];
-        for (int64_t e = rp[row]; e < e1; ++e) {
-            const double a = vf[e];
-            const double zj = zt[(int64_t)ci[e] * ldq + q];
-            acc = fma(a, zj, acc);
-            den = fma(fabs(a), fabs(zj), den);
-        }
-        const double b = pb[row + (int64_t)q * n];
-        w[row + (int64_t)q * n] = weight_of(b, b - acc, den, nzeps, safe1, safe2);
-        mx = max(mx, abs_bits(zt[row * ldq + q]));
-    }
-    for (int o = L; o < 64; o <<= 1) mx = max(mx, shfl_xor_u64(mx, o));   // the lanes of one column within the wave
-    if ((tid & 63) < L) sm[tid >> 6][tid & 63] = mx;
-    __syncthreads();
-    if (tid < L && on)
-        zpart[(int64_t)q * gridDim.x + blockIdx.x] = max(max(sm[0][tid], sm[1][tid]), max(sm[2][tid], sm[3][tid]));
-}
-
-// ||A||_1 of the symmetric A: the largest row sum of |vf| (row sums = column sums), G lanes per row; part[blockIdx.x]
+// ||A||_1 of the symmetric A: the largest row sum of |vf| (row sums = column sums), G lanes per row; part[blockIdx.x].
+// (Not an epilogue of the sweep: it reads neither ci nor z and sums with +=, where the sweep's sums are fma chains.)
 template <int G>
 __global__ __launch_bounds__(kCThreads) void k_sym_norm1(const int64_t* __restrict__ rp, const double* __restrict__ vf,
                                                          int n, u64* __restrict__ part) {
@@ -307,47 +229,6 @@ int ensure_cond(parsy_plan* pl, int nrhs) {
     return 0;
 }
 
-int nblocks(int n, int rows_per_block) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(kRefinePartials, ((int64_t)n + rows_per_block - 1) / rows_per_block));
-}
-
-// w and the partial maxima of |z| of every column, on k_sym_residual's two regimes; returns the number of partials
-int weight_enqueue(parsy_plan* pl, const double* z, const double* pb, double* w, int nrhs, u64* zpart,
-                   hipStream_t stream) {
-    RefineState& R = *pl->refine;
-    const int n = pl->S.n;
-    const double nz = (double)(R.max_row + 1);
-    const double safe1 = nz * DBL_MIN, safe2 = safe1 / 0x1p-53, nzeps = nz * 0x1p-53;
-    if (nrhs <= 4) {
-        const int G = R.group, nb = nblocks(n, kCThreads / G);
-#define C_GROUP(GG, NN)                                                                                              \
-    if (G == GG && nrhs == NN)                                                                                       \
-        hipLaunchKernelGGL((k_sym_weight<GG, NN>), dim3(nb), dim3(kCThreads), 0, stream, R.d_rp, R.d_ci, R.d_vf, z, pb, \
-                           w, n, nzeps, safe1, safe2, zpart);
-#define C_GROUPS(GG) C_GROUP(GG, 1) C_GROUP(GG, 2) C_GROUP(GG, 3) C_GROUP(GG, 4)
-        C_GROUPS(4) C_GROUPS(8) C_GROUPS(16) C_GROUPS(32)
-#undef C_GROUPS
-#undef C_GROUP
-        PARSY_HIP(hipGetLastError());
-        return nb;
-    }
-    // z staged in the plan's xt as the residual stages it (a solve fills xt afresh; this runs between solves)
-    const int ldq = (nrhs + 15) & ~15;
-    PARSY_HIP(grow_device(pl->xt, pl->xt_len, (int64_t)n * ldq));
-    launch_transpose_x(const_cast<double*>(z), n, pl->xt, ldq, n, nrhs, true, stream);
-    const int L = nrhs <= 8 ? 8 : nrhs <= 16 ? 16 : nrhs <= 32 ? 32 : 64;
-    const int nb = nblocks(n, kCThreads / L);
-    const dim3 grid(nb, (nrhs + L - 1) / L);
-#define C_MRHS(LL)                                                                                                   \
-    if (L == LL)                                                                                                     \
-        hipLaunchKernelGGL(k_sym_weight_mrhs<LL>, grid, dim3(kCThreads), 0, stream, R.d_rp, R.d_ci, R.d_vf, pl->xt, ldq, \
-                           pb, w, n, nrhs, nzeps, safe1, safe2, zpart);
-    C_MRHS(8) C_MRHS(16) C_MRHS(32) C_MRHS(64)
-#undef C_MRHS
-    PARSY_HIP(hipGetLastError());
-    return nb;
-}
-
 // The estimator's loop over `ncols` columns of the operand v (w null: no weights): est of every column in its CondCol.
 // ctl = {columns that go on, status of the solves}; the host reads it once per application.
 int estimate(parsy_plan* pl, const char* who, const double* d_L, double* v, const double* w, int ncols, int* ctl,
@@ -400,7 +281,7 @@ int cond_bounds_phase(parsy_plan* pl, const char* who, const double* d_L, int nr
     const double *pb = R.ws, *z = R.ws + nn;
     double *w = C.ws, *v = C.ws + std::max<int64_t>(nn, 1);
     const CondCols c = cond_cols(C);
-    const int nb = weight_enqueue(pl, z, pb, w, nrhs, c.part, stream);
+    const int nb = sym_sweep_enqueue<WeightOut>(pl, z, pb, w, nrhs, c.part, stream);
     if (nb < 0) return -1;
     if (estimate(pl, who, d_L, v, w, nrhs, col_state(R, R.colstate_cap).ctl, stream) != 0) return -1;
     hipLaunchKernelGGL(k_cond_finish, dim3(nrhs), dim3(kCThreads), 0, stream, c.col, c.part, nb, c.out, 0);
@@ -417,16 +298,16 @@ int plan_error_bounds(parsy_plan* pl, const double* d_values, const double* d_L,
     const int n = pl->S.n;
     if (nrhs < 1 || nrhs > 65535 || ldx < n || ldb < n)
         return set_last_error(std::string(who) + ": need 1 <= nrhs <= 65535 and leading dimensions >= n"), -1;
-    if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, nrhs) != 0) return -1;
+    const int* perm = nullptr;
+    if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, nrhs, &perm) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
     double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
     PARSY_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
-    if (refine_gather_values(pl, d_values, stream) != 0 ||
-        refine_permute_in(pl, d_x, ldx, z, nullptr, nrhs, stream) != 0 ||
-        refine_permute_in(pl, d_b, ldb, pb, nullptr, nrhs, stream) != 0)
-        return -1;
+    if (refine_gather_values(pl, d_values, stream) != 0) return -1;
+    enqueue_perm_gather(perm, d_x, ldx, z, nullptr, n, nrhs, stream);
+    enqueue_perm_gather(perm, d_b, ldb, pb, nullptr, n, nrhs, stream);
     const int nb = refine_residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
     if (nb < 0 || refine_report_berr(pl, nb, nrhs, stream) != 0) return -1;
     if (ferr && cond_bounds_phase(pl, who, d_L, nrhs, ferr, stream) != 0) return -1;
@@ -441,7 +322,8 @@ int plan_rcond(parsy_plan* pl, const double* d_values, const double* d_L, double
                hipStream_t stream) {
     const char* who = "parsy_rcond_device";
     if (check_plan(pl, who, kNeedsIdle) != 0) return -1;
-    if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, 1) != 0 || ensure_cond(pl, 1) != 0) return -1;
+    const int* perm = nullptr;   // (not read here: the workspace call uploads it as it always has)
+    if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, 1, &perm) != 0 || ensure_cond(pl, 1) != 0) return -1;
     RefineState& R = *pl->refine;
     CondState& C = *pl->cond;
     C.columns = 1;
@@ -452,11 +334,10 @@ int plan_rcond(parsy_plan* pl, const double* d_values, const double* d_L, double
     PARSY_HIP(hipMemsetAsync(rc.ctl, 0, 2 * sizeof(int), stream));
     PARSY_HIP(hipMemsetAsync(c.col, 0, sizeof(CondCol), stream));
     if (refine_gather_values(pl, d_values, stream) != 0) return -1;
-    const int G = R.group, nb = nblocks(n, kCThreads / G);
-#define C_NORM(GG) \
-    if (G == GG) hipLaunchKernelGGL(k_sym_norm1<GG>, dim3(nb), dim3(kCThreads), 0, stream, R.d_rp, R.d_vf, n, c.part);
-    C_NORM(4) C_NORM(8) C_NORM(16) C_NORM(32)
-#undef C_NORM
+    const int nb = sym_sweep_blocks(n, kCThreads / R.group);
+    dispatch_int(R.group, SweepGroups(), [&](auto g) {
+        hipLaunchKernelGGL(k_sym_norm1<decltype(g)::value>, dim3(nb), dim3(kCThreads), 0, stream, R.d_rp, R.d_vf, n, c.part);
+    });
     PARSY_HIP(hipGetLastError());
     if (rcond && estimate(pl, who, d_L, C.ws + std::max(n, 1), nullptr, 1, rc.ctl, stream) != 0) return -1;
     hipLaunchKernelGGL(k_cond_finish, dim3(1), dim3(kCThreads), 0, stream, c.col, c.part, nb, c.out, 1);

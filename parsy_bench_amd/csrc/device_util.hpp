@@ -31,4 +31,9 @@ __device__ __forceinline__ void put16(double* __restrict__ Z, double4_t acc, dou
     for (int v = 0; v < 4; ++v) Z[l15 * LD + kq + 4 * v] = sign * acc[v];
 }
 
+// beta == 0: y is not read (it may hold NaN)
+__device__ __forceinline__ void store_y(double* __restrict__ y, double alpha, double beta, double s) {
+    *y = beta == 0.0 ? alpha * s : fma(beta, *y, alpha * s);
+}
+
 }  // namespace parsy

@@ -8,6 +8,7 @@
 
 #include "apply.hpp"
 #include "cond.hpp"
+#include "device_util.hpp"
 #include "errors.hpp"
 #include "grad.hpp"
 #include "hip_check.hpp"
@@ -31,6 +32,89 @@ int check_plan(const parsy_plan* pl, const char* who, PlanNeeds needs) {
     if (pl->factor_open) return set_last_error(w + ": a factorization is still open (parsy_factor_begin)"), -1;
     if (pl->levels_open) return set_last_error(w + ": a solve in steps of levels is still open"), -1;
     return 0;
+}
+
+int plan_set_perm(parsy_plan* pl, const int* perm) {
+    const int n = pl->S.n;
+    std::vector<int> p;
+    if (perm) {
+        p.assign(perm, perm + n);
+        std::vector<char> seen((size_t)n, 0);
+        for (int v : p) {
+            if (v < 0 || v >= n || seen[v])
+                return set_last_error("parsy_plan_set_perm: perm is not a permutation of 0..n-1"), -1;
+            seen[v] = 1;
+        }
+    }
+    if (pl->d_perm) {
+        (void)hipSetDevice(pl->device);
+        (void)hipDeviceSynchronize();   // (a call may still read the old one)
+        (void)hipFree(pl->d_perm);
+        pl->device_bytes -= (int64_t)pl->perm.size() * 4;
+        pl->d_perm = nullptr;
+    }
+    pl->perm.swap(p);
+    return 0;
+}
+
+int plan_perm_device(parsy_plan* pl, const int** out) {
+    *out = nullptr;
+    if (pl->perm.empty()) return 0;
+    if (!pl->d_perm) {
+        PARSY_HIP(hipMalloc((void**)&pl->d_perm, pl->perm.size() * 4));
+        PARSY_HIP(hipMemcpy(pl->d_perm, pl->perm.data(), pl->perm.size() * 4, hipMemcpyHostToDevice));
+        pl->device_bytes += (int64_t)pl->perm.size() * 4;
+    }
+    *out = pl->d_perm;
+    return 0;
+}
+
+// ---- n x nrhs operands between the caller's ordering and the plan's own (plan_util.hpp) ----
+constexpr int kPermThreads = 256;
+
+// dst[k, q] = src[perm[k], q] (dst leading dimension n; a second copy into dst2 when given)
+__global__ __launch_bounds__(kPermThreads) void k_perm_gather(const int* __restrict__ perm,
+                                                                     const double* __restrict__ src, int64_t ld, int n,
+                                                                     int nrhs, double* __restrict__ dst,
+                                                                     double* __restrict__ dst2) {
+    const int64_t k = (int64_t)blockIdx.x * kPermThreads + threadIdx.x;
+    if (k >= n) return;
+    const int64_t s = perm ? perm[k] : k;
+    for (int64_t q = blockIdx.y; q < nrhs; q += gridDim.y) {
+        const double v = src[s + q * ld];
+        dst[k + q * n] = v;
+        if (dst2) dst2[k + q * n] = v;
+    }
+}
+
+// dst[perm[k], q] = beta dst[perm[k], q] + alpha src[k, q] (src leading dimension n)
+__global__ __launch_bounds__(kPermThreads) void k_perm_scatter(const int* __restrict__ perm,
+                                                                      const double* __restrict__ src, int n, int nrhs,
+                                                                      double alpha, double beta, double* __restrict__ dst,
+                                                                      int64_t ld) {
+    const int64_t k = (int64_t)blockIdx.x * kPermThreads + threadIdx.x;
+    if (k >= n) return;
+    const int64_t d = perm ? perm[k] : k;
+    for (int64_t q = blockIdx.y; q < nrhs; q += gridDim.y) store_y(dst + d + q * ld, alpha, beta, src[k + q * n]);
+}
+
+// a thread per row, the columns strided over the grid's y (any nrhs >= 1)
+static dim3 perm_grid(int n, int nrhs) {
+    return dim3((unsigned)((n + kPermThreads - 1) / kPermThreads), (unsigned)(nrhs < 65535 ? nrhs : 65535));
+}
+
+void enqueue_perm_gather(const int* perm, const double* src, int64_t ld, double* dst, double* dst2, int n,
+                                       int nrhs, hipStream_t stream) {
+    if (n > 0)
+        hipLaunchKernelGGL(k_perm_gather, perm_grid(n, nrhs), dim3(kPermThreads), 0, stream, perm, src, ld, n, nrhs, dst,
+                           dst2);
+}
+
+void enqueue_perm_scatter(const int* perm, const double* src, double alpha, double beta, double* dst,
+                                        int64_t ld, int n, int nrhs, hipStream_t stream) {
+    if (n > 0)
+        hipLaunchKernelGGL(k_perm_scatter, perm_grid(n, nrhs), dim3(kPermThreads), 0, stream, perm, src, n, nrhs, alpha,
+                           beta, dst, ld);
 }
 
 EventTimer::~EventTimer() {
@@ -240,6 +324,7 @@ void plan_free(parsy_plan* pl) {
             q = nullptr;
         }
         if (pl->xt) (void)hipFree(pl->xt);
+        if (pl->d_perm) (void)hipFree(pl->d_perm);
         if (pl->dinv) (void)hipFree(pl->dinv);
         if (pl->dp.bpart) (void)hipFree(pl->dp.bpart);
         if (pl->h_values_dev) (void)hipFree(pl->h_values_dev);

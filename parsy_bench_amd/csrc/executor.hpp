@@ -93,6 +93,10 @@ struct parsy_plan {
     double kind_ms[PARSY_PROFILE_KINDS] = {};
     int kind_launches[PARSY_PROFILE_KINDS] = {};
     int profiled_runs = 0;
+    // the caller's ordering (parsy_plan_set_perm; plan_util.hpp): perm[new] = old (empty: identity) and its device copy,
+    // uploaded by the first call that reads it (null: identity or not yet uploaded)
+    std::vector<int> perm;
+    int* d_perm = nullptr;
     parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
     parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
     parsy::GradState* grad = nullptr;       // gradients with respect to A's values (grad.hpp): made by the first such call

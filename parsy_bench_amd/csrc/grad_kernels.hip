@@ -22,7 +22,6 @@
 #include "executor.hpp"
 #include "plan_util.hpp"
 #include "grad.hpp"
-#include "refine.hpp"
 
 namespace parsy {
 

@@ -1,5 +1,5 @@
-// Host-side helpers of the files that work on a parsy_plan: the plan's refusals, device buffers that grow or are
-// uploaded with their bytes counted, and the event pair that times a host-buffer call.  The only copy of each; what is
+// Host-side helpers of the files that work on a parsy_plan: the plan's refusals, the caller's ordering, device buffers
+// that grow or are uploaded with their bytes counted, and the event pair that times a host-buffer call.  The only copy of each; what is
 // no template is defined in executor.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,18 @@ namespace parsy {
 enum PlanNeeds { kNeedsDevice, kNeedsA, kNeedsIdle };
 // 0, or -1 with the refusal as the last error; `who` names the call in the message.
 int check_plan(const parsy_plan* pl, const char* who, PlanNeeds needs);
+
+// The caller's ordering of the plan's vectors (perm[new] = old, n entries; null: back to the identity).
+int plan_set_perm(parsy_plan* pl, const int* perm);
+// the device copy of that ordering, uploaded on first use and counted in device_bytes (*out null: identity)
+int plan_perm_device(parsy_plan* pl, const int** out);
+// The one gather and the one scatter of n x nrhs column-major operands under such a device copy (perm null: identity):
+// dst[k, q] = src[perm[k], q] (src leading dimension ld, dst n; a second copy into dst2 when given), and
+// dst[perm[k], q] = beta dst[perm[k], q] + alpha src[k, q] (src leading dimension n, dst ld; beta == 0: dst is not read)
+void enqueue_perm_gather(const int* perm, const double* src, int64_t ld, double* dst, double* dst2, int n, int nrhs,
+                         hipStream_t stream);
+void enqueue_perm_scatter(const int* perm, const double* src, double alpha, double beta, double* dst, int64_t ld, int n,
+                          int nrhs, hipStream_t stream);
 
 // buf (len elements) made at least `need` elements long; the contents are not kept
 template <class T>

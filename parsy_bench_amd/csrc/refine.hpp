@@ -4,21 +4,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <vector>
 
 struct parsy_plan;
 
 namespace parsy {
 
 struct RefineState {
-    // caller's ordering: perm[new] = old (empty: identity), and its device copy (null: identity)
-    std::vector<int> perm;
-    int* d_perm = nullptr;
     // both triangles of P A P' as CSR, built on first use from the A2 pattern the plan scatters (a_dst + L's rows):
     // row i holds its entries in ascending A2 order; src[e] is the A2 index of entry e, vf[e] = values[src[e]]
     int64_t nnz_full = 0;
     int max_row = 0;          // most entries in a row of the full symmetric A
-    int group = 0;            // lanes per row of k_sym_residual with 1-4 right-hand sides (from the mean row length)
+    int group = 0;            // lanes per row of k_sym_sweep with 1-4 right-hand sides (from the mean row length)
     int64_t* d_rp = nullptr;
     int* d_ci = nullptr;
     int* d_src = nullptr;
@@ -32,25 +28,9 @@ struct RefineState {
     int colstate_cap = 0;     // right-hand sides colstate is made for
 };
 
-constexpr int kRefinePartials = 1024;   // workgroups of k_sym_residual (grid-stride over the rows) = partials per column
+constexpr int kRefinePartials = 1024;   // most workgroups of a sweep (sym_sweep.hpp) = partials per column
 constexpr int kRefineThreads = 256;     // threads of a workgroup of every kernel here and in cond_kernels.hip
-
-// ---- device helpers of the max-reductions (also cond_kernels.hip) ----
-using u64 = unsigned long long;
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m) {
-    const int lo = __shfl_xor((int)(unsigned)v, m), hi = __shfl_xor((int)(unsigned)(v >> 32), m);
-    return ((u64)(unsigned)hi << 32) | (u64)(unsigned)lo;
-}
-
-// One wave's max, then the workgroup's across its four waves; lane 0 of wave w leaves its value in sm[w].
-__device__ __forceinline__ u64 block_max(u64 v, u64* sm) {
-    for (int o = 32; o; o >>= 1) v = max(v, shfl_xor_u64(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return max(max(sm[0], sm[1]), max(sm[2], sm[3]));
-}
+using u64 = unsigned long long;         // the bits of a non-negative double, max-reduced
 
 // ---- host helpers shared with the error bounds and the condition estimate (cond_kernels.hip) ----
 // the per-column state inside colstate
@@ -60,14 +40,12 @@ struct ColState {
     int *active, *steps, *ctl;
 };
 ColState col_state(RefineState& R, int cap);
-// Both triangles of P A P' as CSR, on first use; pb, z, r (n x nrhs), the per-column state and the perm's device copy
+// Both triangles of P A P' as CSR, on first use; pb, z, r (n x nrhs), the per-column state and, in *perm, the plan's
+// ordering on the device (plan_perm_device)
 int refine_ensure_pattern(parsy_plan* pl);
-int refine_ensure_workspace(parsy_plan* pl, int nrhs);
+int refine_ensure_workspace(parsy_plan* pl, int nrhs, const int** perm);
 // vf = the caller's A2-order values on the full pattern
 int refine_gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream);
-// dst[k, q] = src[perm[k], q] under the plan's ordering (dst leading dimension n; a second copy into dst2 when given)
-int refine_permute_in(parsy_plan* pl, const double* src, int64_t ld, double* dst, double* dst2, int nrhs,
-                      hipStream_t stream);
 // r = pb - A z and the partial maxima of every column's backward error; returns the number of partials (< 0: error)
 int refine_residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* r, int nrhs, u64* part,
                             hipStream_t stream);
@@ -78,9 +56,6 @@ int refine_report_berr(parsy_plan* pl, int nb, int nrhs, hipStream_t stream);
 int refine_solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* ctl, hipStream_t stream);
 
 void refine_free(parsy_plan* pl);
-int plan_set_perm(parsy_plan* pl, const int* perm);
-// the device copy of that ordering, uploaded on first use (*out null: identity)
-int plan_perm_device(parsy_plan* pl, const int** out);
 int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
                   double* d_r, int ldr, int nrhs, double* berr, hipStream_t stream);
 // ferr (host, nrhs; may be null): the forward error bounds of the returned X (cond.hpp), taken from the z, pb and values

@@ -27,7 +27,6 @@
 #include "hip_check.hpp"
 #include "executor.hpp"
 #include "plan_util.hpp"
-#include "refine.hpp"
 #include "selinv.hpp"
 
 namespace parsy {

@@ -77,8 +77,13 @@ def _columns(n, nrhs, seed):
     return Xt, zero, rng
 
 
-@pytest.mark.parametrize("nrhs", [1, 4, 5, 17])
-@pytest.mark.parametrize("name", ["tiny2d", "small3d", "random300", "small3d*1e3"])
+# every lane split of the sweep (tiny2d 4, random300 8, small3d 16, dense150 32 lanes per row), and on dense150 every
+# column count it is instantiated for (1 .. 4; staged: up to 8, 16, 32, 64)
+_BOUNDS = [(nm, k) for nm in ("tiny2d", "small3d", "random300", "small3d*1e3") for k in (1, 4, 5, 17)] + \
+          [("dense150", k) for k in (1, 2, 3, 4, 5, 12, 17, 64)]
+
+
+@pytest.mark.parametrize("name,nrhs", _BOUNDS)
 def test_error_bounds(api, name, nrhs):
     import torch
     sym, plan, lv, Ad, Ainv = _cond_case(api, name)

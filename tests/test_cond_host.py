@@ -13,6 +13,7 @@ import scipy.linalg as sla
 
 from conftest import problem
 from test_refine_host import EPS, SAFMIN, dporfs, full_matrix
+from test_selinv_host import edge
 
 UPPER = 1 + 1e-6
 
@@ -27,7 +28,7 @@ def scaled(A, k):
 
 
 _INPUTS = {}
-UNSCALED = ["tiny2d", "small3d", "random300", "grid1e-8", "n1", "n2", "n3"]
+UNSCALED = ["tiny2d", "small3d", "random300", "grid1e-8", "dense150", "n1", "n2", "n3"]
 SCALED = [f"{nm}*1e{k}" for nm in ("tiny2d", "small3d", "random300") for k in (2, 3)]
 ALL = UNSCALED + SCALED
 
@@ -46,6 +47,9 @@ def cond_input(name):
         out = (A, perm)
     elif name == "random300":
         out = (M.random_spd(300, density=0.03, seed=5), None)
+    elif name == "dense150":   # (a dense row: 32 lanes per row in the sweeps)
+        A = edge(name)[0]
+        out = (A, np.arange(A.n, dtype=np.int32))
     elif name == "grid1e-8":
         out = (M.grid_spd(24, 24, 1, 5, 1e-8), M.grid_nd(24, 24, 1))
     else:

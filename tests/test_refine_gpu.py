@@ -80,7 +80,7 @@ def _rel(a, b):
 
 # ---- 1. residual against scipy ------------------------------------------------------------------------------
 _RESID = [(nm, k) for nm in ("tiny2d", "ex15", "mid3d", "lap30", "random") for k in (1, 3, 8, 17, 64)] + \
-         [("parabolic_fem", 1)]
+         [("small3d", k) for k in (2, 4, 12)] + [("parabolic_fem", 1)]   # small3d: 16 lanes per row; 2, 4 and 9-16 columns
 
 
 @pytest.mark.parametrize("name,nrhs", _RESID)

@@ -11,7 +11,7 @@ Per workload and number of right-hand sides (median of --reps, ms):
   inverse_pattern -- parsy_inverse_pattern_device on an arbitrary Z (24 nnzA bytes and a gather), for scale
   residual_call -- the yardstick, timed in the same run: parsy_residual_device (berr included, so with its host
                    synchronisation) at the same input, ordering and right-hand sides -- the value gather, two
-                   permutations in, k_sym_residual (one pass over the same pattern with one gathered operand where
+                   permutations in, k_sym_sweep (one pass over the same pattern with one gathered operand where
                    pattern_outer has four) and the berr pass; tools/refine_bench.py records the same call
 """
 import argparse

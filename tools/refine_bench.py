@@ -6,8 +6,8 @@ Usage: python tools/refine_bench.py [--workloads flan,parabolic_fem] [--nrhs 1,8
 Per workload and number of right-hand sides (median of --reps, ms):
   solve_fb     -- the plain forward + backward solve of the permuted system (parsy_solve_device + parsy_backsolve_device)
   residual_call -- parsy_residual_device with the identity ordering and berr: the value gather, the two permutations in,
-                  k_sym_residual and the berr pass, with its host synchronisation
-  gather, k_sym_residual -- the kernels alone: run this tool under `rocprofv3 --kernel-trace --stats`
+                  k_sym_sweep and the berr pass, with its host synchronisation
+  gather, k_sym_sweep -- the kernels alone: run this tool under `rocprofv3 --kernel-trace --stats`
   step         -- one refinement step, host synchronisation included: the call with max_steps = 1 minus the call with
                   max_steps = 0 (both report berr and steps), on values 10 % of the diagonal shift away from the factor
   resid_bytes  -- full pattern values (8 B) and column indices (4 B), row pointers (8 B), z, pb, r once each
