@@ -82,25 +82,7 @@ void build_apply_layout(const Schedule& S, const ApplyIndex& I, ApplyLayout& A);
 // doubles of the products' workspace for blocks of kApplyBlock columns: T, or the partials and the staged X
 int64_t apply_workspace_len(const Schedule& S, const ApplyLayout& A);
 
-struct ApplyState {
-    bool built = false;
-    ApplyIndex I;                     // (pos and the layout are released once they are on the device; the counts stay)
-    ApplyLayout A;
-    int64_t ws_need = 0;              // apply_workspace_len
-    int64_t n_l_tasks = 0, n_lt_tasks = 0;
-    int64_t* d_ptr = nullptr;
-    ApplyOcc* d_occ = nullptr;
-    ApplyTaskL* d_l_tasks = nullptr;
-    ApplyTaskLt* d_lt_tasks = nullptr;
-    ApplyCol* d_col = nullptr;
-    int64_t index_bytes = 0;
-    double* ws = nullptr;             // T / partials + staged X of one block of columns
-    int64_t ws_len = 0;
-    double* sol = nullptr;            // n x nrhs operand of the inverse operators
-    int64_t sol_len = 0;
-    int last_op = -1, last_launches = 0;
-};
-void apply_free(parsy_plan* pl);
+struct ApplyState;   // the device state (feature_states.hpp)
 // the host index of a plan, made on first use (host-only plans too)
 int apply_ensure_host(parsy_plan* pl);
 // refusals of parsy_factor_apply_device / _host that need no device; 0, or -1 with the message set

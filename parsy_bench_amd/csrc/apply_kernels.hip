@@ -25,7 +25,7 @@
 #include "hip_check.hpp"
 #include "executor.hpp"
 #include "plan_util.hpp"
-#include "apply.hpp"
+#include "feature_states.hpp"
 
 namespace parsy {
 
@@ -188,12 +188,17 @@ int ensure_device(parsy_plan* pl) {
     if (apply_ensure_host(pl) != 0) return -1;
     ApplyState& A = *pl->apply;
     PARSY_HIP(hipSetDevice(pl->device));
-    if (A.d_ptr) return 0;
-    if (upload_counted(A.d_ptr, A.I.ptr, A.index_bytes) != 0 || upload_counted(A.d_occ, A.A.occ, A.index_bytes) != 0 ||
-        upload_counted(A.d_l_tasks, A.A.l_tasks, A.index_bytes) != 0 ||
-        upload_counted(A.d_lt_tasks, A.A.lt_tasks, A.index_bytes) != 0 || upload_counted(A.d_col, A.A.col, A.index_bytes) != 0)
-        return -1;
-    pl->device_bytes += A.index_bytes;
+    if (A.on_device) return 0;
+    DevicePool pool(&A.meter);
+    int64_t* d_ptr = pool.upload(A.I.ptr);
+    ApplyOcc* d_occ = pool.upload(A.A.occ);
+    ApplyTaskL* d_l_tasks = pool.upload(A.A.l_tasks);
+    ApplyTaskLt* d_lt_tasks = pool.upload(A.A.lt_tasks);
+    ApplyCol* d_col = pool.upload(A.A.col);
+    if (pool.error() != hipSuccess) return pool_failed(pool);
+    A.index = std::move(pool);
+    A.d_ptr = d_ptr, A.d_occ = d_occ, A.d_l_tasks = d_l_tasks, A.d_lt_tasks = d_lt_tasks, A.d_col = d_col;
+    A.on_device = true;
     A.I = ApplyIndex{{}, {}, A.I.max_occurrences};   // (the host copies have served; the counts stay)
     A.A = ApplyLayout();
     return 0;
@@ -217,7 +222,7 @@ static_assert(kApplyBlock == 8, "APPLY_NB lists the instantiations 1 .. kApplyBl
 }  // namespace
 
 int apply_ensure_host(parsy_plan* pl) {
-    if (!pl->apply) pl->apply = new ApplyState;
+    if (!pl->apply) pl->apply = std::make_unique<ApplyState>(&pl->meter);
     ApplyState& A = *pl->apply;
     if (A.built) return 0;
     build_apply_index(pl->S, A.I);
@@ -227,17 +232,6 @@ int apply_ensure_host(parsy_plan* pl) {
     A.n_lt_tasks = (int64_t)A.A.lt_tasks.size();
     A.built = true;
     return 0;
-}
-
-void apply_free(parsy_plan* pl) {
-    ApplyState* A = pl->apply;
-    if (!A) return;
-    if (pl->device >= 0)
-        for (void* p : {(void*)A->d_ptr, (void*)A->d_occ, (void*)A->d_l_tasks, (void*)A->d_lt_tasks, (void*)A->d_col,
-                        (void*)A->ws, (void*)A->sol})
-            if (p) (void)hipFree(p);
-    delete A;
-    pl->apply = nullptr;
 }
 
 int apply_check_args(const parsy_plan* pl, const char* who, const void* lValues, int op, const void* x, int ldx, int nrhs,
@@ -267,18 +261,20 @@ int plan_factor_apply(parsy_plan* pl, const double* d_L, int op, const double* d
     const dim3 threads(kAThreads);
     const unsigned nblocks = blocks_of(n, kAThreads);
     if (op == PARSY_OP_GINV || op == PARSY_OP_GINVT) {
-        if (grow_counted(pl, A.sol, A.sol_len, (int64_t)n * nrhs) != 0) return -1;
+        PARSY_HIP(A.sol.grow((int64_t)n * nrhs));
+        double* const sol = A.sol.data();
         const bool back = op == PARSY_OP_GINVT;
-        enqueue_perm_gather(back ? nullptr : perm, d_x, ldx, A.sol, nullptr, n, nrhs, stream);
+        enqueue_perm_gather(back ? nullptr : perm, d_x, ldx, sol, nullptr, n, nrhs, stream);
         PARSY_HIP(hipGetLastError());
-        if ((back ? plan_backsolve(pl, d_L, A.sol, nrhs, n, stream) : plan_solve(pl, d_L, A.sol, nrhs, n, stream)) != 0)
+        if ((back ? plan_backsolve(pl, d_L, sol, nrhs, n, stream) : plan_solve(pl, d_L, sol, nrhs, n, stream)) != 0)
             return -1;
-        enqueue_perm_scatter(back ? perm : nullptr, A.sol, alpha, beta, d_y, ldy, n, nrhs, stream);
+        enqueue_perm_scatter(back ? perm : nullptr, sol, alpha, beta, d_y, ldy, n, nrhs, stream);
         PARSY_HIP(hipGetLastError());
         A.last_launches = 2;   // (besides the solve's own)
         return 0;
     }
-    if (grow_counted(pl, A.ws, A.ws_len, A.ws_need) != 0) return -1;
+    PARSY_HIP(A.ws.grow(A.ws_need));
+    double* const ws = A.ws.data();
     for (int q0 = 0; q0 < nrhs; q0 += kApplyBlock) {
         const int nb = std::min(kApplyBlock, nrhs - q0);
         const double* x = d_x + (int64_t)q0 * ldx;
@@ -287,19 +283,19 @@ int plan_factor_apply(parsy_plan* pl, const double* d_L, int op, const double* d
             if (A.n_l_tasks > 0) {
 #define APPLY_L_PANELS(NN)                                                                                              \
     hipLaunchKernelGGL(k_apply_l_panels<NN>, dim3(blocks_of(A.n_l_tasks, kAWaves)), threads, 0, stream, A.d_l_tasks, \
-                       A.n_l_tasks, d_L, x, (int64_t)ldx, A.ws)
+                       A.n_l_tasks, d_L, x, (int64_t)ldx, ws)
                 APPLY_NB(nb, APPLY_L_PANELS)
 #undef APPLY_L_PANELS
                 ++A.last_launches;
             }
 #define APPLY_L_ROWS(NN)                                                                                                  \
-    hipLaunchKernelGGL(k_apply_l_rows<NN>, dim3(nblocks), threads, 0, stream, A.d_ptr, A.d_occ, A.ws, perm, alpha, beta, y, \
+    hipLaunchKernelGGL(k_apply_l_rows<NN>, dim3(nblocks), threads, 0, stream, A.d_ptr, A.d_occ, ws, perm, alpha, beta, y, \
                        (int64_t)ldy, n)
             APPLY_NB(nb, APPLY_L_ROWS)
 #undef APPLY_L_ROWS
             ++A.last_launches;
         } else {
-            double* xt = A.ws + A.ws_need - (int64_t)n * kApplyBlock;   // (the last n rows of the workspace, behind the partials)
+            double* xt = ws + A.ws_need - (int64_t)n * kApplyBlock;   // (the last n rows of the workspace, behind the partials)
 #define APPLY_STAGE(NN) hipLaunchKernelGGL(k_apply_stage<NN>, dim3(nblocks), threads, 0, stream, perm, x, (int64_t)ldx, n, xt)
             APPLY_NB(nb, APPLY_STAGE)
 #undef APPLY_STAGE
@@ -307,13 +303,13 @@ int plan_factor_apply(parsy_plan* pl, const double* d_L, int op, const double* d
             if (A.n_lt_tasks > 0) {
 #define APPLY_LT_PANELS(NN)                                                                                                \
     hipLaunchKernelGGL(k_apply_lt_panels<NN>, dim3(blocks_of(A.n_lt_tasks, kAWaves)), threads, 0, stream, A.d_lt_tasks, \
-                       A.n_lt_tasks, pl->dp.rows, d_L, xt, A.ws)
+                       A.n_lt_tasks, pl->dp.rows, d_L, xt, ws)
                 APPLY_NB(nb, APPLY_LT_PANELS)
 #undef APPLY_LT_PANELS
                 ++A.last_launches;
             }
 #define APPLY_LT_COLS(NN) \
-    hipLaunchKernelGGL(k_apply_lt_cols<NN>, dim3(nblocks), threads, 0, stream, A.d_col, A.ws, alpha, beta, y, (int64_t)ldy, n)
+    hipLaunchKernelGGL(k_apply_lt_cols<NN>, dim3(nblocks), threads, 0, stream, A.d_col, ws, alpha, beta, y, (int64_t)ldy, n)
             APPLY_NB(nb, APPLY_LT_COLS)
 #undef APPLY_LT_COLS
             ++A.last_launches;

@@ -21,7 +21,7 @@
 #include "plan_util.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
-#include "apply.hpp"
+#include "feature_states.hpp"
 
 using parsy::set_last_error;
 
@@ -327,7 +327,7 @@ int parsy_plan_get_info(const parsy_plan* pl, parsy_plan_info* o) {
     o->nnzL = S.nnzL;
     o->n_updates = (int64_t)S.upd.size();
     o->relpos_len = (int64_t)S.relpos.size();
-    o->device_bytes = pl->device_bytes;
+    o->device_bytes = pl->meter.bytes;
     o->flops_stored = S.flops_stored;
     o->update_flops = S.update_flops;
     o->reread_bytes = S.reread_bytes;
@@ -738,7 +738,7 @@ int parsy_factor_apply_get_info(parsy_plan* pl, parsy_apply_info* info) {
     info->max_occurrences = A.I.max_occurrences;
     info->block_columns = parsy::kApplyBlock;
     info->workspace_bytes = A.ws_need * 8;
-    info->device_bytes = A.index_bytes + (A.ws_len + A.sol_len) * 8;
+    info->device_bytes = A.meter.bytes;
     info->last_op = A.last_op;
     info->last_launches = A.last_launches;
     return 0;

@@ -19,8 +19,7 @@
 #include "plan_util.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
-#include "selinv.hpp"
-#include "apply.hpp"
+#include "feature_states.hpp"
 
 using parsy::set_last_error;
 
@@ -37,9 +36,9 @@ int check_device(const parsy_plan* pl, const char* who) {
 // on request (both made once), the right-hand sides' grown to x_len doubles (0: not used, left as it is).
 hipError_t stage(parsy_plan* pl, bool values, int64_t x_len) {
     const parsy::Schedule& S = pl->S;
-    hipError_t e = parsy::grow_device(pl->h_L_dev, pl->h_L_len, std::max<int64_t>(S.xsize, 1));
-    if (e == hipSuccess && values) e = parsy::grow_device(pl->h_values_dev, pl->h_values_len, std::max<int64_t>(S.nnzA, 1));
-    if (e == hipSuccess) e = parsy::grow_device(pl->h_x_dev, pl->h_x_len, x_len);
+    hipError_t e = pl->h_L_dev.grow(std::max<int64_t>(S.xsize, 1));
+    if (e == hipSuccess && values) e = pl->h_values_dev.grow(std::max<int64_t>(S.nnzA, 1));
+    if (e == hipSuccess) e = pl->h_x_dev.grow(x_len);
     return e;
 }
 
@@ -136,12 +135,12 @@ int solve_staged(parsy_plan* pl, const char* who, const double* lValues, double*
     const int64_t need = (int64_t)ldx * nrhs;
     PARSY_HIP(hipSetDevice(pl->device));
     PARSY_HIP(stage(pl, false, need));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_x_dev, x, (size_t)need * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_x_dev.data(), x, (size_t)need * 8, hipMemcpyHostToDevice));
     double sec = 0;
     auto run = [&](bool back) -> int {
-        const int rc = back ? parsy::plan_backsolve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr)
-                            : parsy::plan_solve(pl, pl->h_L_dev, pl->h_x_dev, nrhs, ldx, nullptr);
+        const int rc = back ? parsy::plan_backsolve(pl, pl->h_L_dev.data(), pl->h_x_dev.data(), nrhs, ldx, nullptr)
+                            : parsy::plan_solve(pl, pl->h_L_dev.data(), pl->h_x_dev.data(), nrhs, ldx, nullptr);
         if (rc != 0) return -1;
         PARSY_HIP(hipDeviceSynchronize());
         if (parsy_solve_status(pl) != 0) return -1;
@@ -151,21 +150,17 @@ int solve_staged(parsy_plan* pl, const char* who, const double* lValues, double*
     if (forward && run(false) != 0) return -1;
     if (backward && run(true) != 0) return -1;
     if (seconds) *seconds = sec;
-    PARSY_HIP(hipMemcpy(x, pl->h_x_dev, (size_t)need * 8, hipMemcpyDeviceToHost));
+    PARSY_HIP(hipMemcpy(x, pl->h_x_dev.data(), (size_t)need * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
 // Device buffers of one gradient host call, freed when it returns, and the call's timer.
 struct Scratch {
-    std::vector<void*> bufs;
+    parsy::DevicePool bufs;
     parsy::EventTimer timer;
-    ~Scratch() {
-        for (void* p : bufs) (void)hipFree(p);
-    }
     double* upload(const double* h, int64_t len, bool copy) {
-        double* d = nullptr;
-        if (hipMalloc((void**)&d, (size_t)std::max<int64_t>(len, 1) * 8) != hipSuccess) return nullptr;
-        bufs.push_back(d);
+        double* d = bufs.alloc<double>(std::max<int64_t>(len, 1));
+        if (!d) return nullptr;
         if (copy && len > 0 && hipMemcpy(d, h, (size_t)len * 8, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
         return d;
     }
@@ -185,7 +180,7 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
     const parsy::Schedule& S = pl->S;
     PARSY_HIP(hipSetDevice(pl->device));
     PARSY_HIP(stage(pl, true, 0));
-    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev.data(), values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
     // Small factors take the plain form: kernels, then one download.  Large ones (PARSY_HOST_PIPELINE=0: never): the
     // download of every band of levels runs BEHIND the kernels of the levels above it -- a worker thread copies the runs
     // of lValues that a band has made final while this thread's stream goes on (Flan-class: 19.4 GB at PCIe speed take as
@@ -195,16 +190,16 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
     const bool pipeline_on = !(pe && pe[0] == '0'), pipeline_forced = pe && pe[0] == '2';
     if (!pipeline_on || (!pipeline_forced && S.xsize * 8 < (int64_t)256 << 20) || pl->profile || S.cnlevels < 1 ||
         !ensure_pipeline(pl)) {
-        if (parsy::plan_factor(pl, pl->h_values_dev, pl->h_L_dev, nullptr) != 0) return -1;
+        if (parsy::plan_factor(pl, pl->h_values_dev.data(), pl->h_L_dev.data(), nullptr) != 0) return -1;
         PARSY_HIP(hipDeviceSynchronize());
         if (seconds) *seconds = parsy_last_factor_ms(pl) * 1e-3;
-        PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev, (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
+        PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev.data(), (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
         return 0;
     }
     const size_t nb = pl->h_band_level.size();
     std::atomic<int> recorded{0};
     std::atomic<int> failed{0};
-    double* const dL = pl->h_L_dev;
+    double* const dL = pl->h_L_dev.data();
     const int device = pl->device;
     std::thread worker([&, dL, device] {
         if (hipSetDevice(device) != hipSuccess) {
@@ -230,7 +225,7 @@ int parsy_factor_host(parsy_plan* pl, const double* values, double* lValues, dou
             }
         }
     });
-    int rc = parsy::plan_factor_begin(pl, pl->h_values_dev, dL, pl->h_stream, true);
+    int rc = parsy::plan_factor_begin(pl, pl->h_values_dev.data(), dL, pl->h_stream, true);
     size_t b = 0;
     for (int lev = 0; rc == 0 && lev < S.cnlevels; ++lev) {
         rc = parsy::plan_factor_levels(pl, lev, lev + 1, dL, pl->h_stream);
@@ -288,16 +283,17 @@ int parsy_solve_spd_bounds_host(parsy_plan* pl, const double* values, const doub
     PARSY_HIP(hipSetDevice(pl->device));
     PARSY_HIP(stage(pl, true, std::max<int64_t>((int64_t)S.n * nrhs, 1)));
     const size_t row = (size_t)S.n * 8;
-    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
-    if (S.n > 0) PARSY_HIP(hipMemcpy2D(pl->h_x_dev, row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev.data(), values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(pl->h_x_dev.data(), row, b, (size_t)ldb * 8, row, nrhs, hipMemcpyHostToDevice));
     parsy::EventTimer timer;
     if (!timer.start()) {
         set_last_error(std::string(who) + ": hipEventCreate failed");
         return -1;
     }
-    if (parsy::plan_solve_refined(pl, pl->h_values_dev, pl->h_L_dev, pl->h_x_dev, S.n, pl->h_x_dev, S.n, nrhs, max_steps,
-                                  steps, berr, ferr, nullptr) != 0)
+    double* const dx = pl->h_x_dev.data();
+    if (parsy::plan_solve_refined(pl, pl->h_values_dev.data(), pl->h_L_dev.data(), dx, S.n, dx, S.n, nrhs, max_steps, steps,
+                                  berr, ferr, nullptr) != 0)
         return -1;
     double sec = 0;
     if (!timer.stop(&sec)) {
@@ -307,7 +303,7 @@ int parsy_solve_spd_bounds_host(parsy_plan* pl, const double* values, const doub
     // (max_steps == 0 without steps / berr: nothing synchronised inside the call, so the solves' status is read here)
     if (parsy_solve_status(pl) != 0) return -1;
     if (seconds) *seconds = sec;
-    if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev, row, row, nrhs, hipMemcpyDeviceToHost));
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, pl->h_x_dev.data(), row, row, nrhs, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -322,15 +318,16 @@ int parsy_rcond_host(parsy_plan* pl, const double* values, const double* lValues
     const parsy::Schedule& S = pl->S;
     PARSY_HIP(hipSetDevice(pl->device));
     PARSY_HIP(stage(pl, true, 0));
-    PARSY_HIP(hipMemcpy(pl->h_values_dev, values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_values_dev.data(), values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
     parsy::EventTimer timer;
     if (!timer.start()) {
         set_last_error(std::string(who) + ": hipEventCreate failed");
         return -1;
     }
     double an = 0, rc = 0;
-    if (parsy::plan_rcond(pl, pl->h_values_dev, pl->h_L_dev, &an, rcond ? &rc : nullptr, nullptr) != 0) return -1;
+    if (parsy::plan_rcond(pl, pl->h_values_dev.data(), pl->h_L_dev.data(), &an, rcond ? &rc : nullptr, nullptr) != 0)
+        return -1;
     if (!timer.stop(seconds)) {
         set_last_error(std::string(who) + ": timing the call failed");
         return -1;
@@ -354,12 +351,12 @@ int parsy_selinv_host(parsy_plan* pl, const double* lValues, double* z, double* 
         return -1;
     }
     if (stage(pl, false, 0) != hipSuccess ||
-        parsy::grow_device(X.h_z, X.h_z_len, std::max<int64_t>(S.xsize, 1)) != hipSuccess ||
-        parsy::grow_device(X.h_diag, X.h_diag_len, std::max<int64_t>(S.n, 1)) != hipSuccess) {
+        X.h_z.grow(std::max<int64_t>(S.xsize, 1)) != hipSuccess ||
+        X.h_diag.grow(std::max<int64_t>(S.n, 1)) != hipSuccess) {
         set_last_error(std::string(who) + ": hipMalloc failed");
         return -1;
     }
-    if (hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice) != hipSuccess) {
         set_last_error(std::string(who) + ": upload failed");
         return -1;
     }
@@ -368,14 +365,14 @@ int parsy_selinv_host(parsy_plan* pl, const double* lValues, double* z, double* 
         set_last_error(std::string(who) + ": hipEventCreate failed");
         return -1;
     }
-    if (parsy_selinv_device(pl, pl->h_L_dev, X.h_z, nullptr) != 0) return -1;
-    if (diag && parsy_inverse_diag_device(pl, X.h_z, X.h_diag, nullptr) != 0) return -1;
+    if (parsy_selinv_device(pl, pl->h_L_dev.data(), X.h_z.data(), nullptr) != 0) return -1;
+    if (diag && parsy_inverse_diag_device(pl, X.h_z.data(), X.h_diag.data(), nullptr) != 0) return -1;
     if (!timer.stop(seconds)) {
         set_last_error(std::string(who) + ": timing the call failed");
         return -1;
     }
-    if (hipMemcpy(z, X.h_z, (size_t)S.xsize * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        (diag && S.n > 0 && hipMemcpy(diag, X.h_diag, (size_t)S.n * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+    if (hipMemcpy(z, X.h_z.data(), (size_t)S.xsize * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (diag && S.n > 0 && hipMemcpy(diag, X.h_diag.data(), (size_t)S.n * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
         set_last_error(std::string(who) + ": download failed");
         return -1;
     }
@@ -446,7 +443,7 @@ int parsy_factor_apply_host(parsy_plan* pl, const double* lValues, int op, const
     const int n = S.n;
     PARSY_HIP(hipSetDevice(pl->device));
     PARSY_HIP(stage(pl, false, 0));
-    PARSY_HIP(hipMemcpy(pl->h_L_dev, lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
     // X and Y with leading dimension n on the device; Y goes up only when it is read
     Scratch sc;
     const int64_t len = (int64_t)n * nrhs;
@@ -461,7 +458,8 @@ int parsy_factor_apply_host(parsy_plan* pl, const double* lValues, int op, const
         PARSY_HIP(hipMemcpy2D(d_x, row, x, (size_t)ldx * 8, row, nrhs, hipMemcpyHostToDevice));
         if (beta != 0.0) PARSY_HIP(hipMemcpy2D(d_y, row, y, (size_t)ldy * 8, row, nrhs, hipMemcpyHostToDevice));
     }
-    if (parsy_factor_apply_device(pl, pl->h_L_dev, op, d_x, std::max(n, 1), nrhs, alpha, beta, d_y, std::max(n, 1), nullptr) != 0)
+    if (parsy_factor_apply_device(pl, pl->h_L_dev.data(), op, d_x, std::max(n, 1), nrhs, alpha, beta, d_y, std::max(n, 1),
+                                  nullptr) != 0)
         return -1;
     if (!sc.timer.stop(seconds)) {
         set_last_error(std::string(who) + ": timing the call failed");

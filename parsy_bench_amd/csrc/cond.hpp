@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "device_buffer.hpp"
+
 struct parsy_plan;
 
 namespace parsy {
@@ -21,17 +23,17 @@ struct CondCol {
 };
 
 struct CondState {
-    double* ws = nullptr;          // w, the operand (n x nrhs each, leading dimension n)
-    int64_t ws_len = 0;            // doubles of ws
-    unsigned char* sgn = nullptr;  // the saved sign vector, a byte per row and column (the solve overwrites the operand)
-    int64_t sgn_len = 0;
-    char* cols = nullptr;          // partial maxima of |z| or of A's row sums (kRefinePartials x cap u64), CondCol[cap],
-    int64_t cols_len = 0;          // results (cap + 2 doubles)
+    explicit CondState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                      // parsy_cond_info.device_bytes: everything here, in the plan's figure too
+    DeviceBuf<double> ws{&meter};         // w, the operand (n x nrhs each, leading dimension n)
+    DeviceBuf<unsigned char> sgn{&meter}; // the saved sign vector, a byte per row and column (the solve overwrites the
+                                          // operand)
+    DeviceBuf<char> cols{&meter};         // partial maxima of |z| or of A's row sums (kRefinePartials x cap u64),
+                                          // CondCol[cap], results (cap + 2 doubles)
     int cols_cap = 0;
     int32_t applications = 0, columns = 0;   // of the last call
 };
 
-void cond_free(parsy_plan* pl);
 // FERR of the z the refinement workspace holds (pb, z and the gathered values as the last residual left them; ctl[1] of
 // its column state carries the status of the solves so far) into ferr (host, nrhs); synchronises stream.  `who` names
 // the call in a refusal.

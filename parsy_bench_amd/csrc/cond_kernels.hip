@@ -202,7 +202,7 @@ struct CondCols {
 
 CondCols cond_cols(CondState& C) {
     CondCols c;
-    char* p = C.cols;
+    char* p = C.cols.data();
     c.part = (u64*)p;
     p += (size_t)kRefinePartials * C.cols_cap * sizeof(u64);
     c.col = (CondCol*)p;
@@ -213,17 +213,16 @@ CondCols cond_cols(CondState& C) {
 
 // w, the operand and the signs (n x nrhs each) and the per-column state, grown on demand
 int ensure_cond(parsy_plan* pl, int nrhs) {
-    if (!pl->cond) pl->cond = new CondState;
+    if (!pl->cond) pl->cond = std::make_unique<CondState>(&pl->meter);
     CondState& C = *pl->cond;
     const int64_t nn = std::max<int64_t>((int64_t)pl->S.n * nrhs, 1);
     PARSY_HIP(hipSetDevice(pl->device));
-    if (grow_counted(pl, C.ws, C.ws_len, 2 * nn) != 0 || grow_counted(pl, C.sgn, C.sgn_len, nn) != 0) return -1;
+    PARSY_HIP(C.ws.grow(2 * nn));
+    PARSY_HIP(C.sgn.grow(nn));
     if (C.cols_cap < nrhs) {
         C.cols_cap = 0;
         static_assert(sizeof(CondCol) % 8 == 0, "the results behind the states are doubles");
-        if (grow_counted(pl, C.cols, C.cols_len,
-                         (int64_t)nrhs * (kRefinePartials * 8 + (int64_t)sizeof(CondCol) + 8) + 16) != 0)
-            return -1;
+        PARSY_HIP(C.cols.grow((int64_t)nrhs * (kRefinePartials * 8 + (int64_t)sizeof(CondCol) + 8) + 16));
         C.cols_cap = nrhs;
     }
     return 0;
@@ -240,13 +239,13 @@ int estimate(parsy_plan* pl, const char* who, const double* d_L, double* v, cons
     PARSY_HIP(hipMemsetAsync(c.col, 0, (size_t)ncols * sizeof(CondCol), stream));
     if (n == 0) return 0;   // (est = 0)
     PARSY_HIP(hipMemsetAsync(ctl, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_cond_step, dim3(ncols), dim3(kCThreads), 0, stream, v, w, C.sgn, c.col, n, ctl);
+    hipLaunchKernelGGL(k_cond_step, dim3(ncols), dim3(kCThreads), 0, stream, v, w, C.sgn.data(), c.col, n, ctl);
     PARSY_HIP(hipGetLastError());
     for (;;) {
         if (refine_solve_enqueue(pl, d_L, v, ncols, ctl, stream) != 0) return -1;
         C.applications += 1;
         PARSY_HIP(hipMemsetAsync(ctl, 0, sizeof(int), stream));
-        hipLaunchKernelGGL(k_cond_step, dim3(ncols), dim3(kCThreads), 0, stream, v, w, C.sgn, c.col, n, ctl);
+        hipLaunchKernelGGL(k_cond_step, dim3(ncols), dim3(kCThreads), 0, stream, v, w, C.sgn.data(), c.col, n, ctl);
         PARSY_HIP(hipGetLastError());
         int h[2] = {0, 0};
         PARSY_HIP(hipMemcpyAsync(h, ctl, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -262,24 +261,14 @@ int estimate(parsy_plan* pl, const char* who, const double* d_L, double* v, cons
 
 }  // namespace
 
-void cond_free(parsy_plan* pl) {
-    CondState* C = pl->cond;
-    if (!C) return;
-    if (pl->device >= 0)
-        for (void* p : {(void*)C->ws, (void*)C->sgn, (void*)C->cols})
-            if (p) (void)hipFree(p);
-    delete C;
-    pl->cond = nullptr;
-}
-
 int cond_bounds_phase(parsy_plan* pl, const char* who, const double* d_L, int nrhs, double* ferr, hipStream_t stream) {
     if (ensure_cond(pl, nrhs) != 0) return -1;
     RefineState& R = *pl->refine;
     CondState& C = *pl->cond;
     C.columns = nrhs;
     const int64_t nn = (int64_t)pl->S.n * nrhs;
-    const double *pb = R.ws, *z = R.ws + nn;
-    double *w = C.ws, *v = C.ws + std::max<int64_t>(nn, 1);
+    const double *pb = R.ws.data(), *z = pb + nn;
+    double *w = C.ws.data(), *v = w + std::max<int64_t>(nn, 1);
     const CondCols c = cond_cols(C);
     const int nb = sym_sweep_enqueue<WeightOut>(pl, z, pb, w, nrhs, c.part, stream);
     if (nb < 0) return -1;
@@ -302,7 +291,7 @@ int plan_error_bounds(parsy_plan* pl, const double* d_values, const double* d_L,
     if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, nrhs, &perm) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
-    double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
+    double *pb = R.ws.data(), *z = pb + nn, *r = pb + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
     PARSY_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
     if (refine_gather_values(pl, d_values, stream) != 0) return -1;
@@ -339,7 +328,7 @@ int plan_rcond(parsy_plan* pl, const double* d_values, const double* d_L, double
         hipLaunchKernelGGL(k_sym_norm1<decltype(g)::value>, dim3(nb), dim3(kCThreads), 0, stream, R.d_rp, R.d_vf, n, c.part);
     });
     PARSY_HIP(hipGetLastError());
-    if (rcond && estimate(pl, who, d_L, C.ws + std::max(n, 1), nullptr, 1, rc.ctl, stream) != 0) return -1;
+    if (rcond && estimate(pl, who, d_L, C.ws.data() + std::max(n, 1), nullptr, 1, rc.ctl, stream) != 0) return -1;
     hipLaunchKernelGGL(k_cond_finish, dim3(1), dim3(kCThreads), 0, stream, c.col, c.part, nb, c.out, 1);
     PARSY_HIP(hipGetLastError());
     double h[2] = {0, 0};
@@ -357,9 +346,9 @@ extern "C" int parsy_cond_get_info(parsy_plan* pl, parsy_cond_info* info) {
         parsy::set_last_error("parsy_cond_get_info: null argument");
         return -1;
     }
-    const parsy::CondState* C = pl->cond;
+    const parsy::CondState* C = pl->cond.get();
     info->applications = C ? C->applications : 0;
     info->columns = C ? C->columns : 0;
-    info->device_bytes = C ? C->ws_len * 8 + C->sgn_len + C->cols_len : 0;
+    info->device_bytes = C ? C->meter.bytes : 0;
     return 0;
 }

@@ -6,16 +6,14 @@
 #include <cstring>
 #include <stdexcept>
 
-#include "apply.hpp"
 #include "cond.hpp"
 #include "device_util.hpp"
 #include "errors.hpp"
-#include "grad.hpp"
 #include "hip_check.hpp"
 #include "plan_fwd.hpp"
 #include "plan_util.hpp"
 #include "refine.hpp"
-#include "selinv.hpp"
+#include "feature_states.hpp"
 
 namespace parsy {
 
@@ -46,13 +44,12 @@ int plan_set_perm(parsy_plan* pl, const int* perm) {
             seen[v] = 1;
         }
     }
-    if (pl->d_perm) {
+    if (pl->d_perm.data()) {
         (void)hipSetDevice(pl->device);
         (void)hipDeviceSynchronize();   // (a call may still read the old one)
-        (void)hipFree(pl->d_perm);
-        pl->device_bytes -= (int64_t)pl->perm.size() * 4;
-        pl->d_perm = nullptr;
+        (void)pl->d_perm.reset();
     }
+    pl->perm_on_device = false;
     pl->perm.swap(p);
     return 0;
 }
@@ -60,12 +57,12 @@ int plan_set_perm(parsy_plan* pl, const int* perm) {
 int plan_perm_device(parsy_plan* pl, const int** out) {
     *out = nullptr;
     if (pl->perm.empty()) return 0;
-    if (!pl->d_perm) {
-        PARSY_HIP(hipMalloc((void**)&pl->d_perm, pl->perm.size() * 4));
-        PARSY_HIP(hipMemcpy(pl->d_perm, pl->perm.data(), pl->perm.size() * 4, hipMemcpyHostToDevice));
-        pl->device_bytes += (int64_t)pl->perm.size() * 4;
+    if (!pl->perm_on_device) {
+        PARSY_HIP(pl->d_perm.grow((int64_t)pl->perm.size()));
+        PARSY_HIP(hipMemcpy(pl->d_perm.data(), pl->perm.data(), pl->perm.size() * 4, hipMemcpyHostToDevice));
+        pl->perm_on_device = true;
     }
-    *out = pl->d_perm;
+    *out = pl->d_perm.data();
     return 0;
 }
 
@@ -140,18 +137,15 @@ bool EventTimer::stop(double* seconds) {
 // a pattern or launch array of the plan: the plan owns the block (freed with the plan, or with the launch arrays)
 template <typename T>
 static int upload(parsy_plan* pl, const std::vector<T>& v, const T*& dptr, bool launch_array) {
-    T* d = nullptr;
-    const int rc = upload_counted(d, v, pl->device_bytes);
-    if (d) (launch_array ? pl->launch_owned : pl->owned).push_back(d);
-    dptr = rc == 0 ? d : nullptr;
-    return rc;
+    DevicePool& pool = launch_array ? pl->launches : pl->pattern;
+    dptr = pool.upload(v);
+    return dptr ? 0 : pool_failed(pool);
 }
 
 int plan_upload_launches(parsy_plan* pl) {
     if (pl->device < 0) return 0;
     PARSY_HIP(hipSetDevice(pl->device));
-    for (void* d : pl->launch_owned) (void)hipFree(d);
-    pl->launch_owned.clear();
+    pl->launches.clear();
     pl->levels_open = false;
     const Schedule& S = pl->S;
     if (upload(pl, S.small_list, pl->dp.small_list, true)) return -1;
@@ -167,10 +161,8 @@ int plan_upload_launches(parsy_plan* pl) {
     if (upload(pl, S.solve_wide_list, pl->dp.solve_wide_list, true)) return -1;
     if (upload(pl, S.bsolve_blocks, pl->dp.bsolve_blocks, true)) return -1;
     if (upload(pl, S.bsolve_below, pl->dp.bsolve_below, true)) return -1;
-    if (pl->dp.bpart) {   // (sized by the launch lists)
-        (void)hipFree(pl->dp.bpart);
-        pl->dp.bpart = nullptr;
-    }
+    (void)pl->bpart.reset();   // (sized by the launch lists)
+    pl->dp.bpart = nullptr;
     if (upload(pl, S.bsolve_pairs, pl->dp.bsolve_pairs, true)) return -1;
     if (upload(pl, S.sub_members, pl->dp.sub_members, true) || upload(pl, S.sub_trees, pl->dp.sub_trees, true) ||
         upload(pl, S.sub_slots, pl->dp.sub_slots, true) || upload(pl, S.sub_out_rows, pl->dp.sub_out_rows, true))
@@ -194,26 +186,16 @@ int plan_upload_launches(parsy_plan* pl) {
         // (the hand-off buffers are sized by the lists: made again by the next ONE-launch solve; the status word of the
         // last such solve lived in them)
         for (int d = 0; d < 2; ++d) {
-            if (pl->one_y[d]) {
-                (void)hipFree(pl->one_y[d]);
-                pl->device_bytes -= pl->one_bytes[d];
-            }
-            pl->one_y[d] = nullptr;
-            pl->one_bytes[d] = 0;
+            (void)pl->one_y[d].reset();
             pl->one_cap[d] = 0;
             pl->one_calls[d] = 0;
         }
         pl->solve_status_word = nullptr;
     }
-    {
-        void* d = nullptr;
-        PARSY_HIP(hipMalloc(&d, (size_t)std::max(S.n_chain_launches, 1) * sizeof(int)));
-        pl->launch_owned.push_back(d);
-        pl->dp.tickets = (int*)d;
-        PARSY_HIP(hipMalloc(&d, (size_t)std::max(S.n_solve_chain_launches, 1) * sizeof(int)));
-        pl->launch_owned.push_back(d);
-        pl->dp.stickets = (int*)d;
-    }
+    // (the tickets are not counted)
+    pl->dp.tickets = pl->launches.alloc<int>(std::max(S.n_chain_launches, 1), false);
+    pl->dp.stickets = pl->launches.alloc<int>(std::max(S.n_solve_chain_launches, 1), false);
+    if (pl->launches.error() != hipSuccess) return pool_failed(pl->launches);
     // hipMemcpy from pageable memory returns when the data is staged, hipMemset when it is enqueued:
     // both are only ordered against the NULL stream.  The caller's stream may be a non-blocking one,
     // so everything must have landed before the plan is handed out.
@@ -235,30 +217,17 @@ static int plan_upload(parsy_plan* pl) {
     if (upload(pl, S.wave_ptr, pl->dp.wave_ptr, false)) return -1;
     if (upload(pl, S.split_ranges, pl->dp.split_ranges, false)) return -1;
     {
-        void* d = nullptr;
-        const size_t sbytes = (size_t)std::max<int64_t>(S.n_split_doubles, 1) * sizeof(double);
-        PARSY_HIP(hipMalloc(&d, sbytes));
-        pl->owned.push_back(d);
-        pl->dp.tile_scratch = (double*)d;
-        pl->device_bytes += (int64_t)sbytes;
-    }
-    {
-        void* d = nullptr;
-        PARSY_HIP(hipMalloc(&d, sizeof(int)));
-        pl->owned.push_back(d);
-        pl->dp.info = (int*)d;
-        PARSY_HIP(hipMemset(d, 0x7f, sizeof(int)));
-        PARSY_HIP(hipMalloc(&d, sizeof(int)));
-        pl->owned.push_back(d);
-        pl->dp.sinfo = (int*)d;
-        PARSY_HIP(hipMemset(d, 0, sizeof(int)));
-        const size_t tbytes = 2 * std::max<int64_t>(S.n_tflags, 1) * sizeof(int);
+        DevicePool& P = pl->pattern;
+        const int64_t nflags = 2 * std::max<int64_t>(S.n_tflags, 1);
         pl->dp.n_tflags = (int)S.n_tflags;
-        PARSY_HIP(hipMalloc(&d, tbytes));
-        pl->owned.push_back(d);
-        pl->dp.tflags = (int*)d;
-        PARSY_HIP(hipMemset(d, 0, tbytes));
-        pl->device_bytes += (int64_t)tbytes;
+        pl->dp.tile_scratch = P.alloc<double>(std::max<int64_t>(S.n_split_doubles, 1));
+        pl->dp.tflags = P.alloc<int>(nflags);
+        pl->dp.info = P.alloc<int>(1, false);   // (the two status words are not counted)
+        pl->dp.sinfo = P.alloc<int>(1, false);
+        if (P.error() != hipSuccess) return pool_failed(P);
+        PARSY_HIP(hipMemset(pl->dp.info, 0x7f, sizeof(int)));
+        PARSY_HIP(hipMemset(pl->dp.sinfo, 0, sizeof(int)));
+        PARSY_HIP(hipMemset(pl->dp.tflags, 0, (size_t)nflags * sizeof(int)));
     }
     {
         // lowest priority: the side stream only fills what the main stream's chain leaves idle
@@ -316,20 +285,6 @@ void plan_free(parsy_plan* pl) {
     if (pl->device >= 0) {
         (void)hipSetDevice(pl->device);
         (void)hipDeviceSynchronize();
-        for (void* d : pl->owned) (void)hipFree(d);
-        for (void* d : pl->launch_owned) (void)hipFree(d);
-        if (pl->xscratch) (void)hipFree(pl->xscratch);
-        for (double*& q : pl->one_y) {   // (the state words live in the same allocations)
-            if (q) (void)hipFree(q);
-            q = nullptr;
-        }
-        if (pl->xt) (void)hipFree(pl->xt);
-        if (pl->d_perm) (void)hipFree(pl->d_perm);
-        if (pl->dinv) (void)hipFree(pl->dinv);
-        if (pl->dp.bpart) (void)hipFree(pl->dp.bpart);
-        if (pl->h_values_dev) (void)hipFree(pl->h_values_dev);
-        if (pl->h_L_dev) (void)hipFree(pl->h_L_dev);
-        if (pl->h_x_dev) (void)hipFree(pl->h_x_dev);
         for (hipEvent_t e : {pl->ev_f0, pl->ev_f1, pl->ev_s0, pl->ev_s1})
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : pl->pev) (void)hipEventDestroy(e);
@@ -341,12 +296,7 @@ void plan_free(parsy_plan* pl) {
         if (pl->h_copy) (void)hipStreamDestroy(pl->h_copy);
         for (hipEvent_t e : pl->h_band_ev) (void)hipEventDestroy(e);
     }
-    refine_free(pl);
-    selinv_free(pl);
-    grad_free(pl);
-    cond_free(pl);
-    apply_free(pl);
-    delete pl;
+    delete pl;   // (the pools, the buffers and the feature states free what they hold)
 }
 
 static void profile_mark(parsy_plan* pl, int kind, hipStream_t stream, size_t& cursor, int level = -1, int side = 0,
@@ -388,6 +338,7 @@ static void run_begin(parsy_plan* pl) {
 static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0, size_t i1, double* L,
                       const double* Lc, double* x, int nrhs, int ldx, hipStream_t stream) {
     size_t& cursor = pl->run_cursor;
+    double *const dinv = pl->dinv.data(), *const xscratch = pl->xscratch.data();
     // TILES_EARLY launches go to the side stream (unless profiling / disabled): they wait for the
     // completion event of the level two below their targets and run beside the main stream's
     // block-column chain; the matching TILES (late) launch waits for them.
@@ -444,23 +395,23 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                 break;
             case kLaunchSolvePanel:
                 if (l.fused && nrhs >= pl->dp.gates.chain_mrhs_min)
-                    launch_solve_blocks_mrhs(pl->dp, l.lds_bytes, l.wait_level, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx,
+                    launch_solve_blocks_mrhs(pl->dp, l.lds_bytes, l.wait_level, Lc, dinv, x, xscratch, nrhs, ldx,
                                              pl->solve_ldq, l.jb, pl->dp.gates.wait_bias, stream);
                 else if (l.fused)   // (one right-hand side: chain_mrhs_min is at most 2)
-                    launch_solve_chain(pl->dp, l.first, l.count, Lc, pl->dinv, x, pl->xscratch, l.jb, pl->dp.gates.wait_bias,
+                    launch_solve_chain(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, l.jb, pl->dp.gates.wait_bias,
                                        stream);
                 else
-                    launch_solve_panel(pl->dp, l.first, l.count, Lc, x, pl->xscratch, nrhs, ldx, stream);
+                    launch_solve_panel(pl->dp, l.first, l.count, Lc, x, xscratch, nrhs, ldx, stream);
                 break;
             case kLaunchSolveFixup:
-                launch_solve_fixup(pl->dp, l.first, l.count, x, pl->xscratch, nrhs, ldx, stream);
+                launch_solve_fixup(pl->dp, l.first, l.count, x, xscratch, nrhs, ldx, stream);
                 break;
             case kLaunchBackBelow:
                 if (nrhs == 1) launch_bsolve_below(pl->dp, l.first, l.count, Lc, x, stream);
                 break;
             case kLaunchBackBlock:
                 if (l.fused == 1 && nrhs == 1) {   // one right-hand side: the wave dataflow over block-column pairs
-                    launch_bsolve_chain_w(pl->dp, l.lds_bytes, l.wait_level, Lc, pl->dinv, x, pl->xscratch, l.jb,
+                    launch_bsolve_chain_w(pl->dp, l.lds_bytes, l.wait_level, Lc, dinv, x, xscratch, l.jb,
                                           pl->dp.gates.wait_bias, stream);
                     break;
                 }
@@ -468,7 +419,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                     launch_bsolve_sub_mrhs(pl->dp, pl->S.sub_tiers[0], Lc, x, nrhs, ldx, stream);
                     break;
                 }
-                launch_bsolve_block(pl->dp, l.first, l.count, Lc, pl->dinv, x, pl->xscratch, nrhs, ldx, l.fused,
+                launch_bsolve_block(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, nrhs, ldx, l.fused,
                                     l.early,
                                     l.fused == 1 ? l.jb : 0, pl->dp.gates.wait_bias, stream);
                 break;
@@ -522,38 +473,33 @@ static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream
     // slots -- and are made again, larger, when a wider block comes: earlier solves on the stream are complete by then)
     const int d = backward ? 1 : 0;
     const int want = nrhs == 1 ? 1 : nrhs <= 4 ? 4 : kOneMaxRhs;
-    if (want > pl->one_cap[d] && pl->one_y[d]) {
+    DeviceBuf<double>& buf = pl->one_y[d];
+    if (want > pl->one_cap[d] && buf.data()) {
         PARSY_HIP(hipStreamSynchronize(stream));
-        (void)hipFree(pl->one_y[d]);
-        pl->one_y[d] = nullptr;
-        pl->device_bytes -= pl->one_bytes[d];
-        pl->one_bytes[d] = 0;
+        (void)buf.reset();
         if (pl->solve_status_word) pl->solve_status_word = nullptr;
     }
-    if (!pl->one_y[d]) {
+    if (!buf.data()) {
         pl->one_cap[d] = std::max(pl->one_cap[d], want);
         const size_t len = (size_t)(backward ? pl->S.n : pl->dp.one_f.nslots) * pl->one_cap[d];
-        // (the two {status, ticket} pairs live behind the two buffers: one allocation)
-        const size_t bytes = 2 * len * sizeof(double) + 4 * sizeof(int);
-        if (hipMalloc((void**)&pl->one_y[d], bytes) != hipSuccess) {
+        // (the two {status, ticket} pairs, four ints, live behind the two buffers: one allocation)
+        static_assert(4 * sizeof(int) == 2 * sizeof(double), "the state words are counted as two doubles");
+        if (buf.grow((int64_t)(2 * len + 2)) != hipSuccess) {
             // no room for the hand-off buffers: this plan's solves of that direction go by the level launches from now on
             (void)hipGetLastError();
-            pl->one_y[d] = nullptr;
             pl->one_cap[d] = 0;
             (backward ? pl->one_off_back : pl->one_off) = true;
             return 1;
         }
-        pl->one_bytes[d] = (int64_t)bytes;
-        pl->device_bytes += (int64_t)bytes;
-        PARSY_HIP(solve_arm_handoff(pl->one_y[d], (int64_t)(2 * len), stream));
-        PARSY_HIP(hipMemsetAsync(pl->one_y[d] + 2 * len, 0, 4 * sizeof(int), stream));
+        PARSY_HIP(solve_arm_handoff(buf.data(), (int64_t)(2 * len), stream));
+        PARSY_HIP(hipMemsetAsync(buf.data() + 2 * len, 0, 4 * sizeof(int), stream));
         pl->one_calls[d] = 0;
     }
     const size_t len = (size_t)(backward ? pl->S.n : pl->dp.one_f.nslots) * pl->one_cap[d];
-    int* state = reinterpret_cast<int*>(pl->one_y[d] + 2 * len);
+    int* state = reinterpret_cast<int*>(buf.data() + 2 * len);
     const unsigned k = pl->one_calls[d]++ & 1u;
-    y = pl->one_y[d] + k * len;
-    y_next = pl->one_y[d] + (k ^ 1u) * len;
+    y = buf.data() + k * len;
+    y_next = buf.data() + (k ^ 1u) * len;
     st = state + 2 * k;
     st_next = state + 2 * (k ^ 1u);
     pl->solve_status_word = st;
@@ -593,21 +539,16 @@ static int solve_prologue(parsy_plan* pl, const double* d_L, int nrhs, int ldx, 
         PARSY_HIP(hipMemsetAsync(pl->dp.sinfo, 0, sizeof(int), stream));
         PARSY_HIP(hipMemsetAsync(pl->dp.stickets, 0, (size_t)ntickets * sizeof(int), stream));
     }
-    if (scratch > 0) PARSY_HIP(grow_device(pl->xscratch, pl->xscratch_len, scratch));
-    if (nwide > 0 && !pl->dinv) {
-        const size_t bytes = (size_t)std::max<int64_t>(S.n_dslots, 1) * kTile * kTile * sizeof(double);
-        PARSY_HIP(hipMalloc((void**)&pl->dinv, bytes));
-        pl->device_bytes += (int64_t)bytes;
-    }
+    if (scratch > 0) PARSY_HIP(pl->xscratch.grow(scratch));
+    if (nwide > 0 && !pl->dinv.data()) PARSY_HIP(pl->dinv.grow(std::max<int64_t>(S.n_dslots, 1) * kTile * kTile));
     if (bpart && nrhs == 1 && S.n_bpart_slots > 0 && !pl->dp.bpart) {
-        const size_t bytes = (size_t)S.n_bpart_slots * kTile * sizeof(double);
-        PARSY_HIP(hipMalloc((void**)&pl->dp.bpart, bytes));
-        pl->device_bytes += (int64_t)bytes;
+        PARSY_HIP(pl->bpart.grow((int64_t)S.n_bpart_slots * kTile));
+        pl->dp.bpart = pl->bpart.data();
     }
     PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-    if (arm_wide) launch_solve_arm_wide(pl->dp, nwide, pl->xscratch, nrhs, ldx, ldq, ntickets, stream);
-    else if (armed > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch, armed, stream));
-    launch_diag_inverse(pl->dp, nwide, d_L, pl->dinv, stream);
+    if (arm_wide) launch_solve_arm_wide(pl->dp, nwide, pl->xscratch.data(), nrhs, ldx, ldq, ntickets, stream);
+    else if (armed > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch.data(), armed, stream));
+    launch_diag_inverse(pl->dp, nwide, d_L, pl->dinv.data(), stream);
     return 0;
 }
 
@@ -864,7 +805,7 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
                         (S.xsize >= (int64_t)150 * S.n || G.xt_min_set);
     const int ldq = use_xt ? (nrhs + 15) & ~15 : 0;
     const int64_t need = use_xt ? (int64_t)S.n * ldq : (int64_t)ldx * nrhs;
-    if (use_xt) PARSY_HIP(grow_device(pl->xt, pl->xt_len, need));
+    if (use_xt) PARSY_HIP(pl->xt.grow(need));
     // The chain launches of the wide supernodes take the whole buffer armed -- k_solve_chain_w (one right-hand side),
     // k_solve_blocks_mrhs (from G.chain_mrhs_min on) --, or where it can (no fixup list) the latter's prologue launch,
     // k_solve_arm_wide, arms their columns and zeroes the status word and the tickets.
@@ -873,11 +814,14 @@ int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx
     const int64_t scratch = S.n_solve_wide > 0 ? need : 0;
     if (solve_prologue(pl, d_L, nrhs, ldx, ldq, scratch, false, arm_wide, scratch, stream) != 0) return -1;
     pl->solve_ldq = ldq;
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, S.n, nrhs, true, stream);
-    run_solve(pl, false, d_L, use_xt ? pl->xt : d_x, nrhs, ldx, stream);
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt, ldq, S.n, nrhs, false, stream);
+    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt.data(), ldq, S.n, nrhs, true, stream);
+    run_solve(pl, false, d_L, use_xt ? pl->xt.data() : d_x, nrhs, ldx, stream);
+    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt.data(), ldq, S.n, nrhs, false, stream);
     pl->solve_ldq = 0;
     return solve_end(pl, stream);
 }
 
 }  // namespace parsy
+
+// (here, where the feature states' types are complete)
+parsy_plan::~parsy_plan() = default;

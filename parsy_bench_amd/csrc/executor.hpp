@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/parsy_amd.h"
+#include "device_buffer.hpp"
 #include "kernels.hpp"
 #include "schedule.hpp"
 
@@ -27,31 +29,29 @@ struct parsy_plan {
     bool solve_only = false;  // built from L's pattern alone (no A, no update lists)
     bool sn_mask_set = false, piece_mask_set = false;  // parsy_plan_set_active / _set_active_pieces are in force
 
-    // pattern arrays (uploaded once) and launch arrays (re-uploaded by set_active)
-    std::vector<void*> owned;        // every hipMalloc'd block, for destroy()
-    std::vector<void*> launch_owned; // the launch-array blocks
+    // Device memory (device_buffer.hpp).  What is made with &meter is counted in parsy_plan_info.device_bytes; the
+    // feature states below hang their own meters under it.  dp holds the raw views the kernels receive.
+    parsy::ByteMeter meter;
+    parsy::DevicePool pattern{&meter};    // pattern arrays, flags and status words: made once
+    parsy::DevicePool launches{&meter};   // launch arrays and tickets: made again by set_active
     parsy::DevicePattern dp;
-    int64_t device_bytes = 0;
     int epoch = 0;            // factorization counter (value the Cholesky chain launches publish / wait for)
 
-    double* dinv = nullptr;       // inverse 64x64 diagonal blocks of the wide supernodes (solve)
-    double* xscratch = nullptr;
-    int64_t xscratch_len = 0;
+    parsy::DeviceBuf<double> dinv{&meter};    // inverse 64x64 diagonal blocks of the wide supernodes (solve)
+    parsy::DeviceBuf<double> bpart{&meter};   // dp.bpart: sized by the launch lists, reset with them
+    parsy::DeviceBuf<double> xscratch;        // (not counted)
     // ONE-launch solves (Schedule::solve_one): per direction two hand-off buffers (a solve works through the one its
     // predecessor armed and arms the other: no memset between solves) and two {status, ticket} pairs, used in turn
-    double* one_y[2] = {nullptr, nullptr};   // forward, backward: two buffers + the two state pairs behind them
+    // forward, backward: two buffers + the two state pairs behind them (four ints = two doubles)
+    parsy::DeviceBuf<double> one_y[2] = {parsy::DeviceBuf<double>(&meter), parsy::DeviceBuf<double>(&meter)};
     unsigned one_calls[2] = {0, 0};
     int one_cap[2] = {0, 0};                 // right-hand sides the buffers are made for (1, 4 or 8: grown on demand)
-    int64_t one_bytes[2] = {0, 0};           // ... and their share of device_bytes
     bool one_off = false, one_off_back = false;   // a direction whose buffers could not be allocated: level launches from then on
     const int* solve_status_word = nullptr;   // where the last solve left its status (null: dp.sinfo)
 
-    // buffers of the host-buffer calls (capi_hostcalls.hip) and their lengths in doubles: A's values, the factor, the
-    // right-hand sides; they live as long as the plan and are not counted in device_bytes
-    double* h_values_dev = nullptr;
-    double* h_L_dev = nullptr;
-    double* h_x_dev = nullptr;
-    int64_t h_values_len = 0, h_L_len = 0, h_x_len = 0;
+    // buffers of the host-buffer calls (capi_hostcalls.hip): A's values, the factor, the right-hand sides; they live as
+    // long as the plan and are not counted in device_bytes
+    parsy::DeviceBuf<double> h_values_dev, h_L_dev, h_x_dev;
     // host-buffer factorization with the download behind the kernels (parsy_factor_host): its own
     // streams, one event per band of levels, the (offset, length) runs of lValues that are final after each band
     hipStream_t h_stream = nullptr, h_copy = nullptr;
@@ -81,8 +81,8 @@ struct parsy_plan {
 
     // optional per-launch profiling (hipEvents on the launch stream)
     bool profile = false;
-    double* xt = nullptr;           // X with the right-hand sides of a row contiguous (forward solves with many of them)
-    int64_t xt_len = 0;
+    parsy::DeviceBuf<double> xt;    // X with the right-hand sides of a row contiguous (forward solves with many of them;
+                                    // not counted)
     int solve_ldq = 0;              // > 0: the running solve works on xt with this row stride
     std::vector<hipEvent_t> pev;
     std::vector<int> pev_kind;
@@ -94,14 +94,18 @@ struct parsy_plan {
     int kind_launches[PARSY_PROFILE_KINDS] = {};
     int profiled_runs = 0;
     // the caller's ordering (parsy_plan_set_perm; plan_util.hpp): perm[new] = old (empty: identity) and its device copy,
-    // uploaded by the first call that reads it (null: identity or not yet uploaded)
+    // uploaded by the first call that reads it
     std::vector<int> perm;
-    int* d_perm = nullptr;
-    parsy::RefineState* refine = nullptr;   // A x = b in the caller's ordering (refine.hpp): made by the first such call
-    parsy::SelinvState* selinv = nullptr;   // selected inversion / log-determinant (selinv.hpp): made by the first such call
-    parsy::GradState* grad = nullptr;       // gradients with respect to A's values (grad.hpp): made by the first such call
-    parsy::CondState* cond = nullptr;       // forward error bounds / condition estimate (cond.hpp): made by the first such call
-    parsy::ApplyState* apply = nullptr;     // the factor as an operator (apply.hpp): made by the first such call
+    parsy::DeviceBuf<int> d_perm{&meter};
+    bool perm_on_device = false;     // d_perm holds perm
+    // the states of the features, each made by the first call of its kind
+    std::unique_ptr<parsy::RefineState> refine;   // A x = b in the caller's ordering (refine.hpp)
+    std::unique_ptr<parsy::SelinvState> selinv;   // selected inversion / log-determinant (selinv.hpp)
+    std::unique_ptr<parsy::GradState> grad;       // gradients with respect to A's values (grad.hpp)
+    std::unique_ptr<parsy::CondState> cond;       // forward error bounds / condition estimate (cond.hpp)
+    std::unique_ptr<parsy::ApplyState> apply;     // the factor as an operator (apply.hpp)
+
+    ~parsy_plan();   // (executor.hip, where the state types are complete)
 };
 
 namespace parsy {

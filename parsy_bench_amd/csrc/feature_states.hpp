@@ -1,0 +1,71 @@
+// The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp: those headers
+// are read by host-only translation units too, these structs own device memory).  A plan holds each only once one of
+// the feature's device calls has run.
+#pragma once
+#include "apply.hpp"
+#include "device_buffer.hpp"
+#include "grad.hpp"
+#include "selinv.hpp"
+
+namespace parsy {
+
+// Device state of a plan (selinv_kernels.hip): made by the first selinv / logdet call.
+struct SelinvState {
+    explicit SelinvState(ByteMeter* plan) : meter(plan), diag_meter(plan) {}
+    // parsy_selinv_info.device_bytes is the map's and the scratch's share (meter); the diagonal's arrays are counted in
+    // the plan's figure only (diag_meter)
+    ByteMeter meter, diag_meter;
+    bool map_ready = false;          // set when the schedule and the whole map are on the device
+    SelinvSchedule X;
+    SelinvSplit sp;                  // (tiled_min < 0: the descriptors on the device are not those of a split)
+    DevicePool map{&meter};
+    int64_t *d_cb = nullptr, *d_mo = nullptr;
+    int32_t* d_gmap = nullptr;
+    SelinvBc* d_bcs = nullptr;
+    int32_t* d_tasks = nullptr;
+    int64_t task_cap = 0;            // (descriptor, tile) pairs d_tasks holds
+    DeviceBuf<double> d_scr{&meter}; // level scratch: T, Y and partial slots (64 x 64 doubles each)
+    bool used = false;               // a call has enqueued work that reads the descriptors / scratch
+    // log-determinant and diagonal: per column the offset of its diagonal entry, the reduction's partials and result
+    bool diag_ready = false;         // set when both arrays exist
+    DevicePool diag{&diag_meter};
+    int64_t* d_doff = nullptr;
+    double* d_lpart = nullptr;       // kLogParts sums, kLogParts first bad columns (as doubles), then the result pair
+    // buffers of parsy_selinv_host (capi_hostcalls.hip), plan-lifetime, not counted: Z and the diagonal
+    DeviceBuf<double> h_z, h_diag;
+};
+
+struct GradState {
+    explicit GradState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                 // parsy_grad_info.device_bytes: everything here, in the plan's figure too
+    bool built = false;
+    GradPattern P;                   // (row / col are released once they are on the device; offdiag stays)
+    bool on_device = false;          // set when both arrays are on the device
+    DevicePool pattern{&meter};
+    int32_t *d_row = nullptr, *d_col = nullptr;
+    DeviceBuf<double> ws{&meter};    // P lambda and P x with the right-hand sides of a row contiguous (2 n pitch doubles)
+    DeviceBuf<double> tpart{&meter}; // partial sums and results of parsy_trace_inverse_device
+    int last_lanes = 0;              // lanes per entry of the last sampled product (0: none yet, 1: the direct kernel)
+};
+
+struct ApplyState {
+    explicit ApplyState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                  // parsy_apply_info.device_bytes: everything here, in the plan's figure too
+    bool built = false;
+    ApplyIndex I;                     // (pos and the layout are released once they are on the device; the counts stay)
+    ApplyLayout A;
+    int64_t ws_need = 0;              // apply_workspace_len
+    int64_t n_l_tasks = 0, n_lt_tasks = 0;
+    bool on_device = false;           // set when the five arrays are on the device
+    DevicePool index{&meter};
+    int64_t* d_ptr = nullptr;
+    ApplyOcc* d_occ = nullptr;
+    ApplyTaskL* d_l_tasks = nullptr;
+    ApplyTaskLt* d_lt_tasks = nullptr;
+    ApplyCol* d_col = nullptr;
+    DeviceBuf<double> ws{&meter};     // T / partials + staged X of one block of columns
+    DeviceBuf<double> sol{&meter};    // n x nrhs operand of the inverse operators
+    int last_op = -1, last_launches = 0;
+};
+
+}  // namespace parsy

@@ -28,17 +28,6 @@ struct GradPattern {
 // false with `what` set when an entry lies outside its supernode's panel or above the diagonal
 bool build_grad_pattern(const Schedule& S, GradPattern& P, std::string& what);
 
-struct GradState {
-    bool built = false;
-    GradPattern P;                   // (row / col are released once they are on the device; offdiag stays)
-    int32_t *d_row = nullptr, *d_col = nullptr;
-    int64_t pattern_bytes = 0;
-    double* ws = nullptr;            // P lambda and P x with the right-hand sides of a row contiguous (2 n pitch doubles)
-    int64_t ws_len = 0;
-    double* tpart = nullptr;         // partial sums and results of parsy_trace_inverse_device
-    int64_t tpart_len = 0;
-    int last_lanes = 0;              // lanes per entry of the last sampled product (0: none yet, 1: the direct kernel)
-};
-void grad_free(parsy_plan* pl);
+struct GradState;   // the device state (feature_states.hpp)
 
 }  // namespace parsy

@@ -21,7 +21,7 @@
 #include "hip_check.hpp"
 #include "executor.hpp"
 #include "plan_util.hpp"
-#include "grad.hpp"
+#include "feature_states.hpp"
 
 namespace parsy {
 
@@ -151,7 +151,7 @@ __global__ void k_trace_final(const double* __restrict__ part, int nparts, int n
 }
 
 int ensure_host_pattern(parsy_plan* pl, const char* who) {
-    if (!pl->grad) pl->grad = new GradState;
+    if (!pl->grad) pl->grad = std::make_unique<GradState>(&pl->meter);
     GradState& G = *pl->grad;
     if (G.built) return 0;
     std::string what;
@@ -164,10 +164,13 @@ int ensure_device_pattern(parsy_plan* pl, const char* who) {
     if (ensure_host_pattern(pl, who) != 0) return -1;
     GradState& G = *pl->grad;
     PARSY_HIP(hipSetDevice(pl->device));
-    if (G.d_row) return 0;
-    if (upload_counted(G.d_row, G.P.row, G.pattern_bytes) != 0 || upload_counted(G.d_col, G.P.col, G.pattern_bytes) != 0)
-        return -1;
-    pl->device_bytes += G.pattern_bytes;
+    if (G.on_device) return 0;
+    DevicePool pool(&G.meter);
+    int32_t *d_row = pool.upload(G.P.row), *d_col = pool.upload(G.P.col);
+    if (pool.error() != hipSuccess) return pool_failed(pool);
+    G.pattern = std::move(pool);
+    G.d_row = d_row, G.d_col = d_col;
+    G.on_device = true;
     std::vector<int32_t>().swap(G.P.row);   // (the host copy has served; the counts stay)
     std::vector<int32_t>().swap(G.P.col);
     return 0;
@@ -178,16 +181,6 @@ unsigned capped_grid(int64_t items, int per_block) {
 }
 
 }  // namespace
-
-void grad_free(parsy_plan* pl) {
-    GradState* G = pl->grad;
-    if (!G) return;
-    if (pl->device >= 0)
-        for (void* p : {(void*)G->d_row, (void*)G->d_col, (void*)G->ws, (void*)G->tpart})
-            if (p) (void)hipFree(p);
-    delete G;
-    pl->grad = nullptr;
-}
 
 int plan_pattern_outer(parsy_plan* pl, const double* d_lam, int ldl, const double* d_x, int ldx, int nrhs, double alpha,
                        double beta, double* d_g, hipStream_t stream) {
@@ -225,14 +218,15 @@ int plan_pattern_outer(parsy_plan* pl, const double* d_lam, int ldl, const doubl
     if (nnz == 0) return 0;
     const int pitch = (nrhs + 7) & ~7;
     const int64_t half = (int64_t)n * pitch;
-    if (grow_counted(pl, G.ws, G.ws_len, 2 * half) != 0) return -1;
+    PARSY_HIP(G.ws.grow(2 * half));
+    double* const ws = G.ws.data();
     const unsigned ky = (unsigned)((nrhs + kStage - 1) / kStage);
     hipLaunchKernelGGL(k_pattern_stage, dim3((unsigned)((n + kStage - 1) / kStage), ky, 2), dim3(kGThreads), 0, stream, perm,
-                       d_lam, (int64_t)ldl, d_x, (int64_t)ldx, n, nrhs, pitch, G.ws);
+                       d_lam, (int64_t)ldl, d_x, (int64_t)ldx, n, nrhs, pitch, ws);
     const dim3 grid(capped_grid(nnz, kGThreads / L));
 #define G_MRHS(LL)                                                                                                    \
     if (L == LL)                                                                                                      \
-        hipLaunchKernelGGL(k_pattern_outer_mrhs<LL>, grid, dim3(kGThreads), 0, stream, G.d_row, G.d_col, G.ws, G.ws + half, \
+        hipLaunchKernelGGL(k_pattern_outer_mrhs<LL>, grid, dim3(kGThreads), 0, stream, G.d_row, G.d_col, ws, ws + half, \
                            pitch, nrhs, alpha, beta, d_g, nnz);
     G_MRHS(8) G_MRHS(16) G_MRHS(32) G_MRHS(64)
 #undef G_MRHS
@@ -263,11 +257,12 @@ int plan_trace_inverse(parsy_plan* pl, const double* d_z, const double* d_b, int
     if (ensure_device_pattern(pl, who) != 0) return -1;
     GradState& G = *pl->grad;
     const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>(kTraceParts, (nnz + kGThreads - 1) / kGThreads));
-    if (grow_counted(pl, G.tpart, G.tpart_len, (int64_t)nb * (nparts + 1)) != 0) return -1;
-    double* res = G.tpart + (int64_t)nb * nparts;
+    PARSY_HIP(G.tpart.grow((int64_t)nb * (nparts + 1)));
+    double* const tpart = G.tpart.data();
+    double* res = tpart + (int64_t)nb * nparts;
     hipLaunchKernelGGL(k_trace_part, dim3(nparts, nb), dim3(kGThreads), 0, stream, G.d_row, G.d_col, pl->dp.a_dst, d_z, d_b,
-                       ldb, nnz, G.tpart);
-    hipLaunchKernelGGL(k_trace_final, dim3((nb + 63) / 64), dim3(64), 0, stream, G.tpart, nparts, nb, res);
+                       ldb, nnz, tpart);
+    hipLaunchKernelGGL(k_trace_final, dim3((nb + 63) / 64), dim3(64), 0, stream, tpart, nparts, nb, res);
     PARSY_HIP(hipGetLastError());
     PARSY_HIP(hipMemcpyAsync(out, res, (size_t)nb * 8, hipMemcpyDeviceToHost, stream));
     PARSY_HIP(hipStreamSynchronize(stream));
@@ -292,7 +287,7 @@ int parsy_grad_get_info(parsy_plan* pl, parsy_grad_info* info) {
     const parsy::GradState& G = *pl->grad;
     info->entries = pl->S.nnzA;
     info->offdiag_entries = G.P.offdiag;
-    info->device_bytes = G.pattern_bytes + (G.ws_len + G.tpart_len) * 8;
+    info->device_bytes = G.meter.bytes;
     info->last_lanes = G.last_lanes;
     return 0;
 }

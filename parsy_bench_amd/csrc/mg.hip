@@ -18,6 +18,7 @@
 #include "executor.hpp"
 #include "inspector.hpp"
 #include "plan_fwd.hpp"
+#include "plan_util.hpp"
 
 using parsy::set_last_error;
 
@@ -26,26 +27,25 @@ struct parsy_mg {
     std::vector<int> device;
     std::vector<parsy_plan*> plan;
     parsy_dist* dist = nullptr;
+    std::vector<parsy::DevicePool> pool;     // per rank: its device memory (freed with the rank's device current)
     std::vector<double*> L, values;          // per rank, on its device
     std::vector<hipStream_t> stream;
     std::vector<std::vector<hipEvent_t>> level_done;   // [rank][level]
     std::vector<hipEvent_t> t0, t1;
     struct DevMsg { const int64_t* off = nullptr; const int32_t* len = nullptr; };
     std::vector<DevMsg> dmsg;                // per message, on the RECEIVER's device
-    std::vector<void*> owned;                // (device memory, freed with the matching device current)
-    std::vector<int> owned_dev;
     int64_t xsize = 0, nnzA = 0;
     bool have_values = false;
 };
 
 namespace {
 
-int upload(parsy_mg* mg, int dev, const void* host, size_t bytes, void** out) {
-    PARSY_HIP(hipSetDevice(dev));
-    void* d = nullptr;
-    PARSY_HIP(hipMalloc(&d, std::max<size_t>(bytes, 8)));
-    mg->owned.push_back(d);
-    mg->owned_dev.push_back(dev);
+// a copy of `bytes` bytes in the memory of rank r
+int upload(parsy_mg* mg, int r, const void* host, size_t bytes, void** out) {
+    PARSY_HIP(hipSetDevice(mg->device[(size_t)r]));
+    parsy::DevicePool& pool = mg->pool[(size_t)r];
+    char* d = pool.alloc<char>((int64_t)std::max<size_t>(bytes, 8));
+    if (!d) return parsy::pool_failed(pool);
     if (bytes) PARSY_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
     *out = d;
     return 0;
@@ -73,6 +73,7 @@ parsy_mg* parsy_mg_create(const parsy_symbolic* sym, int nranks, const int* devi
     parsy_mg* mg = new parsy_mg;
     mg->nranks = nranks;
     mg->device.assign(devices, devices + nranks);
+    mg->pool.resize((size_t)nranks);
     auto fail = [&]() -> parsy_mg* {
         parsy_mg_destroy(mg);
         return nullptr;
@@ -122,14 +123,12 @@ parsy_mg* parsy_mg_create(const parsy_symbolic* sym, int nranks, const int* devi
     mg->level_done.resize((size_t)nranks);
     for (int r = 0; r < nranks; ++r) {
         if (hipSetDevice(devices[r]) != hipSuccess) return fail();
-        void* d = nullptr;
-        if (hipMalloc(&d, (size_t)std::max<int64_t>(mg->xsize, 1) * sizeof(double)) != hipSuccess) {
+        parsy::DevicePool& pool = mg->pool[(size_t)r];
+        if (!(mg->L[(size_t)r] = pool.alloc<double>(std::max<int64_t>(mg->xsize, 1)))) {
             set_last_error("parsy_mg_create: out of device memory for the lValues of rank " + std::to_string(r));
             return fail();
         }
-        mg->L[(size_t)r] = (double*)d;
-        if (hipMalloc(&d, (size_t)std::max<int64_t>(mg->nnzA, 1) * sizeof(double)) != hipSuccess) return fail();
-        mg->values[(size_t)r] = (double*)d;
+        if (!(mg->values[(size_t)r] = pool.alloc<double>(std::max<int64_t>(mg->nnzA, 1)))) return fail();
         if (hipStreamCreateWithFlags(&mg->stream[(size_t)r], hipStreamNonBlocking) != hipSuccess) return fail();
         if (hipEventCreate(&mg->t0[(size_t)r]) != hipSuccess || hipEventCreate(&mg->t1[(size_t)r]) != hipSuccess) return fail();
         mg->level_done[(size_t)r].resize((size_t)D.nlevels);
@@ -140,8 +139,8 @@ parsy_mg* parsy_mg_create(const parsy_symbolic* sym, int nranks, const int* devi
     for (size_t m = 0; m < D.msgs.size(); ++m) {
         const parsy::DistMessage& M = D.msgs[m];
         void *o = nullptr, *l = nullptr;
-        if (upload(mg, devices[M.dst], M.off.data(), M.off.size() * sizeof(int64_t), &o) != 0) return fail();
-        if (upload(mg, devices[M.dst], M.len.data(), M.len.size() * sizeof(int32_t), &l) != 0) return fail();
+        if (upload(mg, M.dst, M.off.data(), M.off.size() * sizeof(int64_t), &o) != 0) return fail();
+        if (upload(mg, M.dst, M.len.data(), M.len.size() * sizeof(int32_t), &l) != 0) return fail();
         mg->dmsg[m].off = (const int64_t*)o;
         mg->dmsg[m].len = (const int32_t*)l;
     }
@@ -157,18 +156,13 @@ void parsy_mg_destroy(parsy_mg* mg) {
     for (int r = 0; r < mg->nranks; ++r) {
         (void)hipSetDevice(mg->device[(size_t)r]);
         (void)hipDeviceSynchronize();
-        if ((size_t)r < mg->L.size() && mg->L[(size_t)r]) (void)hipFree(mg->L[(size_t)r]);
-        if ((size_t)r < mg->values.size() && mg->values[(size_t)r]) (void)hipFree(mg->values[(size_t)r]);
+        mg->pool[(size_t)r].clear();
         if ((size_t)r < mg->stream.size() && mg->stream[(size_t)r]) (void)hipStreamDestroy(mg->stream[(size_t)r]);
         if ((size_t)r < mg->t0.size() && mg->t0[(size_t)r]) (void)hipEventDestroy(mg->t0[(size_t)r]);
         if ((size_t)r < mg->t1.size() && mg->t1[(size_t)r]) (void)hipEventDestroy(mg->t1[(size_t)r]);
         if ((size_t)r < mg->level_done.size())
             for (hipEvent_t e : mg->level_done[(size_t)r])
                 if (e) (void)hipEventDestroy(e);
-    }
-    for (size_t k = 0; k < mg->owned.size(); ++k) {
-        (void)hipSetDevice(mg->owned_dev[k]);
-        (void)hipFree(mg->owned[k]);
     }
     for (parsy_plan* pl : mg->plan) parsy_plan_destroy(pl);
     if (mg->dist) parsy_dist_destroy(mg->dist);

@@ -1,12 +1,11 @@
-// Host-side helpers of the files that work on a parsy_plan: the plan's refusals, the caller's ordering, device buffers
-// that grow or are uploaded with their bytes counted, and the event pair that times a host-buffer call.  The only copy of each; what is
-// no template is defined in executor.hip.
+// Host-side helpers of the files that work on a parsy_plan: the plan's refusals, the caller's ordering and the event
+// pair that times a host-buffer call.  The only copy of each, defined in executor.hip.  (Device memory is owned through
+// device_buffer.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <vector>
+#include <string>
 
 #include "executor.hpp"
 #include "hip_check.hpp"
@@ -34,40 +33,10 @@ void enqueue_perm_gather(const int* perm, const double* src, int64_t ld, double*
 void enqueue_perm_scatter(const int* perm, const double* src, double alpha, double beta, double* dst, int64_t ld, int n,
                           int nrhs, hipStream_t stream);
 
-// buf (len elements) made at least `need` elements long; the contents are not kept
-template <class T>
-hipError_t grow_device(T*& buf, int64_t& len, int64_t need) {
-    if (len >= need) return hipSuccess;
-    if (buf) {
-        const hipError_t e = hipFree(buf);
-        if (e != hipSuccess) return e;
-    }
-    buf = nullptr;
-    len = 0;
-    const hipError_t e = hipMalloc((void**)&buf, (size_t)need * sizeof(T));
-    if (e == hipSuccess) len = need;
-    return e;
-}
-
-// ... with its bytes counted in the plan's device_bytes
-template <class T>
-int grow_counted(parsy_plan* pl, T*& buf, int64_t& len, int64_t need) {
-    if (len >= need) return 0;
-    pl->device_bytes -= len * (int64_t)sizeof(T);
-    const hipError_t e = grow_device(buf, len, need);
-    pl->device_bytes += len * (int64_t)sizeof(T);
-    PARSY_HIP(e);
-    return 0;
-}
-
-// d = a new device copy of h (room for one element when h is empty); its bytes are added to `bytes`
-template <class T>
-int upload_counted(T*& d, const std::vector<T>& h, int64_t& bytes) {
-    const size_t b = std::max<size_t>(h.size(), 1) * sizeof(T);
-    PARSY_HIP(hipMalloc((void**)&d, b));
-    if (!h.empty()) PARSY_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    bytes += (int64_t)b;
-    return 0;
+// -1 with the failure of a DevicePool's alloc / upload (its error()) as the last error
+inline int pool_failed(const DevicePool& pool) {
+    set_last_error(std::string("device allocation: ") + hipGetErrorString(pool.error()));
+    return -1;
 }
 
 // The pair of events on the NULL stream that times the device work of one host-buffer call.

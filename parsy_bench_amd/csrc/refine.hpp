@@ -5,26 +5,30 @@
 
 #include <cstdint>
 
+#include "device_buffer.hpp"
+
 struct parsy_plan;
 
 namespace parsy {
 
 struct RefineState {
+    explicit RefineState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;          // everything here is counted, in the plan's figure too
     // both triangles of P A P' as CSR, built on first use from the A2 pattern the plan scatters (a_dst + L's rows):
     // row i holds its entries in ascending A2 order; src[e] is the A2 index of entry e, vf[e] = values[src[e]]
+    bool pattern_ready = false;   // set when the whole pattern is on the device: the fields down to d_vf are valid
     int64_t nnz_full = 0;
     int max_row = 0;          // most entries in a row of the full symmetric A
     int group = 0;            // lanes per row of k_sym_sweep with 1-4 right-hand sides (from the mean row length)
+    DevicePool pattern{&meter};
     int64_t* d_rp = nullptr;
     int* d_ci = nullptr;
     int* d_src = nullptr;
     double* d_vf = nullptr;
-    int64_t pattern_bytes = 0;
     // workspace: pb, z, r (n x nrhs each, leading dimension n) and the per-column state
-    double* ws = nullptr;
-    int64_t ws_len = 0;       // doubles of ws
-    char* colstate = nullptr; // berr bits partials (kPartials x nrhs u64), berr, lstres (nrhs doubles), active, steps (nrhs ints), ctl[2]
-    int64_t colstate_len = 0; // bytes of colstate
+    DeviceBuf<double> ws{&meter};
+    // berr bits partials (kPartials x nrhs u64), berr, lstres (nrhs doubles), active, steps (nrhs ints), ctl[2]
+    DeviceBuf<char> colstate{&meter};
     int colstate_cap = 0;     // right-hand sides colstate is made for
 };
 
@@ -55,7 +59,6 @@ int refine_report_berr(parsy_plan* pl, int nb, int nrhs, hipStream_t stream);
 // folded into ctl[1] on the device (-1: a hand-off wait timed out)
 int refine_solve_enqueue(parsy_plan* pl, const double* d_L, double* x, int nrhs, int* ctl, hipStream_t stream);
 
-void refine_free(parsy_plan* pl);
 int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
                   double* d_r, int ldr, int nrhs, double* berr, hipStream_t stream);
 // ferr (host, nrhs; may be null): the forward error bounds of the returned X (cond.hpp), taken from the z, pb and values

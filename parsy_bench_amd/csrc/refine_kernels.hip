@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kRThreads) void k_refine_state(const u64* __restric
 dim3 grid_nq(int n, int nrhs) { return dim3((unsigned)((n + kRThreads - 1) / kRThreads), (unsigned)nrhs); }
 
 RefineState& state(parsy_plan* pl) {
-    if (!pl->refine) pl->refine = new RefineState;
+    if (!pl->refine) pl->refine = std::make_unique<RefineState>(&pl->meter);
     return *pl->refine;
 }
 
@@ -109,7 +109,7 @@ RefineState& state(parsy_plan* pl) {
 
 ColState col_state(RefineState& R, int cap) {
     ColState c;
-    char* p = R.colstate;
+    char* p = R.colstate.data();
     c.part = (u64*)p;
     p += (size_t)kRefinePartials * cap * sizeof(u64);
     c.berr = (double*)p;
@@ -128,7 +128,7 @@ ColState col_state(RefineState& R, int cap) {
 // scatters it: a_dst[q] = px + (col - c0) * r + (position of row in the supernode's row list).
 int refine_ensure_pattern(parsy_plan* pl) {
     RefineState& R = state(pl);
-    if (R.d_rp) return 0;
+    if (R.pattern_ready) return 0;
     const Schedule& S = pl->S;
     const int n = S.n;
     std::vector<int> arow((size_t)S.nnzA), acol((size_t)S.nnzA);
@@ -161,18 +161,19 @@ int refine_ensure_pattern(parsy_plan* pl) {
             src[fill[col]++] = (int)q;
         }
     }
+    PARSY_HIP(hipSetDevice(pl->device));
+    DevicePool pool(&R.meter);
+    int64_t* d_rp = pool.upload(rp);
+    int *d_ci = pool.upload(ci), *d_src = pool.upload(src);
+    double* d_vf = pool.alloc<double>((int64_t)ci.size());
+    if (pool.error() != hipSuccess) return pool_failed(pool);
+    R.pattern = std::move(pool);
+    R.d_rp = d_rp, R.d_ci = d_ci, R.d_src = d_src, R.d_vf = d_vf;
     R.nnz_full = nf;
     R.max_row = max_row;
     const double mean = n > 0 ? (double)nf / n : 0;
     R.group = mean > 24 ? 32 : mean > 12 ? 16 : mean > 6 ? 8 : 4;
-    PARSY_HIP(hipSetDevice(pl->device));
-    int64_t bytes = 0;
-    if (upload_counted(R.d_rp, rp, bytes) != 0 || upload_counted(R.d_ci, ci, bytes) != 0 ||
-        upload_counted(R.d_src, src, bytes) != 0)
-        return -1;
-    PARSY_HIP(hipMalloc((void**)&R.d_vf, ci.size() * 8));
-    R.pattern_bytes = bytes + (int64_t)ci.size() * 8;
-    pl->device_bytes += R.pattern_bytes;
+    R.pattern_ready = true;
     return 0;
 }
 
@@ -181,11 +182,10 @@ int refine_ensure_workspace(parsy_plan* pl, int nrhs, const int** perm) {
     RefineState& R = state(pl);
     const int64_t need = 3 * (int64_t)pl->S.n * nrhs;
     PARSY_HIP(hipSetDevice(pl->device));
-    if (grow_counted(pl, R.ws, R.ws_len, need) != 0) return -1;
+    PARSY_HIP(R.ws.grow(need));
     if (R.colstate_cap < nrhs) {
         R.colstate_cap = 0;
-        if (grow_counted(pl, R.colstate, R.colstate_len, (int64_t)nrhs * (kRefinePartials * 8 + 8 + 8 + 4 + 4) + 8) != 0)
-            return -1;
+        PARSY_HIP(R.colstate.grow((int64_t)nrhs * (kRefinePartials * 8 + 8 + 8 + 4 + 4) + 8));
         R.colstate_cap = nrhs;
     }
     return plan_perm_device(pl, perm);
@@ -228,18 +228,6 @@ int refine_report_berr(parsy_plan* pl, int nb, int nrhs, hipStream_t stream) {
     return 0;
 }
 
-void refine_free(parsy_plan* pl) {
-    RefineState* R = pl->refine;
-    if (!R) return;
-    if (pl->device >= 0) {
-        for (void* p : {(void*)R->d_rp, (void*)R->d_ci, (void*)R->d_src, (void*)R->d_vf, (void*)R->ws,
-                        (void*)R->colstate})
-            if (p) (void)hipFree(p);
-    }
-    delete R;
-    pl->refine = nullptr;
-}
-
 int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int ldx, const double* d_b, int ldb,
                   double* d_r, int ldr, int nrhs, double* berr, hipStream_t stream) {
     const char* who = "parsy_residual_device";
@@ -251,7 +239,7 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
     if (refine_ensure_pattern(pl) != 0 || refine_ensure_workspace(pl, nrhs, &perm) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
-    double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
+    double *pb = R.ws.data(), *z = pb + nn, *r = pb + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
     if (refine_gather_values(pl, d_values, stream) != 0) return -1;
     enqueue_perm_gather(perm, d_x, ldx, z, nullptr, n, nrhs, stream);
@@ -283,7 +271,7 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
     if ((residuals && refine_ensure_pattern(pl) != 0) || refine_ensure_workspace(pl, nrhs, &perm) != 0) return -1;
     RefineState& R = *pl->refine;
     const int64_t nn = (int64_t)n * nrhs;
-    double *pb = R.ws, *z = R.ws + nn, *r = R.ws + 2 * nn;
+    double *pb = R.ws.data(), *z = pb + nn, *r = pb + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
     PARSY_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
     enqueue_perm_gather(perm, d_b, ldb, pb, z, n, nrhs, stream);

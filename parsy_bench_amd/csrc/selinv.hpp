@@ -70,29 +70,7 @@ void split_selinv(const Schedule& S, const SelinvSchedule& X, int tiled_min, Sel
 int64_t check_selinv(const Schedule& S, const SelinvSchedule& X, const SelinvSplit& sp, std::string& what);
 int selinv_tiled_min();   // PARSY_SELINV_TILED_MIN, read at every call (default kSelinvTiledMin)
 
-// Device state of a plan (selinv_kernels.hip): made by the first selinv / logdet call.
-struct SelinvState {
-    bool map_ready = false;
-    SelinvSchedule X;
-    SelinvSplit sp;
-    int64_t *d_cb = nullptr, *d_mo = nullptr;
-    int32_t* d_gmap = nullptr;
-    SelinvBc* d_bcs = nullptr;
-    int32_t* d_tasks = nullptr;
-    int64_t task_cap = 0;            // (descriptor, tile) pairs d_tasks holds
-    double* d_scr = nullptr;         // level scratch: T, Y and partial slots (64 x 64 doubles each)
-    int64_t scr_len = 0;             // doubles of d_scr
-    int64_t map_bytes = 0;
-    bool used = false;               // a call has enqueued work that reads the descriptors / scratch
-    // log-determinant and diagonal: per column the offset of its diagonal entry, the reduction's partials and result
-    int64_t* d_doff = nullptr;
-    double* d_lpart = nullptr;       // kLogParts sums, kLogParts first bad columns (as doubles), then the result pair
-    int64_t diag_bytes = 0;
-    // buffers of parsy_selinv_host (capi_hostcalls.hip), plan-lifetime, not counted: Z and the diagonal
-    double *h_z = nullptr, *h_diag = nullptr;
-    int64_t h_z_len = 0, h_diag_len = 0;
-};
+struct SelinvState;   // the device state (feature_states.hpp)
 SelinvState& selinv_state(parsy_plan* pl);   // (made on first use)
-void selinv_free(parsy_plan* pl);
 
 }  // namespace parsy

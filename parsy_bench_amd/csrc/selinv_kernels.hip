@@ -27,7 +27,7 @@
 #include "hip_check.hpp"
 #include "executor.hpp"
 #include "plan_util.hpp"
-#include "selinv.hpp"
+#include "feature_states.hpp"
 
 namespace parsy {
 
@@ -394,18 +394,19 @@ __global__ void k_logdet_final(double* __restrict__ part, int nparts) {
 // per column the offset of its diagonal entry, and the log-determinant's partials
 int ensure_diag(parsy_plan* pl) {
     SelinvState& X = selinv_state(pl);
-    if (X.d_doff) return 0;
+    if (X.diag_ready) return 0;
     const Schedule& S = pl->S;
     std::vector<int64_t> doff((size_t)S.n);
     for (int s = 0; s < S.nsuper; ++s)
         for (int q = 0; q < S.sn[s].w; ++q) doff[S.sn[s].c0 + q] = S.sn[s].px + (int64_t)q * S.sn[s].r + q;
     PARSY_HIP(hipSetDevice(pl->device));
-    int64_t bytes = 0;
-    if (upload_counted(X.d_doff, doff, bytes) != 0) return -1;
-    PARSY_HIP(hipMalloc((void**)&X.d_lpart, (2 * kLogParts + 2) * sizeof(double)));
-    bytes += (2 * kLogParts + 2) * sizeof(double);
-    X.diag_bytes = bytes;
-    pl->device_bytes += bytes;
+    DevicePool pool(&X.diag_meter);
+    int64_t* d_doff = pool.upload(doff);
+    double* d_lpart = pool.alloc<double>(2 * kLogParts + 2);
+    if (pool.error() != hipSuccess) return pool_failed(pool);
+    X.diag = std::move(pool);
+    X.d_doff = d_doff, X.d_lpart = d_lpart;
+    X.diag_ready = true;
     return 0;
 }
 
@@ -415,33 +416,38 @@ int ensure_selinv(parsy_plan* pl) {
     PARSY_HIP(hipSetDevice(pl->device));
     if (!X.map_ready) {
         std::string what;
-        if (!build_selinv(pl->S, X.X, what)) return set_last_error("parsy_selinv_device: " + what), -1;
-        int64_t bytes = 0;
-        if (upload_counted(X.d_cb, X.X.cb, bytes) != 0 || upload_counted(X.d_mo, X.X.mo, bytes) != 0 ||
-            upload_counted(X.d_gmap, X.X.gmap, bytes) != 0)
-            return -1;
-        PARSY_HIP(hipMalloc((void**)&X.d_bcs, std::max(X.X.nbc, 1) * sizeof(SelinvBc)));
-        bytes += std::max(X.X.nbc, 1) * sizeof(SelinvBc);
-        for (int b = 0; b < X.X.nbc; ++b) {
-            const SnDesc& d = pl->S.sn[X.X.bc_sn[b]];
-            const int j0 = X.X.bc_j[b] * kTile;
-            X.task_cap += (d.r - j0 - std::min(kTile, d.w - j0) + kTile - 1) / kTile;
+        SelinvSchedule sched;
+        if (!build_selinv(pl->S, sched, what)) return set_last_error("parsy_selinv_device: " + what), -1;
+        int64_t task_cap = 0;
+        for (int b = 0; b < sched.nbc; ++b) {
+            const SnDesc& d = pl->S.sn[sched.bc_sn[b]];
+            const int j0 = sched.bc_j[b] * kTile;
+            task_cap += (d.r - j0 - std::min(kTile, d.w - j0) + kTile - 1) / kTile;
         }
-        PARSY_HIP(hipMalloc((void**)&X.d_tasks, std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t)));
-        bytes += std::max<int64_t>(2 * X.task_cap, 1) * sizeof(int32_t);
-        X.map_bytes = bytes;
-        pl->device_bytes += bytes;
+        DevicePool pool(&X.meter);
+        int64_t *d_cb = pool.upload(sched.cb), *d_mo = pool.upload(sched.mo);
+        int32_t* d_gmap = pool.upload(sched.gmap);
+        SelinvBc* d_bcs = pool.alloc<SelinvBc>(std::max(sched.nbc, 1));
+        int32_t* d_tasks = pool.alloc<int32_t>(std::max<int64_t>(2 * task_cap, 1));
+        if (pool.error() != hipSuccess) return pool_failed(pool);
+        X.map = std::move(pool);
+        X.X = std::move(sched);
+        X.d_cb = d_cb, X.d_mo = d_mo, X.d_gmap = d_gmap, X.d_bcs = d_bcs, X.d_tasks = d_tasks;
+        X.task_cap = task_cap;
         X.map_ready = true;
     }
     const int tmin = selinv_tiled_min();
     if (X.sp.tiled_min != tmin) {
         if (X.used) PARSY_HIP(hipDeviceSynchronize());   // (an earlier call may still read the descriptors and the scratch)
+        // (the split counts as made only when its descriptors and the scratch are on the device)
         split_selinv(pl->S, X.X, tmin, X.sp);
+        X.sp.tiled_min = -1;
         if (!X.sp.bcs.empty())
             PARSY_HIP(hipMemcpy(X.d_bcs, X.sp.bcs.data(), X.sp.bcs.size() * sizeof(SelinvBc), hipMemcpyHostToDevice));
         if (!X.sp.tasks.empty())
             PARSY_HIP(hipMemcpy(X.d_tasks, X.sp.tasks.data(), X.sp.tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (grow_counted(pl, X.d_scr, X.scr_len, X.sp.scratch_slots * kSlot) != 0) return -1;
+        PARSY_HIP(X.d_scr.grow(X.sp.scratch_slots * kSlot));
+        X.sp.tiled_min = tmin;
     }
     return 0;
 }
@@ -449,20 +455,8 @@ int ensure_selinv(parsy_plan* pl) {
 }  // namespace
 
 SelinvState& selinv_state(parsy_plan* pl) {
-    if (!pl->selinv) pl->selinv = new SelinvState;
+    if (!pl->selinv) pl->selinv = std::make_unique<SelinvState>(&pl->meter);
     return *pl->selinv;
-}
-
-void selinv_free(parsy_plan* pl) {
-    SelinvState* X = pl->selinv;
-    if (!X) return;
-    if (pl->device >= 0) {
-        for (void* p : {(void*)X->d_cb, (void*)X->d_mo, (void*)X->d_gmap, (void*)X->d_bcs, (void*)X->d_tasks,
-                        (void*)X->d_scr, (void*)X->d_doff, (void*)X->d_lpart, (void*)X->h_z, (void*)X->h_diag})
-            if (p) (void)hipFree(p);
-    }
-    delete X;
-    pl->selinv = nullptr;
 }
 
 int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stream) {
@@ -474,17 +468,18 @@ int plan_selinv(parsy_plan* pl, const double* d_L, double* d_z, hipStream_t stre
     SelinvState& X = *pl->selinv;
     const SelinvSplit& sp = X.sp;
     X.used = true;
+    double* const scr = X.d_scr.data();
     for (int l = 0; l < X.X.levels; ++l) {
         const int d0 = sp.lvl_bc[l], nt = sp.lvl_ntiled[l], nsm = sp.lvl_bc[l + 1] - d0 - nt;
         const int t0 = sp.lvl_task[l], ntask = sp.lvl_task[l + 1] - t0;
-        if (nt > 0) hipLaunchKernelGGL(k_selinv_tinv, dim3(nt), dim3(64), 0, stream, X.d_bcs, d0, d_L, X.d_scr);
+        if (nt > 0) hipLaunchKernelGGL(k_selinv_tinv, dim3(nt), dim3(64), 0, stream, X.d_bcs, d0, d_L, scr);
         if (ntask > 0) {
             hipLaunchKernelGGL(k_selinv_y, dim3(ntask), dim3(kSThreads), 0, stream, X.d_bcs, X.d_tasks + 2 * t0, d_L,
-                               X.d_scr);
+                               scr);
             hipLaunchKernelGGL(k_selinv_z, dim3(ntask), dim3(kSThreads), 0, stream, X.d_bcs, X.d_tasks + 2 * t0,
-                               X.d_cb, X.d_mo, X.d_gmap, d_z, X.d_scr);
+                               X.d_cb, X.d_mo, X.d_gmap, d_z, scr);
         }
-        if (nt > 0) hipLaunchKernelGGL(k_selinv_zbb, dim3(nt), dim3(kSThreads), 0, stream, X.d_bcs, d0, X.d_scr, d_z);
+        if (nt > 0) hipLaunchKernelGGL(k_selinv_zbb, dim3(nt), dim3(kSThreads), 0, stream, X.d_bcs, d0, scr, d_z);
         if (nsm > 0)
             hipLaunchKernelGGL(k_selinv_small, dim3(nsm), dim3(kSThreads), 0, stream, X.d_bcs, d0 + nt, d_L, X.d_cb,
                                X.d_mo, X.d_gmap, d_z);
@@ -554,7 +549,7 @@ int parsy_selinv_get_info(parsy_plan* pl, parsy_selinv_info* info) {
     info->tiled_block_columns = sp.ntiled;
     info->launches = sp.launches;
     info->flops = X->flops;
-    info->device_bytes = pl->selinv ? pl->selinv->map_bytes + pl->selinv->scr_len * 8 : 0;
+    info->device_bytes = pl->selinv ? pl->selinv->meter.bytes : 0;
     return 0;
 }
 

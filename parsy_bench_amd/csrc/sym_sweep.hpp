@@ -164,14 +164,14 @@ int sym_sweep_enqueue(parsy_plan* pl, const double* z, const double* pb, double*
     // stage z with the right-hand sides of a row contiguous in the plan's xt (the forward solves' staging buffer: a
     // solve fills it afresh, the sweep runs between solves)
     const int ldq = (nrhs + 15) & ~15;
-    PARSY_HIP(grow_device(pl->xt, pl->xt_len, (int64_t)n * ldq));
-    launch_transpose_x(const_cast<double*>(z), n, pl->xt, ldq, n, nrhs, true, stream);
+    PARSY_HIP(pl->xt.grow((int64_t)n * ldq));
+    launch_transpose_x(const_cast<double*>(z), n, pl->xt.data(), ldq, n, nrhs, true, stream);
     const int L = nrhs <= 8 ? 8 : nrhs <= 16 ? 16 : nrhs <= 32 ? 32 : 64;
     const int nb = sym_sweep_blocks(n, kRefineThreads / L);
     const dim3 grid(nb, (nrhs + L - 1) / L);
     dispatch_int(L, std::integer_sequence<int, 8, 16, 32, 64>(), [&](auto l) {
         hipLaunchKernelGGL((k_sym_sweep_mrhs<decltype(l)::value, Out>), grid, threads, 0, stream, R.d_rp, R.d_ci, R.d_vf,
-                           pl->xt, ldq, pb, dst, n, nrhs, out, part);
+                           pl->xt.data(), ldq, pb, dst, n, nrhs, out, part);
     });
     PARSY_HIP(hipGetLastError());
     return nb;

@@ -117,3 +117,77 @@ def test_families_share_one_plan(api, monkeypatch, name):
     finally:
         for p in plans:
             p.close()
+
+
+@pytest.mark.parametrize("restrict", ["set_active", "set_active_pieces"])
+def test_byte_count_does_not_drift_with_set_active(api, restrict):
+    """parsy_plan_set_active / _set_active_pieces make the launch arrays again; the plan's device_bytes must take the old
+    ones off before it adds the new ones.  A mask that drops the last supernode (piece), then no mask, three times: after
+    every pair a solve brings the count back to exactly what it was after the first factor and solve, and gives the
+    same solution.  (Before device memory was owned through device_buffer.hpp this failed: every call added the launch
+    arrays and the backward partial sums again and took nothing off.)
+
+    Between the pair and the solve the count is lower by the solves' hand-off buffers, which are sized by the launch
+    lists, released with them and made again by the next solve: that idle count is the same after every pair, and
+    equals the first count on a plan whose solves use no such buffers."""
+    A, perm, sym = problem("tiny2d")
+    rng = np.random.default_rng(7)
+    b1 = rng.standard_normal(sym.n)
+    plan = _plan(api, sym)
+    try:
+        lv, _ = plan.factor(sym.A2x)
+        assert plan.status() == 0
+        x0, _ = plan.solve(lv, b1)
+        b = plan.info["device_bytes"]
+        count = sym.nsuper if restrict == "set_active" else len(plan.pieces()["supernode"])
+        mask = np.ones(count, dtype=np.uint8)
+        mask[-1] = 0
+        idle = []
+        for k in range(3):
+            getattr(plan, restrict)(mask)
+            getattr(plan, restrict)(None)
+            idle.append(plan.info["device_bytes"])
+            x, _ = plan.solve(lv, b1)
+            now = plan.info["device_bytes"]
+            print(f"{restrict} round {k}: before {b}, after the pair {idle[-1]}, after a solve {now}")
+            assert now == b, f"round {k}: device_bytes {now} after the pair and a solve, {b} before"
+            _same(x, x0, f"round {k}: solve after {restrict}")
+        assert idle[0] <= b and idle == [idle[0]] * 3, (b, idle)
+    finally:
+        plan.close()
+
+
+def test_byte_counts_follow_growth(api):
+    """Workspaces that grow are made again at exactly the size asked for, and the meters follow: after solve_refined with
+    1, 3 and 1 right-hand sides, factor_apply(G) with 2 and 9 and rcond, the plan's count and every feature's equal
+    those of a fresh plan that makes only the widest call of each family."""
+    A, perm, sym = problem("small3d")
+    n = sym.n
+    rng = np.random.default_rng(11)
+    B = rng.standard_normal((n, 9))
+
+    def counts(p):
+        return {"plan": p.info["device_bytes"], "selinv": p.selinv_info["device_bytes"],
+                "grad": p.grad_info["device_bytes"], "cond": p.cond_info["device_bytes"],
+                "apply": p.apply_info["device_bytes"]}
+
+    plans = [_plan(api, sym), _plan(api, sym)]
+    grown, widest = plans
+    try:
+        lv, _ = grown.factor(sym.A2x)
+        assert grown.status() == 0
+        for k in (1, 3, 1):
+            grown.solve_refined(sym.A2x, lv, B[:, :k])
+        for k in (2, 9):
+            grown.factor_apply(lv, B[:, :k], "G")
+        grown.rcond(sym.A2x, lv)
+        widest.factor(sym.A2x)
+        widest.solve_refined(sym.A2x, lv, B[:, :3])
+        widest.factor_apply(lv, B, "G")
+        widest.rcond(sym.A2x, lv)
+        print("grown", counts(grown), "widest", counts(widest))
+        assert counts(grown) == counts(widest)
+        assert counts(grown)["plan"] > 0 and counts(grown)["cond"] > 0 and counts(grown)["apply"] > 0
+    finally:
+        for p in plans:
+            p.close()
