@@ -160,6 +160,9 @@ typedef struct parsy_plan_info {
     int32_t sub_mrhs_cover_level;  /* ... which replace every level launch up to this etree level (-1: only the subtree launch) */
     int64_t dense_strip_entries;   /* dense entries that carry the remainder of their source's row / column run (<= 16 rows behind
                                     * or beside the block), multiplied with the block's staged operands */
+    int32_t split_tiles;           /* tiles whose early wave stream is split: separate workgroups apply its parts to partial tiles
+                                    * (tile scratch), summed in a fixed order when the chain launch loads the tile */
+    int32_t split_parts;           /* ... and the sum of their parts (>= 2 each) */
 } parsy_plan_info;
 
 /* Build a plan from the reference-shaped symbolic arrays (host pointers, copied).
@@ -532,8 +535,9 @@ const char* parsy_last_error(void);
 int parsy_device_count(void);
 
 /* ---- Diagnostics: kernel witness ------------------------------------------------------------------------
- * One host-side counter per solve kernel instantiation that the library can enqueue (process-wide, every plan and
- * device), incremented when a launch of it is enqueued.  Tests use it to prove which kernels a solve ran.
+ * One host-side counter per factor and solve kernel instantiation that the library can enqueue (process-wide, every
+ * plan and device), incremented when a launch of it is enqueued.  Tests use it to prove which kernels a factorization
+ * or a solve ran.
  * Entries 0 .. parsy_debug_kernel_count() - 1; the name is the kernel's, template arguments included (for example
  * "k_solve_small_mrhs<64,true>"; NULL out of range). */
 int parsy_debug_kernel_count(void);

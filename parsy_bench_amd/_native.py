@@ -61,6 +61,7 @@ class PlanInfo(C.Structure):
         ("sub_mrhs_trees", C.c_int32), ("sub_mrhs_slots", C.c_int32),
         ("sub_mrhs_tiers", C.c_int32), ("sub_mrhs_cover_level", C.c_int32),
         ("dense_strip_entries", C.c_int64),
+        ("split_tiles", C.c_int32), ("split_parts", C.c_int32),
     ]
 
     def as_dict(self):

@@ -358,6 +358,11 @@ int parsy_plan_get_info(const parsy_plan* pl, parsy_plan_info* o) {
     o->sub_mrhs_tiers = (int32_t)S.sub_tiers.size();
     o->sub_mrhs_cover_level = S.sub_cover_level;
     o->dense_strip_entries = S.n_strip_entries;
+    for (const parsy::Schedule::SplitDesc& sd : S.split_desc)
+        if (sd.nparts > 1) {
+            o->split_tiles += 1;
+            o->split_parts += sd.nparts;
+        }
     return 0;
 }
 

@@ -30,9 +30,9 @@ struct SolveGates {
 };
 SolveGates read_solve_gates();
 
-// Kernel witness (diagnostics, tests): one host-side counter per solve kernel instantiation that a launch function can
-// enqueue, bumped next to its hipLaunchKernelGGL (a relaxed atomic add on the host: nothing on the GPU).  Exported
-// through parsy_debug_kernel_* so that a test can prove which kernels a solve ran.
+// Kernel witness (diagnostics, tests): one host-side counter per solve kernel instantiation and per factor kernel that a
+// launch function can enqueue, bumped next to its hipLaunchKernelGGL (a relaxed atomic add on the host: nothing on the
+// GPU).  Exported through parsy_debug_kernel_* so that a test can prove which kernels a factorization or a solve ran.
 #define PARSY_WITNESS_KERNELS(X)                                                                                     \
     X(SolveTiny, "k_solve_tiny<16>")                                                                                 \
     X(SolveSmall, "k_solve_small")                                                                                   \
@@ -68,7 +68,14 @@ SolveGates read_solve_gates();
     X(RhsOnes, "k_rhs_ones")                                                                                         \
     X(CopySegments, "k_copy_segments")                                                                               \
     X(SolveSubMrhs, "k_solve_sub_mrhs")                                                                              \
-    X(BsolveSubMrhs, "k_bsolve_sub_mrhs")
+    X(BsolveSubMrhs, "k_bsolve_sub_mrhs")                                                                            \
+    X(ScatterA, "k_scatter_a")                                                                                       \
+    X(CholSmall, "k_chol_small")                                                                                     \
+    X(CholTiles, "k_chol_tiles")                                                                                     \
+    X(CholChain, "k_chol_chain")                                                                                     \
+    X(CholChainRows, "k_chol_chain_rows")                                                                            \
+    X(CholBig, "k_chol_big")                                                                                         \
+    X(CholDense, "k_chol_dense")
 enum WitnessKernel : int {
 #define PARSY_WITNESS_ENUM(id, name) kW##id,
     PARSY_WITNESS_KERNELS(PARSY_WITNESS_ENUM)

@@ -1567,5 +1567,11 @@ def test_coverage_matrix_reaches_every_solve_kernel(api, oracle, monkeypatch):
     assert np.abs(bd.cpu().numpy() - bo).max() <= 1e-12 * max(1.0, np.abs(bo).max())
     union["k_rhs_ones"] = union.get("k_rhs_ones", 0) + api.kernel_launches()["k_rhs_ones"]
     assert set(_NOT_COVERED) <= set(union), "an exclusion names no entry of the witness table"
+    # (the table also holds the factor kernels: tests/test_factor_shapes_gpu.py has their coverage test)
+    from test_kernel_witness import SOLVE_SOURCES, kernel_names
+    solve_kernels = kernel_names(SOLVE_SOURCES)
+    assert {k.split("<")[0] for want in _COVERAGE for k in want[4]} <= solve_kernels
+    union = {k: v for k, v in union.items() if k.split("<")[0] in solve_kernels}
+    assert {k.split("<")[0] for k in union} == solve_kernels and set(_NOT_COVERED) <= set(union)
     missing = sorted(k for k, v in union.items() if v == 0 and k not in _NOT_COVERED)
     assert not missing, f"solve kernels no cell reached: {missing}"
