@@ -503,6 +503,23 @@ int64_t parsy_debug_dense_tasks(const parsy_plan* pl, int32_t* out, int64_t cap)
     return n;
 }
 
+// Diagnostics: the launch table of the plan -- which = 0: factorization, 1: forward solve, 2: backward solve -- as one row
+// per launch record of parsy::kLaunchFields columns, the fields of parsy::Launch in declaration order (kind, first, count,
+// level, side, wait_level, form, rows_only, ticket, lds_bytes, stage, width, width_class, task_first, task_count);
+// returns the number of records (out may be null).
+int64_t parsy_debug_launches(const parsy_plan* pl, int which, int32_t* out, int64_t cap) {
+    if (!pl || which < 0 || which > 2) return -1;
+    const parsy::Schedule& S = pl->S;
+    const std::vector<parsy::Launch>& seq = which == 0 ? S.chol : which == 1 ? S.solve : S.bsolve;
+    for (size_t i = 0; out && i < seq.size() && (int64_t)i < cap; ++i) {
+        const parsy::Launch& l = seq[i];
+        const int32_t row[parsy::kLaunchFields] = {l.kind, l.first, l.count, l.level, l.side, l.wait_level, l.form, l.rows_only,
+                                                   l.ticket, l.lds_bytes, l.stage, l.width, l.width_class, l.task_first, l.task_count};
+        std::copy(row, row + parsy::kLaunchFields, out + (size_t)parsy::kLaunchFields * i);
+    }
+    return (int64_t)seq.size();
+}
+
 // Diagnostics: the launches of the last collected profiled run as rows of (kind, level << 1 | side, work items, ms).
 int64_t parsy_debug_launch_times(const parsy_plan* pl, double* out, int64_t cap) {
     if (!pl) return -1;

@@ -1595,7 +1595,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_chol_chain(const SnDesc* __rest
     tile_task<true>(S, S.s_task, sn, relpos, wents, wptr, split_ranges, tile_scratch, tiles, L, info, tflags, nflags,
                     epoch);
 }
-// CHAIN, second launch of a level (Launch::fused = 1): the tiles of the rows below the diagonal squares -- every
+// CHAIN, second launch of a level (Launch::rows_only = 1): the tiles of the rows below the diagonal squares -- every
 // diagonal tile they wait for was published by the first launch.  Three workgroups per compute unit (52 KB of LDS,
 // <= 168 registers): what a tile spends waiting for memory (its own load, the ring's first chunk, the diagonal
 // block, its stores) runs behind the products of two others instead of one.

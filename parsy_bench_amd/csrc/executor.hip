@@ -367,7 +367,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
         }
         profile_mark(pl, l.kind, stream, cursor, l.level, l.side, l.count);
         switch (l.kind) {
-            case kLaunchSmall: launch_chol_small(pl->dp, l.first, l.count, l.lds_bytes, l.jb, l.fused == 2, L, stream); break;
+            case kLaunchSmall: launch_chol_small(pl->dp, l.first, l.count, l.lds_bytes, l.stage, l.form == kFormSubtrees, L, stream); break;
             case kLaunchTiles:
             case kLaunchBig:
             case kLaunchDense: {
@@ -385,20 +385,20 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                 }
                 break;
             }
-            case kLaunchChain: launch_chol_chain(pl->dp, l.first, l.count, l.jb, pl->epoch, l.fused != 0, L, stream); break;
+            case kLaunchChain: launch_chol_chain(pl->dp, l.first, l.count, l.ticket, pl->epoch, l.rows_only != 0, L, stream); break;
             case kLaunchSolveSmall:
                 // (the subtree launch with many right-hand sides: a wave per subtree and 16 right-hand sides, traffic in LDS)
-                if (l.fused == 2 && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count)
+                if (l.form == kFormSubtrees && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count)
                     launch_solve_sub_mrhs(pl->dp, pl->S.sub_tiers[0], Lc, x, nrhs, ldx, pl->solve_ldq, stream);
                 else
-                    launch_solve_small(pl->dp, l.first, l.count, l.jb, l.fused == 2, Lc, x, nrhs, ldx, pl->solve_ldq, stream);
+                    launch_solve_small(pl->dp, l.first, l.count, l.width, l.form == kFormSubtrees, Lc, x, nrhs, ldx, pl->solve_ldq, stream);
                 break;
             case kLaunchSolvePanel:
-                if (l.fused && nrhs >= pl->dp.gates.chain_mrhs_min)
-                    launch_solve_blocks_mrhs(pl->dp, l.lds_bytes, l.wait_level, Lc, dinv, x, xscratch, nrhs, ldx,
-                                             pl->solve_ldq, l.jb, pl->dp.gates.wait_bias, stream);
-                else if (l.fused)   // (one right-hand side: chain_mrhs_min is at most 2)
-                    launch_solve_chain(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, l.jb, pl->dp.gates.wait_bias,
+                if (l.form == kFormChain && nrhs >= pl->dp.gates.chain_mrhs_min)
+                    launch_solve_blocks_mrhs(pl->dp, l.task_first, l.task_count, Lc, dinv, x, xscratch, nrhs, ldx,
+                                             pl->solve_ldq, l.ticket, pl->dp.gates.wait_bias, stream);
+                else if (l.form == kFormChain)   // (one right-hand side: chain_mrhs_min is at most 2)
+                    launch_solve_chain(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, l.ticket, pl->dp.gates.wait_bias,
                                        stream);
                 else
                     launch_solve_panel(pl->dp, l.first, l.count, Lc, x, xscratch, nrhs, ldx, stream);
@@ -410,18 +410,17 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                 if (nrhs == 1) launch_bsolve_below(pl->dp, l.first, l.count, Lc, x, stream);
                 break;
             case kLaunchBackBlock:
-                if (l.fused == 1 && nrhs == 1) {   // one right-hand side: the wave dataflow over block-column pairs
-                    launch_bsolve_chain_w(pl->dp, l.lds_bytes, l.wait_level, Lc, dinv, x, xscratch, l.jb,
+                if (l.form == kFormChain && nrhs == 1) {   // one right-hand side: the wave dataflow over block-column pairs
+                    launch_bsolve_chain_w(pl->dp, l.task_first, l.task_count, Lc, dinv, x, xscratch, l.ticket,
                                           pl->dp.gates.wait_bias, stream);
                     break;
                 }
-                if (l.fused == 2 && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count) {
+                if (l.form == kFormSubtrees && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count) {
                     launch_bsolve_sub_mrhs(pl->dp, pl->S.sub_tiers[0], Lc, x, nrhs, ldx, stream);
                     break;
                 }
-                launch_bsolve_block(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, nrhs, ldx, l.fused,
-                                    l.early,
-                                    l.fused == 1 ? l.jb : 0, pl->dp.gates.wait_bias, stream);
+                launch_bsolve_block(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, nrhs, ldx, (LaunchForm)l.form,
+                                    l.width_class, l.ticket, pl->dp.gates.wait_bias, stream);
                 break;
         }
     }
@@ -570,7 +569,7 @@ static void run_solve(parsy_plan* pl, bool backward, const double* d_L, double* 
         }
     }
     for (size_t li = 0; li < seq.size(); ++li)
-        if (seq[li].fused != 2 && seq[li].level > S.sub_cover_level)
+        if (seq[li].form != kFormSubtrees && seq[li].level > S.sub_cover_level)
             run_range(pl, seq, li, li + 1, nullptr, d_L, x, nrhs, ldx, stream);
     if (backward) {
         for (size_t k = S.sub_tiers.size(); k-- > 0;) {

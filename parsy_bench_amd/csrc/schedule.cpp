@@ -939,6 +939,60 @@ static void build_sub_tiers(Schedule& S) {
     }
 }
 
+// The makers of the launch records: each takes what its kind and form have, every other field keeps its default.
+// (`count`, and what a launch takes from its members -- lds_bytes, stage, width, task_count --, is filled in by name
+// while build_launches appends the launch's descriptors.)
+static Launch main_launch(int32_t kind, int32_t first, int32_t level) {
+    Launch L{kind};
+    L.first = first;
+    L.level = level;
+    return L;
+}
+// TILES and the BIG / DENSE launches of a PUSH: on the side stream once `wait_level` is complete; the main-stream
+// launches of `level` wait for it
+static Launch side_launch(int32_t kind, int32_t first, int32_t level, int32_t wait_level) {
+    Launch L = main_launch(kind, first, level);
+    L.side = 1;
+    L.wait_level = wait_level;
+    return L;
+}
+static Launch small_launch(int32_t first, int32_t level) { return main_launch(kLaunchSmall, first, level); }
+static Launch subtrees_launch(int32_t kind) {   // SMALL, SOLVE_SMALL, BACK_BLOCK: the pairs [0, count) of the kind's range array
+    Launch L = main_launch(kind, 0, 0);
+    L.form = kFormSubtrees;
+    return L;
+}
+static Launch chain_launch(int32_t first, int32_t level, int32_t ticket, bool rows_only) {
+    Launch L = main_launch(kLaunchChain, first, level);
+    L.ticket = ticket;
+    L.rows_only = rows_only;
+    return L;
+}
+static Launch solve_small_launch(int32_t first, int32_t count, int32_t level) {
+    Launch L = main_launch(kLaunchSolveSmall, first, level);
+    L.count = count;
+    return L;
+}
+// chain form of SOLVE_PANEL / BACK_BLOCK: a ticket counter and a task range (solve_mtasks / bsolve_pairs) from task_first on
+static Launch level_chain_launch(int32_t kind, int32_t first, int32_t level, int32_t ticket, int32_t task_first) {
+    Launch L = main_launch(kind, first, level);
+    L.form = kFormChain;
+    L.ticket = ticket;
+    L.task_first = task_first;
+    return L;
+}
+static Launch fixup_launch(int32_t count, int32_t level) {
+    Launch L = main_launch(kLaunchSolveFixup, 0, level);
+    L.count = count;
+    return L;
+}
+static Launch back_block_launch(int32_t first, int32_t count, int32_t level, int32_t width_class) {
+    Launch L = main_launch(kLaunchBackBlock, first, level);
+    L.count = count;
+    L.width_class = width_class;
+    return L;
+}
+
 void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pieces) {
     const int ns = S.nsuper;
     // PARSY_FORCE_UNFUSED=1 schedules the solve's fallback form everywhere (per-block-column
@@ -1138,7 +1192,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         // ---- Cholesky -------------------------------------------------------------
         if (lev == 0 && S.n_chol_subtrees > 0) {
             // the subtrees of SMALL supernodes, one workgroup each: LDS and stage sized for the largest member
-            Launch L{kLaunchSmall, 0, 0, 0, 0, 0, 2, 0, -1, 0};
+            Launch L = subtrees_launch(kLaunchSmall);
             L.count = subtree_ranges(
                 S.chol_subtree, S.n_chol_subtrees, S.chol_cost, [&] { return (int32_t)S.small_list.size(); },
                 [&](int32_t t) {
@@ -1146,13 +1200,13 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                     S.small_list.push_back(S.piece0[t]);
                     L.lds_bytes = std::max<int32_t>(L.lds_bytes, T.w * T.r * (int)sizeof(double));
                     for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
-                        L.jb = std::max<int32_t>(L.jb, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
+                        L.stage = std::max<int32_t>(L.stage, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
                 },
                 S.small_ranges, true);
             if (L.count > 0) S.chol.push_back(L);
         }
         {
-            Launch L{kLaunchSmall, (int32_t)S.small_list.size(), 0, lev, 0, 0, 0, 0, -1, 0};
+            Launch L = small_launch((int32_t)S.small_list.size(), lev);
             for (int q = S.clevelPtr[lev]; q < S.clevelPtr[lev + 1]; ++q) {
                 const int t = S.clevelSet[q];
                 if (!S.active_piece[t] || S.chol_subtree[S.csn_real[t]] >= 0) continue;
@@ -1160,10 +1214,10 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                 if (is_small(T)) {
                     S.small_list.push_back(t);
                     L.lds_bytes = std::max<int32_t>(L.lds_bytes, T.w * T.r * (int)sizeof(double));
-                    // jb carries the stage size of the SMALL launch: the largest descendant block,
+                    // the stage size of the SMALL launch: the largest descendant block,
                     // capped (kernel: kSmallStage = 2048 doubles)
                     for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
-                        L.jb = std::max<int32_t>(L.jb, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
+                        L.stage = std::max<int32_t>(L.stage, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
                 } else {
                     bigs.push_back(t);
                 }
@@ -1174,21 +1228,21 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         // ---- PUSH(lev): this level's wide supernodes update everything at least two levels up (side
         // stream, once the level is complete); NEXT(lev - 1): the level below updates this level's tiles
         if (lev + 2 < S.cnlevels) {
-            Launch Ld = emit_big(big_push[lev], Launch{kLaunchDense, 0, 0, lev + 2, 0, 0, 0, 1, lev, 1}, true);
+            Launch Ld = emit_big(big_push[lev], side_launch(kLaunchDense, 0, lev + 2, lev), true);
             if (Ld.count > 0) early_launches.push_back(Ld);
-            Launch Lp = emit_big(big_push[lev], Launch{kLaunchBig, 0, 0, lev + 2, 0, 0, 0, 1, lev, 1}, false);
+            Launch Lp = emit_big(big_push[lev], side_launch(kLaunchBig, 0, lev + 2, lev), false);
             if (Lp.count > 0) early_launches.push_back(Lp);
         }
         if (lev > 0) {
-            Launch Ld = emit_big(big_next[lev - 1], Launch{kLaunchDense, 0, 0, lev, 0, 0, 0, 0, -1, 0}, true);
+            Launch Ld = emit_big(big_next[lev - 1], main_launch(kLaunchDense, 0, lev), true);
             if (Ld.count > 0) S.chol.push_back(Ld);
-            Launch Ln = emit_big(big_next[lev - 1], Launch{kLaunchBig, 0, 0, lev, 0, 0, 0, 0, -1, 0}, false);
+            Launch Ln = emit_big(big_next[lev - 1], main_launch(kLaunchBig, 0, lev), false);
             if (Ln.count > 0) S.chol.push_back(Ln);
         }
         if (!bigs.empty()) {
             // ---- TILES: the early part of the external updates, longest streams first ------
             {
-                Launch Lt{kLaunchTiles, (int32_t)S.tiles.size(), 0, lev, 0, 0, 0, 1, lev - 2, 1};
+                Launch Lt = side_launch(kLaunchTiles, (int32_t)S.tiles.size(), lev, lev - 2);
                 std::vector<std::pair<int32_t, TileDesc>> wt;  // (weight, tile)
                 for (int t : bigs) {
                     const SnDesc& T = S.csn[t];
@@ -1241,8 +1295,8 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             bool chain_split = false;
             for (int t : bigs) chain_split = chain_split || splits(t);
             for (int part = 0; part < (chain_split ? 2 : 1); ++part) {
-            Launch Lc{kLaunchChain, (int32_t)S.tiles.size(), 0, lev, S.n_chain_launches++, 0, 0, 0, -1, 0};
-            Lc.fused = part;   // 1: only tiles below the squares (k_chol_chain_rows: three workgroups per compute unit)
+            // part 1: only tiles below the squares (k_chol_chain_rows: three workgroups per compute unit)
+            Launch Lc = chain_launch((int32_t)S.tiles.size(), lev, S.n_chain_launches++, part == 1);
             // Walkers stay resident for their whole chain, so the block-column-major interleaving is
             // done per batch of at most walker_batch supernodes: what a walker waits for then lies at most
             // one batch of tiles ahead of it in ticket order, and the walkers of the batches in flight
@@ -1303,12 +1357,12 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         sbigs.clear();
         // ---- forward solve ----------------------------------------------------------
         if (lev == 0 && S.n_solve_subtrees > 0) {
-            Launch L{kLaunchSolveSmall, 0, 0, 0, 0, 0, 2, 0, -1, 0};
+            Launch L = subtrees_launch(kLaunchSolveSmall);
             L.count = subtree_ranges(
                 S.solve_subtree, S.n_solve_subtrees, S.solve_cost, [&] { return (int32_t)S.solve_small_list.size(); },
                 [&](int32_t t) {
                     S.solve_small_list.push_back(t);
-                    L.jb = std::max<int32_t>(L.jb, S.sn[t].w);
+                    L.width = std::max<int32_t>(L.width, S.sn[t].w);
                 },
                 S.solve_small_ranges);
             if (L.count > 0) S.solve.push_back(L);
@@ -1331,10 +1385,10 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             }
             for (const std::vector<int32_t>* group : {&tiny, &narrow}) {
                 if (group->empty()) continue;
-                Launch L{kLaunchSolveSmall, (int32_t)S.solve_small_list.size(), (int32_t)group->size(), lev, 0, 0, 0, 0, -1, 0};
+                Launch L = solve_small_launch((int32_t)S.solve_small_list.size(), (int32_t)group->size(), lev);
                 for (int32_t t : *group) {
                     S.solve_small_list.push_back(t);
-                    L.jb = std::max<int32_t>(L.jb, S.sn[t].w);  // widest supernode of the launch
+                    L.width = std::max<int32_t>(L.width, S.sn[t].w);  // widest supernode of the launch
                 }
                 S.solve.push_back(L);
             }
@@ -1345,20 +1399,20 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             for (int t : sbigs) chain_wgs += ceil_div(S.sn[t].r, kSolveRows);
             if (chain_wgs <= max_chain) {
                 // one launch: every 256-row chunk of every wide supernode of the level
-                Launch Lc{kLaunchSolvePanel, (int32_t)S.solve_panels.size(), 0, lev, S.n_solve_chain_launches++, 0, 1, 0, -1, 0};
+                Launch Lc = level_chain_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev, S.n_solve_chain_launches++,
+                                               (int32_t)S.solve_mtasks.size());
                 for (int t : sbigs)
                     for (int c = 0; c * kSolveRows < S.sn[t].r; ++c)
                         S.solve_panels.push_back(PanelDesc{t, c, c * kSolveRows, 0});
                 Lc.count = (int32_t)S.solve_panels.size() - Lc.first;
                 // the same launch for many right-hand sides (k_solve_blocks_mrhs): the block columns of the triangles
                 // first (producers, ascending), then the row chunks below the supernodes' own columns
-                Lc.lds_bytes = (int32_t)S.solve_mtasks.size();
                 for (int t : sbigs)
                     for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) S.solve_mtasks.push_back(PanelDesc{t, jb, -1, 0});
                 for (int t : sbigs)
                     for (int c = 0, row0 = S.sn[t].w; row0 < S.sn[t].r; ++c, row0 += kSolveRowsMrhs)
                         S.solve_mtasks.push_back(PanelDesc{t, c, row0, 0});
-                Lc.wait_level = (int32_t)S.solve_mtasks.size() - Lc.lds_bytes;
+                Lc.task_count = (int32_t)S.solve_mtasks.size() - Lc.task_first;
                 S.solve.push_back(Lc);
                 for (int t : sbigs) {
                     for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) {
@@ -1370,7 +1424,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                 int maxnb = 0;
                 for (int t : sbigs) maxnb = std::max(maxnb, ceil_div(S.sn[t].w, kTile));
                 for (int jb = 0; jb < maxnb; ++jb) {
-                    Launch Lp{kLaunchSolvePanel, (int32_t)S.solve_panels.size(), 0, lev, jb, 0, 0, 0, -1, 0};
+                    Launch Lp = main_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev);
                     for (int t : sbigs) {
                         const SnDesc& T = S.sn[t];
                         if (ceil_div(T.w, kTile) <= jb) continue;
@@ -1398,7 +1452,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
     // PARSY_BSOLVE_BELOW=0: never split the rows below off; 2: for every wide supernode with rows below (tests)
     const int below_mode = env_int("PARSY_BSOLVE_BELOW", 1);
     auto in_level_launches = [&](int t) { return S.active[t] && S.bsolve_subtree[t] < 0; };
-    // the supernodes of one block column of a level: the tiny ones (one wave each: Launch::early = 1) in a launch
+    // the supernodes of one block column of a level: the tiny ones (one wave each: Launch::width_class = 1) in a launch
     // of their own when there are enough of them, the others one workgroup each
     auto narrow_launches = [&](int lev) {
         std::vector<int32_t> tiny, tiny2, narrow;
@@ -1420,8 +1474,8 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         }
         for (const std::vector<int32_t>* group : {&tiny, &tiny2, &narrow}) {
             if (group->empty()) continue;
-            Launch Ln{kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), (int32_t)group->size(), lev, 0, 0, 0, 0, -1,
-                      group == &tiny ? 1 : group == &tiny2 ? 2 : 0};
+            Launch Ln = back_block_launch((int32_t)S.bsolve_blocks.size(), (int32_t)group->size(), lev,
+                                          group == &tiny ? 1 : group == &tiny2 ? 2 : 0);
             for (int32_t t : *group) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
             S.bsolve.push_back(Ln);
         }
@@ -1436,8 +1490,8 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             if (nbc > 1) wide_blocks += nbc;
         }
         if (wide_blocks > 0 && wide_blocks <= max_chain) {
-            Launch Lc{kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), 0, lev, S.n_solve_chain_launches++,
-                      (int32_t)S.bsolve_pairs.size(), 1, 0, -1, 0};
+            Launch Lc = level_chain_launch(kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), lev, S.n_solve_chain_launches++,
+                                           (int32_t)S.bsolve_pairs.size());
             // One right-hand side: a block column's sums over the rows BELOW the supernode's own columns (x final there)
             // need no hand-off, but in the chain launch only the block column's own four waves stream them -- a level of
             // few, tall supernodes (the separators below the root: 53 workgroups for 0.9 GB of panel) ran at 1.2 TB/s.
@@ -1449,7 +1503,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                 if (S.active[t] && S.sn[t].w > kTile) groups_here += ceil_div(ceil_div(S.sn[t].w, kTile), kBackGroup);
             }
             const bool below_level = below_mode >= 2 || (below_mode == 1 && groups_here <= kBelowMaxGroups);
-            Launch Lw{kLaunchBackBelow, (int32_t)S.bsolve_below.size(), 0, lev, 0, 0, 0, 0, -1, 0};
+            Launch Lw = main_launch(kLaunchBackBelow, (int32_t)S.bsolve_below.size(), lev);
             for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
                 const int t = S.levelSet[q];
                 const int nbc = ceil_div(S.sn[t].w, kTile);
@@ -1472,13 +1526,13 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             Lw.count = (int32_t)S.bsolve_below.size() - Lw.first;
             if (Lw.count > 0) S.bsolve.push_back(Lw);
             Lc.count = (int32_t)S.bsolve_blocks.size() - Lc.first;
-            Lc.wait_level = (int32_t)S.bsolve_pairs.size() - Lc.lds_bytes;
+            Lc.task_count = (int32_t)S.bsolve_pairs.size() - Lc.task_first;
             S.bsolve.push_back(Lc);
             narrow_launches(lev);
             continue;
         }
         for (int jb = maxnb - 1; jb >= 1; --jb) {
-            Launch Lb{kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), 0, lev, jb, 0, 0, 0, -1, 0};
+            Launch Lb = back_block_launch((int32_t)S.bsolve_blocks.size(), 0, lev, 0);
             for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
                 const int t = S.levelSet[q];
                 if (in_level_launches(t) && ceil_div(S.sn[t].w, kTile) > jb) S.bsolve_blocks.push_back(PanelDesc{t, jb, 0, 0});
@@ -1487,7 +1541,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             if (Lb.count > 0) S.bsolve.push_back(Lb);
         }
         if (maxnb > 1) {   // block column 0 of the wide supernodes (their other block columns: the launches above)
-            Launch Lb{kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), 0, lev, 0, 0, 0, 0, -1, 0};
+            Launch Lb = back_block_launch((int32_t)S.bsolve_blocks.size(), 0, lev, 0);
             for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
                 const int t = S.levelSet[q];
                 if (in_level_launches(t) && ceil_div(S.sn[t].w, kTile) > 1) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
@@ -1500,7 +1554,8 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
     if (S.n_bsolve_subtrees > 0) {
         // the subtrees last: every ancestor outside them is final; inside, a workgroup walks from the subtree's
         // root down (the forward order reversed)
-        Launch L{kLaunchBackBlock, 0, 0, 0, 0, 0, 2, 0, -1, 1};   // (tiny supernodes: one wave per subtree)
+        Launch L = subtrees_launch(kLaunchBackBlock);
+        L.width_class = 1;   // (tiny supernodes: one wave per subtree)
         std::vector<int32_t> members;
         L.count = subtree_ranges(
             S.bsolve_subtree, S.n_bsolve_subtrees, S.solve_cost,
@@ -1513,7 +1568,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         if (L.count > 0) S.bsolve.push_back(L);
     }
     if (!S.solve_fix_list.empty())
-        S.solve.push_back(Launch{kLaunchSolveFixup, 0, (int32_t)S.solve_fix_list.size(), S.nlevels, 0, 0, 0, 0, -1, 0});
+        S.solve.push_back(fixup_launch((int32_t)S.solve_fix_list.size(), S.nlevels));
     build_solve_one(S, active != nullptr || active_pieces != nullptr);
 }
 
@@ -1597,10 +1652,10 @@ static void build_solve_one(Schedule& S, bool sharded) {
             nbk += mb[(size_t)t];
         }
         int nfused_f = 0, nfused_b = 0;
-        for (const Launch& l : S.solve) nfused_f += l.fused == 2 && l.kind == kLaunchSolveSmall;
-        for (const Launch& l : S.bsolve) nfused_b += l.fused == 2 && l.kind == kLaunchBackBlock;
-        const bool first_ok = nfused_f == (S.n_solve_subtrees > 0) && (nfused_f == 0 || S.solve.front().fused == 2);
-        const bool last_ok = nfused_b == (S.n_bsolve_subtrees > 0) && (nfused_b == 0 || S.bsolve.back().fused == 2);
+        for (const Launch& l : S.solve) nfused_f += l.form == kFormSubtrees && l.kind == kLaunchSolveSmall;
+        for (const Launch& l : S.bsolve) nfused_b += l.form == kFormSubtrees && l.kind == kLaunchBackBlock;
+        const bool first_ok = nfused_f == (S.n_solve_subtrees > 0) && (nfused_f == 0 || S.solve.front().form == kFormSubtrees);
+        const bool last_ok = nfused_b == (S.n_bsolve_subtrees > 0) && (nfused_b == 0 || S.bsolve.back().form == kFormSubtrees);
         if (!first_ok || !last_ok || nf == 0 || nbk == 0) return;
     }
     auto fits = [&](int64_t members) {
@@ -1655,7 +1710,7 @@ int64_t simulate_chain(const Schedule& S, int slots) {
                 if (t.I == 0 && t.J == 0) t.role = 0;
                 else if (t.I == t.J) t.role = 2;
                 else if (t.I == t.J + 1 && t.I < nbc) t.role = 1;
-                if (L.fused != 0 && t.I < nbc) ++stuck;   // a rows launch holds no tile of a diagonal square
+                if (L.rows_only && t.I < nbc) ++stuck;   // a rows launch holds no tile of a diagonal square
                 resident.push_back(t);
                 progress = true;
             }
@@ -1723,7 +1778,7 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
         int last_level = -1;
         for (const Launch& l : S.solve) {
             if (l.kind == kLaunchSolveSmall) {
-                if (l.fused == 2) {
+                if (l.form == kFormSubtrees) {
                     for (int b = l.first; b < l.first + l.count; ++b) {
                         const int32_t q0 = S.solve_small_ranges[2 * (size_t)b], q1 = S.solve_small_ranges[2 * (size_t)b + 1];
                         if (q0 < 0 || q1 <= q0 || q1 > (int32_t)S.solve_small_list.size()) {
@@ -1734,7 +1789,7 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
                             const int t = S.solve_small_list[q];
                             seen[t]++;
                             if (q > q0 && t <= S.solve_small_list[q - 1]) fail("forward subtree run is not in index order");
-                            if (S.sn[t].w > l.jb) fail("forward subtree launch: supernode wider than the launch's width class");
+                            if (S.sn[t].w > l.width) fail("forward subtree launch: supernode wider than the launch's width class");
                         }
                     }
                 } else {
@@ -1744,7 +1799,7 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
                         const int t = S.solve_small_list[q];
                         seen[t]++;
                         if (level_of[t] != l.level) fail("forward launch holds a supernode of another level");
-                        if (S.sn[t].w > l.jb || S.sn[t].w > kTile) fail("forward launch: supernode wider than its width class");
+                        if (S.sn[t].w > l.width || S.sn[t].w > kTile) fail("forward launch: supernode wider than its width class");
                     }
                 }
             } else if (l.kind == kLaunchSolvePanel) {
@@ -1754,20 +1809,20 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
                     const PanelDesc& pd = S.solve_panels[q];
                     if (pd.sn < 0 || pd.sn >= ns || S.sn[pd.sn].w <= kTile || level_of[pd.sn] != l.level)
                         fail("forward chain launch: bad chunk descriptor " + std::to_string(q));
-                    else if (l.fused) {
+                    else if (l.form == kFormChain) {
                         if (pd.row0 != pd.jb * kSolveRows || pd.row0 >= S.sn[pd.sn].r) fail("forward chain launch: bad chunk rows");
                         chunks[pd.sn]++;
                     }
                 }
-                if (l.fused) {
+                if (l.form == kFormChain) {
                     // the same launch for many right-hand sides: per supernode its block columns in ascending order BEFORE
                     // anything that waits for them (tickets go in list order), every row below its columns exactly once
-                    if (l.lds_bytes < 0 || l.wait_level < 0 || (size_t)l.lds_bytes + (size_t)l.wait_level > S.solve_mtasks.size())
-                        fail("forward chain launch: bad task range (many right-hand sides)");
+                    if (l.task_first < 0 || l.task_count < 0 || (size_t)l.task_first + (size_t)l.task_count > S.solve_mtasks.size())
+                        fail("forward chain launch solve[" + std::to_string(&l - S.solve.data()) + "]: bad task range (many right-hand sides)");
                     else {
                         std::vector<int> next_block(ns, 0);
                         std::vector<int64_t> next_row(ns, -1);
-                        for (int q = l.lds_bytes; q < l.lds_bytes + l.wait_level; ++q) {
+                        for (int q = l.task_first; q < l.task_first + l.task_count; ++q) {
                             const PanelDesc& pd = S.solve_mtasks[(size_t)q];
                             if (pd.sn < 0 || pd.sn >= ns || S.sn[pd.sn].w <= kTile || level_of[pd.sn] != l.level) {
                                 fail("forward chain launch: bad task " + std::to_string(q));
@@ -1822,8 +1877,8 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
             int64_t below_done = 0;
             for (const Launch& l : S.bsolve) {
                 if (l.kind == kLaunchBackBelow) below_done += l.count;
-                if (l.kind != kLaunchBackBlock || l.fused != 1) continue;
-                for (int g = l.lds_bytes; g < l.lds_bytes + l.wait_level; ++g) {
+                if (l.kind != kLaunchBackBlock || l.form != kFormChain) continue;
+                for (int g = l.task_first; g < l.task_first + l.task_count; ++g) {
                     const PanelDesc& pd = S.bsolve_pairs[(size_t)g];
                     if (pd.pad <= 0) continue;
                     const SnDesc& T = S.sn[(size_t)pd.sn];
@@ -1841,7 +1896,7 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
         }
         for (const Launch& l : S.bsolve) {
             if (l.kind != kLaunchBackBlock) continue;
-            if (l.fused == 2) {
+            if (l.form == kFormSubtrees) {
                 for (int b = l.first; b < l.first + l.count; ++b) {
                     const int32_t q0 = S.bsolve_ranges[2 * (size_t)b], q1 = S.bsolve_ranges[2 * (size_t)b + 1];
                     if (q0 < 0 || q1 <= q0 || q1 > (int32_t)S.bsolve_blocks.size()) {
@@ -1865,16 +1920,16 @@ static void check_solve_launches(const Schedule& S, const std::function<void(con
                 }
                 if (S.sn[pd.sn].w <= kTile) {
                     seen[pd.sn]++;
-                    if (l.early == 1 && S.sn[pd.sn].w > kTinyWidth) fail("backward launch: supernode wider than its width class");
-                    if (l.early == 2 && S.sn[pd.sn].w > kTinyWidth2) fail("backward launch: supernode wider than its width class");
+                    if (l.width_class == 1 && S.sn[pd.sn].w > kTinyWidth) fail("backward launch: supernode wider than its width class");
+                    if (l.width_class == 2 && S.sn[pd.sn].w > kTinyWidth2) fail("backward launch: supernode wider than its width class");
                 } else {
                     blocks[pd.sn]++;
                 }
             }
-            if (l.fused == 1) {
+            if (l.form == kFormChain) {
                 // the groups of the one-right-hand-side kernel: the same block columns, last one first
                 int prev_sn = -1, next_jb = -1;
-                for (int g = l.lds_bytes; g < l.lds_bytes + l.wait_level; ++g) {
+                for (int g = l.task_first; g < l.task_first + l.task_count; ++g) {
                     const PanelDesc& pd = S.bsolve_pairs[(size_t)g];
                     if (pd.sn != prev_sn) {
                         if (prev_sn >= 0 && next_jb != -1) fail("backward groups of supernode " + std::to_string(prev_sn) + " stop early");
@@ -1980,9 +2035,9 @@ static void check_solve_one(const Schedule& S, Fail&& fail) {
                 break;
             }
     if (S.one_subtrees) {
-        if (S.n_solve_subtrees > 0 && (S.solve.empty() || S.solve.front().fused != 2))
+        if (S.n_solve_subtrees > 0 && (S.solve.empty() || S.solve.front().form != kFormSubtrees))
             fail("one-launch forward solve: the subtree launch is not the first launch");
-        if (S.n_bsolve_subtrees > 0 && (S.bsolve.empty() || S.bsolve.back().fused != 2))
+        if (S.n_bsolve_subtrees > 0 && (S.bsolve.empty() || S.bsolve.back().form != kFormSubtrees))
             fail("one-launch backward solve: the subtree launch is not the last launch");
     }
 }
@@ -2073,11 +2128,53 @@ static void check_sub_tiers(const Schedule& S, Fail&& fail) {
     }
 }
 
+// The launch records themselves: a record's kind belongs to its list, and every field that its kind and form do not have
+// holds its default -- what a positional initialiser of the record could not keep apart.
+static void check_launch_records(const Schedule& S, const std::function<void(const std::string&)>& fail) {
+    static const char* const kind_name[] = {"SMALL", "TILES", "CHAIN", "BIG", "BACK_BELOW", "SOLVE_SMALL", "SOLVE_PANEL",
+                                            "SOLVE_FIXUP", "BACK_BLOCK", "DENSE"};
+    auto check_list = [&](const std::vector<Launch>& seq, const char* list, auto&& in_list, int ntickets) {
+        for (size_t i = 0; i < seq.size(); ++i) {
+            const Launch& l = seq[i];
+            const int k = l.kind;
+            const bool known = k >= 0 && k <= kLaunchDense;
+            const std::string who = std::string("launch ") + list + "[" + std::to_string(i) + "] (" + (known ? kind_name[k] : "?") + "): ";
+            if (!known || !in_list(k)) {
+                fail(who + "kind " + std::to_string(k) + " does not belong to this list");
+                continue;
+            }
+            const bool may_chain = k == kLaunchSolvePanel || k == kLaunchBackBlock;
+            const bool may_subtrees = k == kLaunchSmall || k == kLaunchSolveSmall || k == kLaunchBackBlock;
+            if (!(l.form == kFormEach || (l.form == kFormChain && may_chain) || (l.form == kFormSubtrees && may_subtrees)))
+                fail(who + "form " + std::to_string(l.form) + " is not one of its kind's");
+            const bool chain_form = may_chain && l.form == kFormChain;
+            if (l.first < 0 || l.count < 0) fail(who + "negative descriptor range");
+            if (l.side != 0 && !(l.side == 1 && (k == kLaunchTiles || k == kLaunchBig || k == kLaunchDense)))
+                fail(who + "side = " + std::to_string(l.side) + " on a kind that has no side-stream launches");
+            if (l.wait_level < -1 || (l.wait_level != -1 && !l.side)) fail(who + "wait_level = " + std::to_string(l.wait_level) + " on a main-stream launch or below -1");
+            if (l.rows_only != 0 && !(l.rows_only == 1 && k == kLaunchChain)) fail(who + "rows_only is set");
+            if (l.ticket != 0 && !(k == kLaunchChain || chain_form)) fail(who + "has a ticket counter but takes no tickets");
+            if (l.ticket < 0 || (l.ticket > 0 && l.ticket >= ntickets)) fail(who + "ticket counter " + std::to_string(l.ticket) + " does not exist");
+            if ((l.lds_bytes != 0 || l.stage != 0) && k != kLaunchSmall) fail(who + "lds_bytes / stage are set");
+            if (l.lds_bytes < 0 || l.stage < 0) fail(who + "negative lds_bytes / stage");
+            if (l.width != 0 && k != kLaunchSolveSmall) fail(who + "width is set");
+            if (l.width_class < 0 || l.width_class > 2 || (l.width_class != 0 && k != kLaunchBackBlock))
+                fail(who + "width_class = " + std::to_string(l.width_class));
+            if ((l.task_first != 0 || l.task_count != 0) && !chain_form) fail(who + "has a task range but is no chain-form launch");
+        }
+    };
+    check_list(S.chol, "chol", [](int k) { return is_chol_launch(k); }, S.n_chain_launches);
+    check_list(S.solve, "solve", [](int k) { return k == kLaunchSolveSmall || k == kLaunchSolvePanel || k == kLaunchSolveFixup; },
+               S.n_solve_chain_launches);
+    check_list(S.bsolve, "bsolve", [](int k) { return k == kLaunchBackBelow || k == kLaunchBackBlock; }, S.n_solve_chain_launches);
+}
+
 int64_t check_schedule(const Schedule& S, std::string& what) {
     int64_t bad = 0;
     auto fail = [&](const std::string& msg) {
         if (bad++ == 0) what = msg;
     };
+    check_launch_records(S, fail);
     check_solve_launches(S, fail);
     check_solve_one(S, fail);
     check_sub_tiers(S, fail);
@@ -2259,7 +2356,7 @@ int64_t check_schedule(const Schedule& S, std::string& what) {
         std::vector<int> seen(nc, 0);
         for (const Launch& l : S.chol) {
             if (l.kind != kLaunchSmall) continue;
-            if (l.fused == 2) {
+            if (l.form == kFormSubtrees) {
                 for (int b = l.first; b < l.first + l.count; ++b) {
                     const int32_t q0 = S.small_ranges[2 * (size_t)b], q1 = S.small_ranges[2 * (size_t)b + 1];
                     if (q0 < 0 || q1 <= q0 || q1 > (int32_t)S.small_list.size()) {

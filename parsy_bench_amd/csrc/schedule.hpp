@@ -168,21 +168,34 @@ enum LaunchKind : int32_t {
 };
 inline bool is_chol_launch(int kind) { return (kind >= 0 && kind <= kLaunchBig) || kind == kLaunchDense; }
 
+// How a launch's workgroups find their work.  SMALL, SOLVE_SMALL: Each | Subtrees; SOLVE_PANEL: Each | Chain;
+// BACK_BLOCK: all three; every other kind: Each.
+enum LaunchForm : int32_t {
+    kFormEach = 0,       // one workgroup per entry [first, first + count) of the kind's descriptor array
+    kFormChain = 1,      // the wide supernodes of a whole level in one launch, work handed out by a ticket counter
+    kFormSubtrees = 2,   // one workgroup walks a subtree: first / count are (begin, end) pairs in the kind's range array
+};
+
+// One launch of a factorization or a solve.  Every field has one meaning; a field the launch's kind and form do not have
+// keeps its default (check_schedule holds every record to that).  Built by the makers in schedule.cpp.
 struct Launch {
     int32_t kind;
-    int32_t first, count;  // range in the kind's descriptor array
-    int32_t level;         // etree level of the targets; side launches: level whose main-stream launches wait for it
-    int32_t jb;            // SMALL: stage size; CHAIN: index of its ticket counter; SOLVE_PANEL / BACK: block column
-    int32_t lds_bytes;     // dynamic LDS (SMALL); BACK chain launch: first entry of its workgroups in bsolve_pairs;
-                           // SOLVE_PANEL chain launch: first entry of its tasks in solve_mtasks
-    int32_t fused;         // SOLVE_PANEL / BACK: 1 = chain launch of the whole level; SMALL, SOLVE_SMALL, BACK:
-                           // 2 = subtree launch (first / count: (begin, end) pairs in the kind's range array);
-                           // CHAIN: 1 = the level's second launch (tiles below the diagonal squares only)
-    int32_t side;          // 1: runs on the plan's side stream (TILES), 0: main stream
-    int32_t wait_level;    // side launches: wait until this etree level is complete (-1: init only);
-                           // BACK chain launch: number of its entries in bsolve_pairs; SOLVE_PANEL chain launch: in solve_mtasks
-    int32_t early;         // TILES: always 1 (kept for the launch dumps)
+    int32_t first = 0, count = 0;   // range in the kind's descriptor array (kFormSubtrees: in its range array)
+    int32_t level = 0;              // etree level of the targets; side launches: level whose main-stream launches wait for it
+    int32_t side = 0;               // 1: runs on the plan's side stream (TILES, and the BIG / DENSE launches of a PUSH)
+    int32_t wait_level = -1;        // side launches: wait until this etree level is complete (-1: init only)
+    int32_t form = kFormEach;
+    int32_t rows_only = 0;          // CHAIN: 1 = the level's second launch (tiles below the diagonal squares only)
+    int32_t ticket = 0;             // CHAIN, chain-form SOLVE_PANEL / BACK_BLOCK: index of the launch's ticket counter
+    int32_t lds_bytes = 0;          // SMALL: dynamic LDS of the largest panel
+    int32_t stage = 0;              // SMALL: stage size in doubles (the largest descendant block, capped)
+    int32_t width = 0;              // SOLVE_SMALL: widest supernode of the launch
+    int32_t width_class = 0;        // BACK_BLOCK: 0 | 1 (<= kTinyWidth) | 2 (<= kTinyWidth2): the one-wave kernels' classes
+    int32_t task_first = 0, task_count = 0;   // chain-form SOLVE_PANEL: its tasks in solve_mtasks (many right-hand sides);
+                                              // chain-form BACK_BLOCK: its workgroups in bsolve_pairs (one right-hand side)
 };
+constexpr int kLaunchFields = 15;   // a record is that many int32_t in declaration order (the launch table of the diagnostics)
+static_assert(sizeof(Launch) == kLaunchFields * sizeof(int32_t), "Launch: fields and kLaunchFields disagree");
 
 constexpr int kSplitChunks = 192;        // early wave streams longer than this (16-wide k chunks) are split ...
 constexpr int kSplitTarget = 128;        // ... into parts of about this length (at most kSplitMaxParts)
@@ -318,7 +331,7 @@ struct Schedule {
     std::vector<PanelDesc> solve_panels;
     std::vector<PanelDesc> solve_mtasks;  // chain launches, many right-hand sides: per wide supernode its block columns
                                           // (row0 = -1), then the 256-row chunks of the rows below its columns (row0 >= w);
-                                          // Launch::lds_bytes / wait_level = first entry / number of entries of a launch
+                                          // Launch::task_first / task_count = first entry / number of entries of a launch
     std::vector<int32_t> solve_fix_list;  // wide supernodes solved by per-block-column launches
     std::vector<int32_t> solve_wide_list; // (supernode, block column) pairs of the wide supernodes solved by
                                           // SOLVE_CHAIN: the diagonal blocks whose inverses a solve needs
@@ -394,7 +407,8 @@ int64_t simulate_chain(const Schedule& S, int slots);
 // Host-side consistency check of the Cholesky view: levels of sources and targets, windows of the wave and BIG
 // entries, exact cover of every update by its entries (flop identity), order of the launch sequence -- and of the
 // launches of both solves (every active supernode / chunk / block column exactly once, subtree runs in order,
-// width classes, the backward chain's groups).  Returns the number of violations (0 = consistent) and describes
+// width classes, the backward chain's groups) -- and of the launch records themselves: a field that a record's kind and
+// form do not have holds its default, a kind belongs to its list.  Returns the number of violations (0 = consistent) and describes
 // the first one in `what`.
 int64_t check_schedule(const Schedule& S, std::string& what);
 constexpr int kSmallMaxUpdates = 8;   // supernodes with more updates go the tiled way (MFMA streams, parallel tiles)

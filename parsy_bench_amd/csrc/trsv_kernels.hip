@@ -3682,26 +3682,27 @@ void launch_bsolve_chain_w(const DevicePattern& P, int first, int count, const d
                        P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias, P.bpart);
 }
 
-// mode: Launch::fused -- 0: one workgroup per block, 1: chain launch (tickets), 2: subtree launch (`first` counts
-// (begin, end) pairs of bsolve_ranges, which index the whole block list); tiny: Launch::early (0 | width class 1 | 2)
+// form: Launch::form -- kFormEach: one workgroup per block, kFormChain: chain launch (tickets), kFormSubtrees: subtree launch
+// (`first` counts (begin, end) pairs of bsolve_ranges, which index the whole block list); width_class: Launch::width_class
+// (0 | 1: kTinyWidth | 2: kTinyWidth2)
 void launch_bsolve_block(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
-                         double* x, double* xscratch, int nrhs, int ldx, int mode, int tiny, int ticket,
+                         double* x, double* xscratch, int nrhs, int ldx, LaunchForm form, int width_class, int ticket,
                          int wait_bias, hipStream_t stream) {
     if (count <= 0) return;
-    const int chain = mode == 1;
-    const PanelDesc* pds = mode == 2 ? P.bsolve_blocks : P.bsolve_blocks + first;
-    const int32_t* ranges = mode == 2 ? P.bsolve_ranges + 2 * first : nullptr;
+    const int chain = form == kFormChain;
+    const PanelDesc* pds = form == kFormSubtrees ? P.bsolve_blocks : P.bsolve_blocks + first;
+    const int32_t* ranges = form == kFormSubtrees ? P.bsolve_ranges + 2 * first : nullptr;
     const SolveGates& G = P.gates;
-    if (tiny == 1 && nrhs >= G.bmrhs_min) {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
+    if (width_class == 1 && nrhs >= G.bmrhs_min) {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
         const dim3 grid(count, std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM));
         witness_launch(kWBsolveTinyMrhs);
         hipLaunchKernelGGL(k_bsolve_tiny_mrhs, grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L, x, nrhs, ldx);
         return;
     }
-    if (tiny && nrhs < G.bmrhs_min) {   // width class kTinyWidth (1) or kTinyWidth2 (2), a subtree launch or a level's launch: one wave each
+    if (width_class && nrhs < G.bmrhs_min) {   // width class kTinyWidth (1) or kTinyWidth2 (2), a subtree launch or a level's launch: one wave each
         const dim3 grid(count, std::min(kPassLanes, nrhs));
         static_assert(kTinyWidth == 16 && kTinyWidth2 == 32, "witness entries k_bsolve_tiny<16>, <32>");
-        if (tiny == 1) {
+        if (width_class == 1) {
             witness_launch(kWBsolveTiny16);
             hipLaunchKernelGGL(k_bsolve_tiny<kTinyWidth>, grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L, x, nrhs,
                                ldx);
