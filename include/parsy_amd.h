@@ -500,6 +500,50 @@ int parsy_factor_apply_get_info(parsy_plan* plan, parsy_apply_info* info);      
  * ascending; ptr holds n + 1 entries, pos ssize.  Host-only plans too. */
 int parsy_factor_apply_row_index(const parsy_plan* plan, int64_t* ptr, int64_t* pos);
 
+/* ---- Update and downdate of the factor: A + W W' and A - W W' without a refactorization ------------------------------
+ * W is a sparse n x k matrix (k >= 0) in compressed columns in the caller's ordering: wp (k + 1 entries) and wi (row
+ * indices, strictly ascending within a column) on the host, the values on the device.  Its rows go through the plan's
+ * ordering (parsy_plan_set_perm).  The call turns d_lValues, the factor of P A P', into the factor of P (A + sign W W') P'
+ * by one rotation per (column of L, column of W) pair, columns of L ascending:
+ *     r = sqrt(d^2 + sign w^2), c = r / d, s = w / d with d = L_jj, w = W_jt;  L_jj = r, W_jt = 0, and below the diagonal
+ *     L_ij = (L_ij + sign s W_it) / c,  W_it = c W_it - s L_ij.
+ * Only the supernodes on the etree paths above the first row j_t (factor's ordering) of each column t of W are read and
+ * written, each panel once per block of 8 columns of W; everything else of d_lValues keeps its bits, the strict upper
+ * triangles of the diagonal blocks are neither read nor written, and d_wx is not changed.
+ * THE PATTERN OF L DOES NOT CHANGE: a column t with a non-zero outside the structure of column j_t of L (the row list of
+ * j_t's supernode from j_t on) is refused, on the host, before anything is enqueued; the message names the column and the
+ * row.  Further refusals (parsy_last_error names each; nothing is written): a NULL argument with k > 0, sign other than
+ * +1 / -1, k < 0, a row index outside 0 .. n - 1, indices unsorted or repeated within a column, a plan restricted by
+ * parsy_plan_set_active / _set_active_pieces, a host-only plan.  k == 0 and empty columns are no-ops.
+ * A pivot with r^2 <= 0 or not finite (a downdate that leaves the matrix indefinite) is reported by parsy_updown_status
+ * after the stream is synchronised: 0, or the first such column, 1-based, in the factor's ordering (-1: the plan has no
+ * device, as parsy_factor_status).  Its rotation is
+ * left out, so no NaN spreads, but d_lValues is then NO LONGER A FACTOR of anything; the plan stays usable (factor
+ * again).  The caller's values of A are not touched: whoever refines afterwards supplies the values of A + sign W W'.
+ * The call uploads W's pattern and waits for the stream once before it enqueues; kernels are ordered by the stream alone.
+ * The first device call makes an n x 8 workspace, counted in the plan's device_bytes. */
+int parsy_factor_updown_device(parsy_plan* plan, double* d_lValues, int sign, int k, const int* wp, const int* wi,
+                               const double* d_wx, void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  Synchronous. */
+int parsy_factor_updown_host(parsy_plan* plan, double* lValues, int sign, int k, const int* wp, const int* wi,
+                             const double* wx, double* seconds);
+int parsy_updown_status(parsy_plan* plan);
+/* The supernodes the call above would touch, ascending, each with the first column (factor's ordering) the rotations
+ * reach in it: the start column j_t in the supernode that holds it, the first row below the child's columns in an
+ * ancestor.  supernodes / first_col (either may be NULL) hold up to nsuper entries.  Returns the count, or -1 for a W the
+ * update would refuse.  Host-only plans too. */
+int parsy_updown_path(const parsy_plan* plan, int k, const int* wp, const int* wi, int* supernodes, int* first_col);
+typedef struct parsy_updown_info {
+    int32_t path_supernodes;   /* of the last device call (0: none yet) */
+    int32_t last_launches;     /* kernels it enqueued */
+    int32_t last_k;
+    int32_t last_sign;
+    int64_t block_columns;     /* block columns of 64 columns on that path, from the entry columns on */
+    int64_t entries_touched;   /* stored entries of L in the columns walked, summed over the blocks of 8 columns of W */
+    int64_t device_bytes;      /* workspace, coefficient table and W's pattern held (0 before the first device call) */
+} parsy_updown_info;
+int parsy_updown_get_info(parsy_plan* plan, parsy_updown_info* info);          /* host-only plans too */
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

@@ -94,6 +94,7 @@ EXPORTED_SYMBOLS = [
     "parsy_cond_get_info", "parsy_error_bounds_device", "parsy_solve_spd_bounds_device", "parsy_solve_spd_bounds_host",
     "parsy_rcond_device", "parsy_rcond_host",
     "parsy_factor_apply_device", "parsy_factor_apply_host", "parsy_factor_apply_get_info", "parsy_factor_apply_row_index",
+    "parsy_factor_updown_device", "parsy_factor_updown_host", "parsy_updown_status", "parsy_updown_path", "parsy_updown_get_info",
 ]
 
 
@@ -106,6 +107,16 @@ class ApplyInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class UpdownInfo(C.Structure):
+    _fields_ = [
+        ("path_supernodes", C.c_int32), ("last_launches", C.c_int32), ("last_k", C.c_int32), ("last_sign", C.c_int32),
+        ("block_columns", C.c_int64), ("entries_touched", C.c_int64), ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class CondInfo(C.Structure):
@@ -243,6 +254,11 @@ def _declare(lib):
     lib.parsy_factor_apply_host.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp]
     lib.parsy_factor_apply_get_info.argtypes = [vp, vp]
     lib.parsy_factor_apply_row_index.argtypes = [vp, vp, vp]
+    lib.parsy_factor_updown_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.parsy_factor_updown_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.parsy_updown_status.argtypes = [vp]
+    lib.parsy_updown_path.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.parsy_updown_get_info.argtypes = [vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -520,6 +520,75 @@ class Plan:
             m = np.broadcast_to(m.reshape(self.sym.n, -1), zz.reshape(self.sym.n, -1).shape).reshape(zz.shape)
         return self.factor_apply(lValues, zz, op, alpha=1.0, y=m, beta=1.0)[0]
 
+    # update / downdate of the factor: A + W W' and A - W W' in place (include/parsy_amd.h) ---------------------------
+    @staticmethod
+    def _w_csc(W, n):
+        """(wp, wi, wx) of W: a (wp, wi, wx) triple as it is, or a dense (n,) / (n, k) array whose non-zeros are the
+        pattern."""
+        if isinstance(W, tuple):
+            wp, wi, wx = W
+            return _i32(wp), _i32(wi), _f64(wx)
+        D = np.asarray(W, dtype=np.float64)
+        if D.ndim == 1:
+            D = D.reshape(n, 1)
+        if D.ndim != 2 or D.shape[0] != n:
+            raise ValueError(f"W is {D.shape}, the plan has n = {n}")
+        cols = [np.flatnonzero(D[:, t]) for t in range(D.shape[1])]
+        wp = np.concatenate([[0], np.cumsum([c.size for c in cols])]).astype(np.int32)
+        wi = (np.concatenate(cols) if cols else np.zeros(0)).astype(np.int32)
+        wx = np.concatenate([D[c, t] for t, c in enumerate(cols)]).astype(np.float64) if cols else np.zeros(0)
+        return wp, wi, np.ascontiguousarray(wx)
+
+    def updown_device(self, d_lValues: int, wp, wi, d_wx: int, sign: int = +1, stream: int = 0) -> None:
+        """d_lValues, the factor of A, becomes the factor of A + sign W W' (W: host pattern wp / wi in the caller's
+        ordering, values on the device) under the plan's ordering (set_perm).  The pattern of L does not change: a W
+        that would change it is refused.  Check updown_status() afterwards."""
+        wp = _i32(wp)
+        wi = _i32(wi)
+        if N.lib().parsy_factor_updown_device(self._h, d_lValues or None, int(sign), wp.size - 1, N.ptr(wp), N.ptr(wi),
+                                              d_wx or None, stream) != 0:
+            raise RuntimeError("parsy_factor_updown_device failed: " + N.last_error())
+
+    def updown(self, lValues, W, sign: int = +1):
+        """Host arrays: (the factor of A + sign W W', device_seconds); lValues is not changed.  W: dense (n,) or (n, k) in
+        the caller's ordering (its non-zeros are the pattern) or a (wp, wi, wx) triple.  On first use the plan takes
+        sym.Perm as its ordering, as solve_refined does.  After a failed downdate (updown_status() != 0) the result is
+        not a factor."""
+        if not getattr(self, "_perm_set", False):
+            self.set_perm(self.sym.Perm)
+            self._perm_set = True
+        wp, wi, wx = self._w_csc(W, self.sym.n)
+        lv = np.array(lValues, dtype=np.float64, copy=True).reshape(-1)
+        sec = C.c_double(0)
+        if N.lib().parsy_factor_updown_host(self._h, N.ptr(lv), int(sign), wp.size - 1, N.ptr(wp), N.ptr(wi), N.ptr(wx),
+                                            C.byref(sec)) != 0:
+            raise RuntimeError("parsy_factor_updown_host failed: " + N.last_error())
+        return lv, sec.value
+
+    def updown_status(self) -> int:
+        """0, or the first column (1-based, factor's ordering) whose pivot failed in the last update / downdate."""
+        return int(N.lib().parsy_updown_status(self._h))
+
+    def updown_path(self, W):
+        """(supernodes, first_col) an update by W would touch, ascending, under the plan's ordering as it is set; W as
+        in updown().  Host-only plans too."""
+        wp, wi, _ = self._w_csc(W, self.sym.n)
+        sn = np.zeros(max(self.sym.nsuper, 1), dtype=np.int32)
+        fc = np.zeros(max(self.sym.nsuper, 1), dtype=np.int32)
+        cnt = N.lib().parsy_updown_path(self._h, wp.size - 1, N.ptr(wp), N.ptr(wi), N.ptr(sn), N.ptr(fc))
+        if cnt < 0:
+            raise RuntimeError("parsy_updown_path failed: " + N.last_error())
+        return sn[:cnt].copy(), fc[:cnt].copy()
+
+    @property
+    def updown_info(self) -> dict:
+        """Of the last updown_device / updown call: path_supernodes, block_columns, last_launches, last_k, last_sign,
+        entries_touched; device_bytes (0 before the first device call)."""
+        ui = N.UpdownInfo()
+        if N.lib().parsy_updown_get_info(self._h, C.byref(ui)) != 0:
+            raise RuntimeError("parsy_updown_get_info failed: " + N.last_error())
+        return ui.as_dict()
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

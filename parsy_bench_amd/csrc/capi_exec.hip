@@ -766,6 +766,47 @@ int parsy_factor_apply_get_info(parsy_plan* pl, parsy_apply_info* info) {
     return 0;
 }
 
+int parsy_factor_updown_device(parsy_plan* pl, double* d_lValues, int sign, int k, const int* wp, const int* wi,
+                               const double* d_wx, void* stream) {
+    return parsy::plan_factor_updown(pl, d_lValues, sign, k, wp, wi, d_wx, stream);
+}
+
+int parsy_updown_status(parsy_plan* pl) { return parsy::plan_updown_status(pl); }
+
+int parsy_updown_path(const parsy_plan* pl, int k, const int* wp, const int* wi, int* supernodes, int* first_col) {
+    const char* who = "parsy_updown_path";
+    if (!pl) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    parsy::UpdownW W;
+    if (parsy::updown_prepare(pl->S, pl->perm, who, k, wp, wi, W) != 0) return -1;
+    std::vector<parsy::UpdownNode> path;
+    parsy::updown_path(pl->S, W, 0, k, path);
+    for (size_t i = 0; i < path.size(); ++i) {
+        if (supernodes) supernodes[i] = path[i].sn;
+        if (first_col) first_col[i] = path[i].first_col;
+    }
+    return (int)path.size();
+}
+
+int parsy_updown_get_info(parsy_plan* pl, parsy_updown_info* info) {
+    if (!pl || !info) {
+        set_last_error("parsy_updown_get_info: null argument");
+        return -1;
+    }
+    if (parsy::updown_ensure_host(pl) != 0) return -1;
+    const parsy::UpdownState& U = *pl->updown;
+    info->path_supernodes = U.path_supernodes;
+    info->last_launches = U.last_launches;
+    info->last_k = U.last_k;
+    info->last_sign = U.last_sign;
+    info->block_columns = U.block_columns;
+    info->entries_touched = U.entries_touched;
+    info->device_bytes = U.meter.bytes;
+    return 0;
+}
+
 void parsy_dropin_reset(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_plans) parsy::plan_free(kv.second);

@@ -471,4 +471,35 @@ int parsy_factor_apply_host(parsy_plan* pl, const double* lValues, int op, const
     return 0;
 }
 
+int parsy_factor_updown_host(parsy_plan* pl, double* lValues, int sign, int k, const int* wp, const int* wi, const double* wx,
+                             double* seconds) {
+    const char* who = "parsy_factor_updown_host";
+    if (parsy::updown_check_args(pl, who, lValues, sign, k, wp, wi, wx) != 0) return -1;
+    {
+        // the refusals of W come before the one of a host-only plan, as in the device call
+        parsy::UpdownW W;
+        if (parsy::updown_prepare(pl->S, pl->perm, who, k, wp, wi, W) != 0) return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    if (seconds) *seconds = 0.0;
+    if (k == 0) return parsy_factor_updown_device(pl, nullptr, sign, 0, wp, wi, nullptr, nullptr);
+    const parsy::Schedule& S = pl->S;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    Scratch sc;
+    double* d_wx = sc.upload(wx, wp[k], wp[k] > wp[0]);   // (positions in wx count from its start, whatever wp[0] is)
+    if (!d_wx || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_factor_updown_device(pl, pl->h_L_dev.data(), sign, k, wp, wi, d_wx, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev.data(), (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

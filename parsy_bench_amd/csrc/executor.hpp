@@ -19,6 +19,7 @@ struct SelinvState;
 struct GradState;
 struct CondState;
 struct ApplyState;
+struct UpdownState;
 }
 
 struct parsy_plan {
@@ -104,6 +105,7 @@ struct parsy_plan {
     std::unique_ptr<parsy::GradState> grad;       // gradients with respect to A's values (grad.hpp)
     std::unique_ptr<parsy::CondState> cond;       // forward error bounds / condition estimate (cond.hpp)
     std::unique_ptr<parsy::ApplyState> apply;     // the factor as an operator (apply.hpp)
+    std::unique_ptr<parsy::UpdownState> updown;   // update / downdate of the factor (updown.hpp)
 
     ~parsy_plan();   // (executor.hip, where the state types are complete)
 };

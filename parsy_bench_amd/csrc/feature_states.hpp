@@ -1,11 +1,12 @@
-// The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp: those headers
-// are read by host-only translation units too, these structs own device memory).  A plan holds each only once one of
+// The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp: those
+// headers are read by host-only translation units too, these structs own device memory).  A plan holds each only once one of
 // the feature's device calls has run.
 #pragma once
 #include "apply.hpp"
 #include "device_buffer.hpp"
 #include "grad.hpp"
 #include "selinv.hpp"
+#include "updown.hpp"
 
 namespace parsy {
 
@@ -66,6 +67,21 @@ struct ApplyState {
     DeviceBuf<double> ws{&meter};     // T / partials + staged X of one block of columns
     DeviceBuf<double> sol{&meter};    // n x nrhs operand of the inverse operators
     int last_op = -1, last_launches = 0;
+};
+
+struct UpdownState {
+    explicit UpdownState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                  // parsy_updown_info.device_bytes: everything here, in the plan's figure too
+    bool on_device = false;           // set when the workspace, the table and the status word exist
+    DevicePool fixed{&meter};
+    double* d_w = nullptr;            // n x kUpdownBlock, the columns of a row contiguous; all zero between calls
+    double* d_coef = nullptr;         // kUpdownTile x kUpdownBlock rotations of the block column under way
+    int32_t* d_status = nullptr;      // smallest 1-based column whose pivot failed (INT_MAX: none)
+    DeviceBuf<int32_t> pattern{&meter};   // of the block of W under way: rows, columns, positions in the caller's values
+    DeviceBuf<int64_t> segs{&meter};      // the row lists of a path: prefix sums of their lengths, then their offsets in lR
+    bool used = false;                // a call has enqueued work that writes the status word
+    int path_supernodes = 0, last_launches = 0, last_k = 0, last_sign = 0;
+    int64_t block_columns = 0, entries_touched = 0;
 };
 
 }  // namespace parsy
