@@ -544,6 +544,66 @@ typedef struct parsy_updown_info {
 } parsy_updown_info;
 int parsy_updown_get_info(parsy_plan* plan, parsy_updown_info* info);          /* host-only plans too */
 
+/* ---- Row delete and row add: take a variable out of the factor and put it back, without a refactorization -----------
+ * `row` is in the caller's ordering (parsy_plan_set_perm); p is its position in the factor's ordering.  With
+ *     L = [L11 0 0; l12' l22 0; L31 l32 L33]      (row and column p in the middle)
+ * DELETE turns d_lValues, the factor of P A P', into the factor of the matrix whose row and column p are the identity's:
+ *     w = l32;  l12 = 0, l22 = 1, l32 = 0 (exactly);  then the update L33 L33' + w w'.
+ * ADD takes the new column of the symmetric matrix -- nz row indices ci (host, strictly ascending, caller's ordering, the
+ * diagonal entry `row` among them) and the values d_cx on the device, never written -- and makes
+ *     L11 l12 = a12;  l22 = sqrt(a22 - l12' l12);  l32 = (a32 - L31 l12) / l22;  then the downdate L33 L33' - l32 l32'.
+ * What stood in row p left of the diagonal, in l22 and in column p before an add is NEVER READ; it is overwritten.  The
+ * caller's obligation: everything else of d_lValues is the factor of A with row and column `row` deleted -- after a
+ * delete, or after factoring values whose row `row` is the identity's.  The plan keeps no record of deleted rows:
+ * entries of the column that couple `row` to another row that is still deleted must be left out by the caller.
+ * THE PATTERN OF L DOES NOT CHANGE: every off-diagonal non-zero (i, p) of the column must be a stored entry of L -- for
+ * i > p, i in the structure of column p; for i < p, p in the row list of i's supernode from i on.  A column that breaks
+ * the rule is refused on the host, before anything is enqueued; the message names the row in both orderings.
+ * Further refusals (parsy_last_error names each; nothing is written): a NULL argument, a row outside 0 .. n - 1, indices
+ * unsorted or repeated, a missing diagonal entry, a plan restricted by parsy_plan_set_active / _set_active_pieces, a
+ * host-only plan.
+ * Only these stored entries are written: row p in the panels of the supernodes whose row list holds p (the row subtree
+ * T(p), parsy_rowmod_reach), column p, and the columns of the rotation pass -- parsy_factor_updown_device's own, entered
+ * at the first row below p of column p.  Everything else keeps its bits; the strict upper triangles of the diagonal
+ * blocks are neither read nor written.  An add reads every entry of L in the columns of T(p) and in the rows below them
+ * once.  Two calls on the same input give the same bits.
+ * STATUS: parsy_rowmod_status after the stream is synchronised (it is parsy_updown_status's word): 0; `p + 1` when the
+ * add's own pivot a22 - l12' l12 was <= 0 or not finite -- column p is then left as the identity's, row p as the solve
+ * left it, and no downdate is enqueued; a larger column when the downdate behind it left the matrix indefinite.  After a
+ * failure d_lValues is NO LONGER A FACTOR of anything, and nothing in it is NaN or Inf that was not before; the plan
+ * stays usable (factor again).
+ * Each call uploads its lists and waits for the stream once before it enqueues; an add whose column has rows below p
+ * waits a second time, behind the kernel that forms l22, to read the status word.  Kernels are ordered by the stream
+ * alone.  The first device call makes the workspaces (one double per entry of the row lists, n doubles, the transpose
+ * of the row lists) and, where it does not exist yet, parsy_factor_updown_device's; all counted in the plan's
+ * device_bytes.  parsy_updown_get_info's counters do not move with a row call (its device_bytes may). */
+int parsy_factor_rowdel_device(parsy_plan* plan, double* d_lValues, int row, void* stream);
+int parsy_factor_rowadd_device(parsy_plan* plan, double* d_lValues, int row, int nz, const int* ci, const double* d_cx,
+                               void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  Synchronous. */
+int parsy_factor_rowdel_host(parsy_plan* plan, double* lValues, int row, double* seconds);
+int parsy_factor_rowadd_host(parsy_plan* plan, double* lValues, int row, int nz, const int* ci, const double* cx,
+                             double* seconds);
+int parsy_rowmod_status(parsy_plan* plan);
+/* T(p) of `row`, ascending: per supernode the position of p in its row list and its height inside T(p) (0: no child in
+ * T(p), else 1 + the largest height of its children there).  p's own supernode is a member when p is not its first
+ * column.  The arrays (each may be NULL) hold up to nsuper entries.  Returns the count, or -1.  Host-only plans too. */
+int parsy_rowmod_reach(parsy_plan* plan, int row, int* supernodes, int* position, int* height);
+typedef struct parsy_rowmod_info {
+    int32_t last_op;             /* of the last device call: 0 none yet, 1 delete, 2 add */
+    int32_t last_row;            /* its row in the factor's ordering (-1: none yet) */
+    int32_t reach_supernodes;    /* supernodes of T(p) */
+    int32_t heights;             /* heights of T(p): launches of each of the two row kernels of an add */
+    int32_t row_launches;        /* kernels enqueued over T(p): solve and panel per height and the clearing; delete: one */
+    int32_t column_launches;     /* the kernel on column p (1) */
+    int32_t rotation_launches;   /* kernels of the rotation pass */
+    int32_t reserved;
+    int64_t entries_read;        /* stored entries of L the row pass of an add reads (0 after a delete) */
+    int64_t entries_walked;      /* stored entries of L in the columns the rotation pass walks (read and written once) */
+    int64_t device_bytes;        /* index and workspaces held (0 before the first device call) */
+} parsy_rowmod_info;
+int parsy_rowmod_get_info(parsy_plan* plan, parsy_rowmod_info* info);          /* host-only plans too */
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

@@ -95,6 +95,8 @@ EXPORTED_SYMBOLS = [
     "parsy_rcond_device", "parsy_rcond_host",
     "parsy_factor_apply_device", "parsy_factor_apply_host", "parsy_factor_apply_get_info", "parsy_factor_apply_row_index",
     "parsy_factor_updown_device", "parsy_factor_updown_host", "parsy_updown_status", "parsy_updown_path", "parsy_updown_get_info",
+    "parsy_factor_rowdel_device", "parsy_factor_rowadd_device", "parsy_factor_rowdel_host", "parsy_factor_rowadd_host",
+    "parsy_rowmod_status", "parsy_rowmod_reach", "parsy_rowmod_get_info",
 ]
 
 
@@ -117,6 +119,17 @@ class UpdownInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RowmodInfo(C.Structure):
+    _fields_ = [
+        ("last_op", C.c_int32), ("last_row", C.c_int32), ("reach_supernodes", C.c_int32), ("heights", C.c_int32),
+        ("row_launches", C.c_int32), ("column_launches", C.c_int32), ("rotation_launches", C.c_int32),
+        ("reserved", C.c_int32), ("entries_read", C.c_int64), ("entries_walked", C.c_int64), ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class CondInfo(C.Structure):
@@ -259,6 +272,13 @@ def _declare(lib):
     lib.parsy_updown_status.argtypes = [vp]
     lib.parsy_updown_path.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.parsy_updown_get_info.argtypes = [vp, vp]
+    lib.parsy_factor_rowdel_device.argtypes = [vp, vp, C.c_int, vp]
+    lib.parsy_factor_rowadd_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_factor_rowdel_host.argtypes = [vp, vp, C.c_int, vp]
+    lib.parsy_factor_rowadd_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.parsy_rowmod_status.argtypes = [vp]
+    lib.parsy_rowmod_reach.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.parsy_rowmod_get_info.argtypes = [vp, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -589,6 +589,90 @@ class Plan:
             raise RuntimeError("parsy_updown_get_info failed: " + N.last_error())
         return ui.as_dict()
 
+    # row delete / row add in the factor (include/parsy_amd.h) --------------------------------------------------------
+    @staticmethod
+    def _column(column, n):
+        """(ci, cx) of a column: an (indices, values) pair sorted by index, or a dense (n,) vector whose non-zeros are the
+        pattern."""
+        if isinstance(column, tuple):
+            ci, cx = _i32(column[0]), _f64(column[1])
+            if ci.size != cx.size:
+                raise ValueError(f"the column has {ci.size} indices and {cx.size} values")
+            return ci, cx
+        d = np.asarray(column, dtype=np.float64)
+        if d.shape != (n,):
+            raise ValueError(f"the column is {d.shape}, the plan has n = {n}")
+        ci = np.flatnonzero(d).astype(np.int32)
+        return ci, np.ascontiguousarray(d[ci])
+
+    def rowdel_device(self, d_lValues: int, row: int, stream: int = 0) -> None:
+        """d_lValues, the factor of A, becomes the factor of A with row and column `row` (the plan's ordering: set_perm)
+        made the identity's.  The pattern of L does not change.  Check rowmod_status() afterwards."""
+        if N.lib().parsy_factor_rowdel_device(self._h, d_lValues or None, int(row), stream) != 0:
+            raise RuntimeError("parsy_factor_rowdel_device failed: " + N.last_error())
+
+    def rowadd_device(self, d_lValues: int, row: int, ci, d_cx: int, stream: int = 0) -> None:
+        """Puts row and column `row` back: ci the ascending row indices (host) of the full symmetric column, the diagonal
+        among them, d_cx its values on the device.  What stood in that row and column of the factor is not read; a
+        column outside the pattern of L is refused.  Check rowmod_status() afterwards."""
+        ci = _i32(ci)
+        if N.lib().parsy_factor_rowadd_device(self._h, d_lValues or None, int(row), ci.size, N.ptr(ci), d_cx or None,
+                                              stream) != 0:
+            raise RuntimeError("parsy_factor_rowadd_device failed: " + N.last_error())
+
+    def _take_perm(self):
+        if not getattr(self, "_perm_set", False):
+            self.set_perm(self.sym.Perm)
+            self._perm_set = True
+
+    def rowdel(self, lValues, row: int):
+        """Host arrays: (the factor with row / column `row` of A made the identity's, device_seconds); lValues is not
+        changed.  On first use the plan takes sym.Perm as its ordering, as updown does."""
+        self._take_perm()
+        lv = np.array(lValues, dtype=np.float64, copy=True).reshape(-1)
+        sec = C.c_double(0)
+        if N.lib().parsy_factor_rowdel_host(self._h, N.ptr(lv), int(row), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_factor_rowdel_host failed: " + N.last_error())
+        return lv, sec.value
+
+    def rowadd(self, lValues, row: int, column):
+        """Host arrays: (the factor with row / column `row` put back, device_seconds); lValues is not changed.  column:
+        the full symmetric column in the caller's ordering, a dense (n,) vector (its non-zeros are the pattern) or an
+        (indices, values) pair, the diagonal entry present.  After a failure (rowmod_status() != 0) the result is not a
+        factor."""
+        self._take_perm()
+        ci, cx = self._column(column, self.sym.n)
+        lv = np.array(lValues, dtype=np.float64, copy=True).reshape(-1)
+        sec = C.c_double(0)
+        if N.lib().parsy_factor_rowadd_host(self._h, N.ptr(lv), int(row), ci.size, N.ptr(ci), N.ptr(cx), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_factor_rowadd_host failed: " + N.last_error())
+        return lv, sec.value
+
+    def rowmod_status(self) -> int:
+        """0; p + 1 (p: the row in the factor's ordering) when the add's own pivot failed; a larger column (1-based) when
+        the downdate behind it left the matrix indefinite."""
+        return int(N.lib().parsy_rowmod_status(self._h))
+
+    def rowmod_reach(self, row: int):
+        """(supernodes, position, height) of the row subtree of `row` under the plan's ordering as it is set, ascending.
+        Host-only plans too."""
+        m = max(self.sym.nsuper, 1)
+        sn, pos, h = (np.zeros(m, dtype=np.int32) for _ in range(3))
+        cnt = N.lib().parsy_rowmod_reach(self._h, int(row), N.ptr(sn), N.ptr(pos), N.ptr(h))
+        if cnt < 0:
+            raise RuntimeError("parsy_rowmod_reach failed: " + N.last_error())
+        return sn[:cnt].copy(), pos[:cnt].copy(), h[:cnt].copy()
+
+    @property
+    def rowmod_info(self) -> dict:
+        """Of the last rowdel_device / rowadd_device call: last_op (1 delete, 2 add), last_row, reach_supernodes, heights,
+        row_launches, column_launches, rotation_launches, entries_read, entries_walked; device_bytes (0 before the first
+        device call)."""
+        ri = N.RowmodInfo()
+        if N.lib().parsy_rowmod_get_info(self._h, C.byref(ri)) != 0:
+            raise RuntimeError("parsy_rowmod_get_info failed: " + N.last_error())
+        return ri.as_dict()
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())

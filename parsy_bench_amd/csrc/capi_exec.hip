@@ -807,6 +807,56 @@ int parsy_updown_get_info(parsy_plan* pl, parsy_updown_info* info) {
     return 0;
 }
 
+int parsy_factor_rowdel_device(parsy_plan* pl, double* d_lValues, int row, void* stream) {
+    return parsy::plan_factor_rowdel(pl, d_lValues, row, stream);
+}
+
+int parsy_factor_rowadd_device(parsy_plan* pl, double* d_lValues, int row, int nz, const int* ci, const double* d_cx,
+                               void* stream) {
+    return parsy::plan_factor_rowadd(pl, d_lValues, row, nz, ci, d_cx, stream);
+}
+
+int parsy_rowmod_status(parsy_plan* pl) { return parsy::plan_updown_status(pl); }
+
+int parsy_rowmod_reach(parsy_plan* pl, int row, int* supernodes, int* position, int* height) {
+    const char* who = "parsy_rowmod_reach";
+    if (!pl) {
+        set_last_error(std::string(who) + ": null argument");
+        return -1;
+    }
+    const int p = parsy::rowmod_position(pl->S, parsy::plan_perm_inverse(pl), who, row);
+    if (p < 0 || parsy::rowmod_ensure_host(pl) != 0) return -1;
+    std::vector<parsy::RowmodNode> reach;
+    parsy::rowmod_reach(pl->S, pl->rowmod->I, p, reach);
+    for (size_t i = 0; i < reach.size(); ++i) {
+        if (supernodes) supernodes[i] = reach[i].sn;
+        if (position) position[i] = reach[i].pos;
+        if (height) height[i] = reach[i].height;
+    }
+    return (int)reach.size();
+}
+
+int parsy_rowmod_get_info(parsy_plan* pl, parsy_rowmod_info* info) {
+    if (!pl || !info) {
+        set_last_error("parsy_rowmod_get_info: null argument");
+        return -1;
+    }
+    if (!pl->rowmod) pl->rowmod = std::make_unique<parsy::RowmodState>(&pl->meter);   // (the index only once it is asked for)
+    const parsy::RowmodState& R = *pl->rowmod;
+    info->last_op = R.last_op;
+    info->last_row = R.last_row;
+    info->reach_supernodes = R.reach;
+    info->heights = R.heights;
+    info->row_launches = R.row_launches;
+    info->column_launches = R.column_launches;
+    info->rotation_launches = R.rotation_launches;
+    info->reserved = 0;
+    info->entries_read = R.entries_read;
+    info->entries_walked = R.entries_walked;
+    info->device_bytes = R.meter.bytes;
+    return 0;
+}
+
 void parsy_dropin_reset(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_plans) parsy::plan_free(kv.second);

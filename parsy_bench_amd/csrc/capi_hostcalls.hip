@@ -502,4 +502,54 @@ int parsy_factor_updown_host(parsy_plan* pl, double* lValues, int sign, int k, c
     return 0;
 }
 
+int parsy_factor_rowdel_host(parsy_plan* pl, double* lValues, int row, double* seconds) {
+    const char* who = "parsy_factor_rowdel_host";
+    if (parsy::rowdel_check_args(pl, who, lValues, row, nullptr) != 0) return -1;
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    parsy::EventTimer timer;
+    if (!timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_factor_rowdel_device(pl, pl->h_L_dev.data(), row, nullptr) != 0) return -1;
+    if (!timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev.data(), (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int parsy_factor_rowadd_host(parsy_plan* pl, double* lValues, int row, int nz, const int* ci, const double* cx,
+                             double* seconds) {
+    const char* who = "parsy_factor_rowadd_host";
+    {
+        // the refusals of the column come before the one of a host-only plan, as in the device call
+        parsy::RowmodColumn col;
+        if (parsy::rowadd_check_args(pl, who, lValues, row, nz, ci, cx, col) != 0) return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    Scratch sc;
+    double* d_cx = sc.upload(cx, nz, true);
+    if (!d_cx || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_factor_rowadd_device(pl, pl->h_L_dev.data(), row, nz, ci, d_cx, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    PARSY_HIP(hipMemcpy(lValues, pl->h_L_dev.data(), (size_t)S.xsize * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

@@ -51,7 +51,16 @@ int plan_set_perm(parsy_plan* pl, const int* perm) {
     }
     pl->perm_on_device = false;
     pl->perm.swap(p);
+    pl->perm_inv.clear();
     return 0;
+}
+
+const std::vector<int>& plan_perm_inverse(parsy_plan* pl) {
+    if (pl->perm_inv.size() != pl->perm.size()) {
+        pl->perm_inv.resize(pl->perm.size());
+        for (size_t i = 0; i < pl->perm.size(); ++i) pl->perm_inv[(size_t)pl->perm[i]] = (int)i;
+    }
+    return pl->perm_inv;
 }
 
 int plan_perm_device(parsy_plan* pl, const int** out) {

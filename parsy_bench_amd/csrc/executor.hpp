@@ -20,6 +20,7 @@ struct GradState;
 struct CondState;
 struct ApplyState;
 struct UpdownState;
+struct RowmodState;
 }
 
 struct parsy_plan {
@@ -97,6 +98,7 @@ struct parsy_plan {
     // the caller's ordering (parsy_plan_set_perm; plan_util.hpp): perm[new] = old (empty: identity) and its device copy,
     // uploaded by the first call that reads it
     std::vector<int> perm;
+    std::vector<int> perm_inv;       // its inverse (plan_perm_inverse), made on first use
     parsy::DeviceBuf<int> d_perm{&meter};
     bool perm_on_device = false;     // d_perm holds perm
     // the states of the features, each made by the first call of its kind
@@ -106,6 +108,7 @@ struct parsy_plan {
     std::unique_ptr<parsy::CondState> cond;       // forward error bounds / condition estimate (cond.hpp)
     std::unique_ptr<parsy::ApplyState> apply;     // the factor as an operator (apply.hpp)
     std::unique_ptr<parsy::UpdownState> updown;   // update / downdate of the factor (updown.hpp)
+    std::unique_ptr<parsy::RowmodState> rowmod;   // row delete / row add in the factor (rowmod.hpp)
 
     ~parsy_plan();   // (executor.hip, where the state types are complete)
 };

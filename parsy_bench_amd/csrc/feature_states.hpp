@@ -1,10 +1,11 @@
-// The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp: those
-// headers are read by host-only translation units too, these structs own device memory).  A plan holds each only once one of
-// the feature's device calls has run.
+// The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp,
+// rowmod.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
+// each only once one of the feature's device calls has run.
 #pragma once
 #include "apply.hpp"
 #include "device_buffer.hpp"
 #include "grad.hpp"
+#include "rowmod.hpp"
 #include "selinv.hpp"
 #include "updown.hpp"
 
@@ -82,6 +83,32 @@ struct UpdownState {
     bool used = false;                // a call has enqueued work that writes the status word
     int path_supernodes = 0, last_launches = 0, last_k = 0, last_sign = 0;
     int64_t block_columns = 0, entries_touched = 0;
+    std::vector<int64_t> walk_segs;   // host copy of segs for plan_updown_walk (lives until the next walk: its upload is asynchronous)
+};
+
+struct RowmodDesc {                   // a supernode of the row subtree as the kernels read it
+    int64_t px, pi;                   // its panel in lValues, its row list in lR
+    int32_t c0, r;                    // first column, rows
+    int32_t ks, q;                    // columns that take part, position of p in the row list
+};
+
+struct RowmodState {
+    explicit RowmodState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                  // parsy_rowmod_info.device_bytes: everything here, in the plan's figure too
+    ApplyIndex I;                     // the transpose of the row lists (kept on the host: parsy_rowmod_reach reads it)
+    bool built = false;
+    bool on_device = false;           // set when the index and both workspaces exist
+    DevicePool fixed{&meter};
+    int64_t *d_ptr = nullptr, *d_pos = nullptr;   // the device copy of the index
+    double* d_t = nullptr;            // one double per entry of lR; all zero between calls
+    double* d_y = nullptr;            // n doubles; all zero between calls
+    DeviceBuf<RowmodDesc> nodes{&meter};   // of the call under way: T(p) grouped by height
+    DeviceBuf<int64_t> segs{&meter};       // prefix sums over T(p): of ks (k_rowdel_zero), of r (k_rowmod_clear)
+    DeviceBuf<int32_t> ints{&meter};       // the panel launches' (supernode, first row) pairs; rows and positions of the column
+    // of the last device call
+    int last_op = 0, last_row = -1;   // 0: none yet, 1: delete, 2: add; the row in the factor's ordering
+    int reach = 0, heights = 0, row_launches = 0, column_launches = 0, rotation_launches = 0;
+    int64_t entries_read = 0, entries_walked = 0;
 };
 
 }  // namespace parsy

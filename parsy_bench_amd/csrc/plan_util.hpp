@@ -23,6 +23,8 @@ int check_plan(const parsy_plan* pl, const char* who, PlanNeeds needs);
 
 // The caller's ordering of the plan's vectors (perm[new] = old, n entries; null: back to the identity).
 int plan_set_perm(parsy_plan* pl, const int* perm);
+// its inverse (inv[old] = new; empty: identity), made by the first call that asks and kept until the ordering changes
+const std::vector<int>& plan_perm_inverse(parsy_plan* pl);
 // the device copy of that ordering, uploaded on first use and counted in device_bytes (*out null: identity)
 int plan_perm_device(parsy_plan* pl, const int** out);
 // The one gather and the one scatter of n x nrhs column-major operands under such a device copy (perm null: identity):

@@ -7,8 +7,6 @@
 
 namespace parsy {
 
-namespace {
-
 // the supernode that holds column j
 int supernode_of(const Schedule& S, int j) {
     int lo = 0, hi = S.nsuper - 1;
@@ -19,6 +17,8 @@ int supernode_of(const Schedule& S, int j) {
     }
     return lo;
 }
+
+namespace {
 
 int refuse(const char* who, const std::string& what) {
     set_last_error(std::string(who) + ": " + what);

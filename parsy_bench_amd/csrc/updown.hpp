@@ -41,6 +41,8 @@ struct UpdownNode {         // a supernode of a path and the first column the ro
     int32_t sn, first_col;
 };
 
+// the supernode that holds column j
+int supernode_of(const Schedule& S, int j);
 // The refusals that need no device and the pattern rule; 0 with `out` filled, or -1 with the message set.  perm: the
 // plan's ordering (perm[new] = old; empty: identity).
 int updown_prepare(const Schedule& S, const std::vector<int>& perm, const char* who, int k, const int* wp, const int* wi,
@@ -59,5 +61,21 @@ int updown_ensure_host(parsy_plan* pl);
 int plan_factor_updown(parsy_plan* pl, double* d_L, int sign, int k, const int* wp, const int* wi, const double* d_wx,
                        void* stream);
 int plan_updown_status(parsy_plan* pl);
+
+// The rotation pass alone, for ONE column that already stands in column 0 of the workspace (rowmod.hpp): the path entered
+// at first_col (< 0: no path), with the same launches as a call with k = 1 makes behind its scatter.  _begin makes the
+// device state and uploads the path's row lists on `stream` (nothing of it is read before the stream has run that copy);
+// _reset arms the status word as a call does; _run enqueues.  The counters of parsy_updown_get_info do not move.
+struct UpdownWalk {
+    std::vector<UpdownNode> path;
+    int64_t rows_total = 0;          // rows of the path's row lists
+    int launches = 0;
+    int64_t entries = 0;             // stored entries of L in the columns walked
+};
+int plan_updown_walk_begin(parsy_plan* pl, int first_col, UpdownWalk& Wk, void* stream);
+int plan_updown_status_reset(parsy_plan* pl, void* stream);
+int plan_updown_walk_run(parsy_plan* pl, double* d_L, int sign, UpdownWalk& Wk, void* stream);
+double* plan_updown_workspace(parsy_plan* pl);       // (null before the device state exists)
+int32_t* plan_updown_status_word(parsy_plan* pl);
 
 }  // namespace parsy

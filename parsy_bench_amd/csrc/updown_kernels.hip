@@ -236,6 +236,40 @@ int ensure_device(parsy_plan* pl) {
     return 0;
 }
 
+// The rotation pass over a path for the nb <= kUpdownBlock columns that stand in the workspace, then the clearing of
+// the workspace rows of the path's row lists (d_segs: k_updown_clear_w's segments, rows_total: their last prefix sum).
+void enqueue_walk(parsy_plan* pl, double* d_L, int sign, int nb, const std::vector<UpdownNode>& path, const int64_t* d_segs,
+                  int64_t rows_total, hipStream_t stream, int& launches, int64_t& entries) {
+    const Schedule& S = pl->S;
+    UpdownState& U = *pl->updown;
+    const double sigma = (double)sign;
+    const dim3 threads(kUThreads);
+    for (const UpdownNode& N : path) {
+        const SnDesc& D = S.sn[(size_t)N.sn];
+        const int first = N.first_col - D.c0;
+        for (int cb = first / kUpdownTile * kUpdownTile; cb < D.w; cb += kUpdownTile) {
+            const int nc = std::min(kUpdownTile, D.w - cb);
+            const int j0 = std::max(first - cb, 0);
+            hipLaunchKernelGGL(k_updown_diag, dim3(1), threads, 0, stream, d_L, D.px, D.r, cb, nc, j0, D.c0 + cb, sigma,
+                               U.d_w, U.d_coef, U.d_status);
+            ++launches;
+            const int row0 = cb + nc;
+            if (row0 < D.r) {
+#define UPDOWN_ROWS(NN)                                                                                                 \
+    hipLaunchKernelGGL(k_updown_rows<NN>, dim3(blocks_of(D.r - row0, kUThreads)), threads, 0, stream, d_L, D.px, D.r, cb, \
+                       nc, j0, row0, pl->dp.rows + D.pi, U.d_coef, U.d_w)
+                UPDOWN_NB(nb, UPDOWN_ROWS)
+#undef UPDOWN_ROWS
+                ++launches;
+            }
+            for (int j = cb + j0; j < cb + nc; ++j) entries += D.r - j;
+        }
+    }
+    hipLaunchKernelGGL(k_updown_clear_w, dim3(blocks_of(rows_total, kUThreads)), threads, 0, stream, d_segs, (int)path.size(),
+                       pl->dp.rows, U.d_w);
+    ++launches;
+}
+
 }  // namespace
 
 int updown_ensure_host(parsy_plan* pl) {
@@ -310,43 +344,59 @@ int plan_factor_updown(parsy_plan* pl, double* d_L, int sign, int k, const int* 
     PARSY_HIP(hipMemsetAsync(U.d_status, 0x7f, sizeof(int32_t), stream));
     U.used = true;
 
-    const double sigma = (double)sign;
     const dim3 threads(kUThreads);
     const int32_t* const d_pat = U.pattern.data();
     for (const Block& B : blocks) {
         hipLaunchKernelGGL(k_updown_scatter_w, dim3(blocks_of(B.nnz, kUThreads)), threads, 0, stream, d_pat + B.e0,
                            d_pat + nnz_all + B.e0, d_pat + 2 * (int64_t)nnz_all + B.e0, B.nnz, d_wx, U.d_w);
         ++U.last_launches;
-        for (const UpdownNode& N : B.path) {
-            const SnDesc& D = S.sn[(size_t)N.sn];
-            const int first = N.first_col - D.c0;
-            for (int cb = first / kUpdownTile * kUpdownTile; cb < D.w; cb += kUpdownTile) {
-                const int nc = std::min(kUpdownTile, D.w - cb);
-                const int j0 = std::max(first - cb, 0);
-                hipLaunchKernelGGL(k_updown_diag, dim3(1), threads, 0, stream, d_L, D.px, D.r, cb, nc, j0,
-                                   D.c0 + cb, sigma, U.d_w, U.d_coef, U.d_status);
-                ++U.last_launches;
-                const int row0 = cb + nc;
-                if (row0 < D.r) {
-#define UPDOWN_ROWS(NN)                                                                                                 \
-    hipLaunchKernelGGL(k_updown_rows<NN>, dim3(blocks_of(D.r - row0, kUThreads)), threads, 0, stream, d_L, D.px, D.r, cb, \
-                       nc, j0, row0, pl->dp.rows + D.pi, U.d_coef, U.d_w)
-                    UPDOWN_NB(B.nb, UPDOWN_ROWS)
-#undef UPDOWN_ROWS
-                    ++U.last_launches;
-                }
-                for (int j = cb + j0; j < cb + nc; ++j) U.entries_touched += D.r - j;
-            }
-        }
         const int nseg = (int)B.path.size();
-        const int64_t total = segs[(size_t)(B.seg0 + nseg)];
-        hipLaunchKernelGGL(k_updown_clear_w, dim3(blocks_of(total, kUThreads)), threads, 0, stream, U.segs.data() + B.seg0,
-                           nseg, pl->dp.rows, U.d_w);
-        ++U.last_launches;
+        enqueue_walk(pl, d_L, sign, B.nb, B.path, U.segs.data() + B.seg0, segs[(size_t)(B.seg0 + nseg)], stream,
+                     U.last_launches, U.entries_touched);
         PARSY_HIP(hipGetLastError());
     }
     return 0;
 }
+
+int plan_updown_walk_begin(parsy_plan* pl, int first_col, UpdownWalk& Wk, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    Wk = UpdownWalk();
+    if (first_col < 0) return 0;
+    if (ensure_device(pl) != 0) return -1;
+    UpdownState& U = *pl->updown;
+    const Schedule& S = pl->S;
+    UpdownW one;
+    one.k = 1, one.ptr = {0, 1}, one.row = {first_col}, one.src = {0};
+    updown_path(S, one, 0, 1, Wk.path);
+    std::vector<int64_t>& segs = U.walk_segs;
+    segs.clear();
+    int64_t run = 0;
+    for (const UpdownNode& N : Wk.path) segs.push_back(run), run += S.sn[(size_t)N.sn].r;
+    segs.push_back(run);
+    for (const UpdownNode& N : Wk.path) segs.push_back(S.sn[(size_t)N.sn].pi);
+    Wk.rows_total = run;
+    PARSY_HIP(U.segs.grow((int64_t)segs.size()));
+    PARSY_HIP(hipMemcpyAsync(U.segs.data(), segs.data(), segs.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+int plan_updown_status_reset(parsy_plan* pl, void* stream) {
+    if (ensure_device(pl) != 0) return -1;
+    PARSY_HIP(hipMemsetAsync(pl->updown->d_status, 0x7f, sizeof(int32_t), (hipStream_t)stream));
+    pl->updown->used = true;
+    return 0;
+}
+
+int plan_updown_walk_run(parsy_plan* pl, double* d_L, int sign, UpdownWalk& Wk, void* stream) {
+    if (Wk.path.empty()) return 0;
+    UpdownState& U = *pl->updown;
+    enqueue_walk(pl, d_L, sign, 1, Wk.path, U.segs.data(), Wk.rows_total, (hipStream_t)stream, Wk.launches, Wk.entries);
+    PARSY_HIP(hipGetLastError());
+    return 0;
+}
+
+double* plan_updown_workspace(parsy_plan* pl) { return pl->updown ? pl->updown->d_w : nullptr; }
+int32_t* plan_updown_status_word(parsy_plan* pl) { return pl->updown ? pl->updown->d_status : nullptr; }
 
 int plan_updown_status(parsy_plan* pl) {
     if (!pl || pl->device < 0) return -1;
