@@ -375,6 +375,63 @@ int parsy_rcond_device(parsy_plan* plan, const double* d_values, const double* d
 int parsy_rcond_host(parsy_plan* plan, const double* values, const double* lValues, double* anorm, double* rcond,
                      double* seconds);
 
+/* ---- The smallest eigenpairs of A v = lambda M v, through the factor -----------------------------------------------
+ * The k lowest eigenvalues of the pencil (A, M), A and M symmetric positive definite on the plan's pattern, and their
+ * eigenvectors: a block Davidson iteration with (L L')^-1 as preconditioner and a thick restart, the basis held on the
+ * device (at most max_basis <= 128 columns; V, A V and M V side by side: 3 n max_basis doubles, 2 n max_basis with
+ * M = I, plus a few n x 16 blocks).
+ *   d_values, d_mvalues  A's and M's values in A2 order, as parsy_factor_device takes them; M lives on the pattern of A,
+ *                        absent entries are stored zeros; d_mvalues NULL: M = I.
+ *   d_x0, ldx0, block    the start block, n x block column-major in the caller's ordering (parsy_plan_set_perm), as
+ *                        parsy_residual_device takes vectors; 1 <= block <= 16 is also the number of columns a step
+ *                        adds.  The library holds no random number generator: the same x0 gives the same bits.
+ *   lambda, resid        host, k entries: the eigenvalues ascending and eta_i = ||A y_i - lambda_i M y_i||_inf /
+ *                        ((||A||_inf + |lambda_i| ||M||_inf) ||y_i||_inf), the normwise backward error of the pair,
+ *                        computed from the RETURNED vectors by fresh products with `values` (not from kept quantities).
+ *   d_y, ldy             k columns, M-orthonormal, caller's ordering.
+ *   *nconv               host: the returned pairs with resid <= tol.
+ * Returns 0 when the loop ran: *nconv < k after max_iter iterations is not an error, the other pairs are the current
+ * Ritz pairs with their true eta (a pair the basis does not hold yet -- fewer than k columns after max_iter steps --
+ * comes back as lambda = NaN, resid = +inf and a zero column).  With *nconv == k every resid[i] <= tol.  -1: a refusal, a
+ * HIP error or a solve whose hand-off wait timed out.  -2: the Gram matrix of a block is not positive definite beyond
+ * the drop rule, which means M is not SPD; parsy_last_error names the iteration.
+ * Each step takes two projections against the basis and two passes of Cholesky-QR in the M inner product; in the first
+ * the Gram matrix is scaled to unit diagonal and a column whose pivot falls below 2^-26 is dropped (counted in
+ * `dropped`); if every column of a block is dropped the call ends as unconverged.
+ * STALE FACTOR: the expansion is (L L')^-1 (A y - theta M y), the residual of `values`, so lValues may be the factor of
+ * nearby values or of A - sigma M with sigma below the spectrum: the eigenpairs returned are those of `values` and
+ * d_mvalues, the factor only sets the number of iterations.
+ * Refused up front, with parsy_last_error set and the outputs untouched: what parsy_residual_device refuses; k < 1,
+ * block < 1, block > 16; max_basis > 128, > n or < k + 2 block (max_basis == 0: max(3 k, k + 4 block) clipped to
+ * min(n, 128), refused when that is below k + 2 block); max_iter < 1; tol < (max_row + 1) 2^-52 (max_row: most entries
+ * in a row of A), which an FP64 residual cannot show; a leading dimension < n; NULL pointers other than d_mvalues.
+ * SYNCHRONISATION: the small dense work -- a Jacobi eigensolver of the projected matrix, a Cholesky factor of a block's
+ * Gram matrix -- runs on the host: the stream is waited for four times per iteration (the projected matrix, the eta
+ * of the k wanted pairs, the Gram matrix of each Cholesky-QR pass), once more at a restart and before the returned pairs
+ * are formed (V'MV, which squares the rotation up), and the call returns with the stream idle.
+ * The feature's own kernels sum in fixed orders without atomics: given the same solve results the outputs are bitwise
+ * reproducible (the many-right-hand-side solves of a plan with wide supernodes add with float atomics and are not, as
+ * for the estimates above).  The first call allocates the workspace and
+ * adds it to the plan's device_bytes; it grows with max_basis. */
+typedef struct parsy_eigs_info {
+    int32_t iterations;     /* of the last call: expansions of the basis */
+    int32_t restarts;
+    int32_t nconv;
+    int32_t basis;          /* columns of V at return */
+    int32_t dropped;        /* columns the drop rule removed */
+    int32_t reserved;
+    int64_t solve_columns;  /* right-hand sides sent through forward + backward solve pairs */
+    int64_t device_bytes;   /* workspace held by this feature (0 before the first device call) */
+} parsy_eigs_info;
+int parsy_eigs_get_info(parsy_plan* plan, parsy_eigs_info* info);      /* host-only plans too */
+int parsy_eigs_device(parsy_plan* plan, const double* d_values, const double* d_mvalues, const double* d_lValues, int k,
+                      const double* d_x0, int ldx0, int block, double tol, int max_basis, int max_iter, double* lambda,
+                      double* d_y, int ldy, double* resid, int32_t* nconv, void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  Synchronous. */
+int parsy_eigs_host(parsy_plan* plan, const double* values, const double* mvalues, const double* lValues, int k,
+                    const double* x0, int ldx0, int block, double tol, int max_basis, int max_iter, double* lambda,
+                    double* y, int ldy, double* resid, int32_t* nconv, double* seconds);
+
 /* ---- Selected inversion: entries of A^-1 on the pattern of L, and log det A -------------------------------------
  * Z = (P A P')^-1 on the stored pattern of L by the Takahashi recurrences, level by level from the root of the tree of
  * the block columns (at most 64 columns of a supernode each).  Two kernel paths: a tiled one (FP64 MFMA, one workgroup

@@ -97,6 +97,7 @@ EXPORTED_SYMBOLS = [
     "parsy_factor_updown_device", "parsy_factor_updown_host", "parsy_updown_status", "parsy_updown_path", "parsy_updown_get_info",
     "parsy_factor_rowdel_device", "parsy_factor_rowadd_device", "parsy_factor_rowdel_host", "parsy_factor_rowadd_host",
     "parsy_rowmod_status", "parsy_rowmod_reach", "parsy_rowmod_get_info",
+    "parsy_eigs_get_info", "parsy_eigs_device", "parsy_eigs_host",
 ]
 
 
@@ -126,6 +127,16 @@ class RowmodInfo(C.Structure):
         ("last_op", C.c_int32), ("last_row", C.c_int32), ("reach_supernodes", C.c_int32), ("heights", C.c_int32),
         ("row_launches", C.c_int32), ("column_launches", C.c_int32), ("rotation_launches", C.c_int32),
         ("reserved", C.c_int32), ("entries_read", C.c_int64), ("entries_walked", C.c_int64), ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class EigsInfo(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32), ("restarts", C.c_int32), ("nconv", C.c_int32), ("basis", C.c_int32),
+        ("dropped", C.c_int32), ("reserved", C.c_int32), ("solve_columns", C.c_int64), ("device_bytes", C.c_int64),
     ]
 
     def as_dict(self):
@@ -279,6 +290,10 @@ def _declare(lib):
     lib.parsy_rowmod_status.argtypes = [vp]
     lib.parsy_rowmod_reach.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.parsy_rowmod_get_info.argtypes = [vp, vp]
+    lib.parsy_eigs_get_info.argtypes = [vp, vp]
+    eigs = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    lib.parsy_eigs_device.argtypes = eigs
+    lib.parsy_eigs_host.argtypes = eigs
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -340,6 +340,59 @@ class Plan:
             raise RuntimeError("parsy_rcond_host failed: " + N.last_error())
         return rc.value, an.value, sec.value
 
+    # the smallest eigenpairs of A v = lambda M v through the factor -------------------------------------------------
+    @property
+    def eigs_info(self) -> dict:
+        """Of the last eigs call: iterations, restarts, nconv, basis, dropped, solve_columns; device_bytes (0 before the
+        first device call)."""
+        ei = N.EigsInfo()
+        if N.lib().parsy_eigs_get_info(self._h, C.byref(ei)) != 0:
+            raise RuntimeError("parsy_eigs_get_info failed: " + N.last_error())
+        return ei.as_dict()
+
+    def eigs_device(self, d_values: int, d_mvalues: int, d_lValues: int, k: int, d_x0: int, ldx0: int, block: int,
+                    d_y: int, ldy: int, tol: float = 1e-10, max_basis: int = 0, max_iter: int = 200, stream: int = 0,
+                    lam=None, resid=None):
+        """parsy_eigs_device on device pointers (d_mvalues 0: M = I).  Returns (rc, lam, resid, nconv): rc 0, or -2 when
+        M is not SPD; every other failure raises.  lam / resid: float64 arrays of k entries to receive the results
+        (default: new ones)."""
+        lam = np.zeros(max(k, 0), dtype=np.float64) if lam is None else lam
+        resid = np.zeros(max(k, 0), dtype=np.float64) if resid is None else resid
+        nconv = C.c_int32(0)
+        rc = N.lib().parsy_eigs_device(self._h, d_values or None, d_mvalues or None, d_lValues or None, k, d_x0 or None,
+                                       ldx0, block, tol, max_basis, max_iter, N.ptr(lam), d_y or None, ldy, N.ptr(resid),
+                                       C.byref(nconv), stream)
+        if rc not in (0, -2):
+            raise RuntimeError("parsy_eigs_device failed: " + N.last_error())
+        return rc, lam, resid, nconv.value
+
+    def eigs(self, values, lValues, k: int, M=None, x0=None, tol: float = 1e-10, max_basis: int = 0, max_iter: int = 200):
+        """The k smallest eigenpairs of A v = lambda M v for the ORIGINAL matrices (caller's ordering, like
+        solve_refined; on first use the plan takes sym.Perm as its ordering).  values, M: A2 order (M None: the
+        identity); lValues: the factor of `values` or of values nearby.  x0: the start block (n, block), block <= 16;
+        None: numpy.random.default_rng(0).standard_normal((n, min(k, 8))).  Returns (lam, Y, info): lam ascending, Y
+        (n, k) M-orthonormal, info = eigs_info plus "resid", "nconv" and "seconds".  Raises when M is not SPD."""
+        if not getattr(self, "_perm_set", False):
+            self.set_perm(self.sym.Perm)
+            self._perm_set = True
+        n = self.sym.n
+        if x0 is None:
+            x0 = np.random.default_rng(0).standard_normal((n, min(max(k, 1), 8)))
+        X0 = np.asfortranarray(np.asarray(x0, dtype=np.float64).reshape(n, -1))
+        vals, lv = _f64(values), _f64(lValues)
+        mv = None if M is None else _f64(M)
+        lam, resid = np.zeros(max(k, 0)), np.zeros(max(k, 0))
+        Y = np.zeros((n, max(k, 0)), order="F")
+        nconv, sec = C.c_int32(0), C.c_double(0)
+        rc = N.lib().parsy_eigs_host(self._h, N.ptr(vals), N.ptr(mv), N.ptr(lv), k, X0.ctypes.data_as(C.c_void_p), n,
+                                     X0.shape[1], tol, max_basis, max_iter, N.ptr(lam), Y.ctypes.data_as(C.c_void_p), n,
+                                     N.ptr(resid), C.byref(nconv), C.byref(sec))
+        if rc != 0:
+            raise RuntimeError("parsy_eigs_host failed: " + N.last_error())
+        info = self.eigs_info
+        info.update(resid=resid, nconv=nconv.value, seconds=sec.value)
+        return lam, np.ascontiguousarray(Y), info
+
     # selected inversion: entries of A^-1 on the pattern of L, and log det A ------------------------------------
     @property
     def selinv_info(self) -> dict:

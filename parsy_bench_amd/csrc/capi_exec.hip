@@ -21,6 +21,7 @@
 #include "plan_util.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
+#include "eigs.hpp"
 #include "feature_states.hpp"
 
 using parsy::set_last_error;
@@ -741,6 +742,17 @@ int parsy_rcond_device(parsy_plan* pl, const double* d_values, const double* d_l
         return -1;
     }
     return parsy::plan_rcond(pl, d_values, d_lValues, anorm, rcond, (hipStream_t)stream);
+}
+
+int parsy_eigs_device(parsy_plan* pl, const double* d_values, const double* d_mvalues, const double* d_lValues, int k,
+                      const double* d_x0, int ldx0, int block, double tol, int max_basis, int max_iter, double* lambda,
+                      double* d_y, int ldy, double* resid, int32_t* nconv, void* stream) {
+    if (!pl || !d_values || !d_lValues || !d_x0 || !lambda || !d_y || !resid || !nconv) {
+        set_last_error("parsy_eigs_device: null argument (only d_mvalues may be NULL)");
+        return -1;
+    }
+    return parsy::plan_eigs(pl, d_values, d_mvalues, d_lValues, k, d_x0, ldx0, block, tol, max_basis, max_iter, lambda, d_y,
+                            ldy, resid, nconv, (hipStream_t)stream);
 }
 
 int parsy_factor_apply_device(parsy_plan* pl, const double* d_lValues, int op, const double* d_x, int ldx, int nrhs,

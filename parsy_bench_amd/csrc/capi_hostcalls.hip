@@ -19,6 +19,7 @@
 #include "plan_util.hpp"
 #include "refine.hpp"
 #include "cond.hpp"
+#include "eigs.hpp"
 #include "feature_states.hpp"
 
 using parsy::set_last_error;
@@ -334,6 +335,59 @@ int parsy_rcond_host(parsy_plan* pl, const double* values, const double* lValues
     }
     if (anorm) *anorm = an;
     if (rcond) *rcond = rc;
+    return 0;
+}
+
+int parsy_eigs_host(parsy_plan* pl, const double* values, const double* mvalues, const double* lValues, int k,
+                    const double* x0, int ldx0, int block, double tol, int max_basis, int max_iter, double* lambda, double* y,
+                    int ldy, double* resid, int32_t* nconv, double* seconds) {
+    const char* who = "parsy_eigs_host";
+    if (!pl || !values || !lValues || !x0 || !lambda || !y || !resid || !nconv) {
+        set_last_error(std::string(who) + ": null argument (only mvalues may be NULL)");
+        return -1;
+    }
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const parsy::Schedule& S = pl->S;
+    if (k < 1 || k > parsy::kEigsMaxBasis || block < 1 || block > parsy::kEigsMaxBlock || ldx0 < S.n || ldy < S.n) {
+        set_last_error(std::string(who) + ": need 1 <= k <= 128, 1 <= block <= 16 and leading dimensions >= n");
+        return -1;
+    }
+    PARSY_HIP(hipSetDevice(pl->device));
+    // x0 and Y share the staging buffer of the right-hand sides; M's values get one that lives as long as the call
+    const int64_t nx0 = (int64_t)S.n * block, ny = (int64_t)S.n * k;
+    PARSY_HIP(stage(pl, true, std::max<int64_t>(nx0 + ny, 1)));
+    parsy::DeviceBuf<double> m_dev;
+    if (mvalues) {
+        PARSY_HIP(m_dev.grow(std::max<int64_t>(S.nnzA, 1)));
+        PARSY_HIP(hipMemcpy(m_dev.data(), mvalues, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    }
+    const size_t row = (size_t)S.n * 8;
+    PARSY_HIP(hipMemcpy(pl->h_values_dev.data(), values, (size_t)S.nnzA * 8, hipMemcpyHostToDevice));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)S.xsize * 8, hipMemcpyHostToDevice));
+    double *dx0 = pl->h_x_dev.data(), *dy = dx0 + nx0;
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(dx0, row, x0, (size_t)ldx0 * 8, row, block, hipMemcpyHostToDevice));
+    parsy::EventTimer timer;
+    if (!timer.start()) {
+        set_last_error(std::string(who) + ": hipEventCreate failed");
+        return -1;
+    }
+    // (into locals: a refusal or a failure leaves the caller's outputs untouched)
+    std::vector<double> lam((size_t)k), res((size_t)k);
+    int32_t nc = 0;
+    const int rc = parsy::plan_eigs(pl, pl->h_values_dev.data(), mvalues ? m_dev.data() : nullptr, pl->h_L_dev.data(), k, dx0,
+                                    S.n, block, tol, max_basis, max_iter, lam.data(), dy, S.n, res.data(), &nc, nullptr);
+    if (rc != 0) {
+        (void)hipDeviceSynchronize();   // (m_dev is freed on return)
+        return rc;
+    }
+    if (!timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    if (S.n > 0) PARSY_HIP(hipMemcpy2D(y, (size_t)ldy * 8, dy, row, row, k, hipMemcpyDeviceToHost));
+    std::copy(lam.begin(), lam.end(), lambda);
+    std::copy(res.begin(), res.end(), resid);
+    *nconv = nc;
     return 0;
 }
 

@@ -33,8 +33,6 @@ namespace {
 constexpr int kCThreads = kRefineThreads;
 constexpr int kCondMaxApplications = 11;
 
-__device__ __forceinline__ u64 abs_bits(double v) { return (u64)__double_as_longlong(fabs(v)); }
-
 // dporfs's weight of a row, and |z| of the row for the column's max (z is read here, behind the sums)
 struct WeightOut : SweepScale {
     __device__ __forceinline__ u64 operator()(double* w, bool first, double b, double acc, double den,
@@ -46,27 +44,6 @@ struct WeightOut : SweepScale {
         return abs_bits(*zp);
     }
 };
-
-// ||A||_1 of the symmetric A: the largest row sum of |vf| (row sums = column sums), G lanes per row; part[blockIdx.x].
-// (Not an epilogue of the sweep: it reads neither ci nor z and sums with +=, where the sweep's sums are fma chains.)
-template <int G>
-__global__ __launch_bounds__(kCThreads) void k_sym_norm1(const int64_t* __restrict__ rp, const double* __restrict__ vf,
-                                                         int n, u64* __restrict__ part) {
-    __shared__ u64 sm[4];
-    const int tid = threadIdx.x, g = tid % G;
-    constexpr int kRows = kCThreads / G;
-    u64 mx = 0;
-    for (int64_t row = (int64_t)blockIdx.x * kRows + tid / G; row < n; row += (int64_t)gridDim.x * kRows) {
-        double s = 0.0;
-        const int64_t e1 = rp[row + 1];
-        for (int64_t e = rp[row] + g; e < e1; e += G) s += fabs(vf[e]);
-#pragma unroll
-        for (int o = G / 2; o; o >>= 1) s += __shfl_xor(s, o);
-        mx = max(mx, abs_bits(s));
-    }
-    const u64 v = block_max(mx, sm);
-    if (tid == 0) part[blockIdx.x] = v;
-}
 
 enum Produce { kZero, kUniform, kSigns, kUnit, kAlternating };
 
@@ -270,7 +247,7 @@ int cond_bounds_phase(parsy_plan* pl, const char* who, const double* d_L, int nr
     const double *pb = R.ws.data(), *z = pb + nn;
     double *w = C.ws.data(), *v = w + std::max<int64_t>(nn, 1);
     const CondCols c = cond_cols(C);
-    const int nb = sym_sweep_enqueue<WeightOut>(pl, z, pb, w, nrhs, c.part, stream);
+    const int nb = sym_sweep_enqueue<WeightOut>(pl, R.d_vf, z, pb, w, nrhs, c.part, stream);
     if (nb < 0) return -1;
     if (estimate(pl, who, d_L, v, w, nrhs, col_state(R, R.colstate_cap).ctl, stream) != 0) return -1;
     hipLaunchKernelGGL(k_cond_finish, dim3(nrhs), dim3(kCThreads), 0, stream, c.col, c.part, nb, c.out, 0);
@@ -294,7 +271,7 @@ int plan_error_bounds(parsy_plan* pl, const double* d_values, const double* d_L,
     double *pb = R.ws.data(), *z = pb + nn, *r = pb + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
     PARSY_HIP(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), stream));
-    if (refine_gather_values(pl, d_values, stream) != 0) return -1;
+    if (refine_gather_values(pl, d_values, R.d_vf, stream) != 0) return -1;
     enqueue_perm_gather(perm, d_x, ldx, z, nullptr, n, nrhs, stream);
     enqueue_perm_gather(perm, d_b, ldb, pb, nullptr, n, nrhs, stream);
     const int nb = refine_residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
@@ -322,7 +299,7 @@ int plan_rcond(parsy_plan* pl, const double* d_values, const double* d_L, double
     const CondCols c = cond_cols(C);
     PARSY_HIP(hipMemsetAsync(rc.ctl, 0, 2 * sizeof(int), stream));
     PARSY_HIP(hipMemsetAsync(c.col, 0, sizeof(CondCol), stream));
-    if (refine_gather_values(pl, d_values, stream) != 0) return -1;
+    if (refine_gather_values(pl, d_values, R.d_vf, stream) != 0) return -1;
     const int nb = sym_sweep_blocks(n, kCThreads / R.group);
     dispatch_int(R.group, SweepGroups(), [&](auto g) {
         hipLaunchKernelGGL(k_sym_norm1<decltype(g)::value>, dim3(nb), dim3(kCThreads), 0, stream, R.d_rp, R.d_vf, n, c.part);

@@ -21,6 +21,7 @@ struct CondState;
 struct ApplyState;
 struct UpdownState;
 struct RowmodState;
+struct EigsState;
 }
 
 struct parsy_plan {
@@ -109,6 +110,7 @@ struct parsy_plan {
     std::unique_ptr<parsy::ApplyState> apply;     // the factor as an operator (apply.hpp)
     std::unique_ptr<parsy::UpdownState> updown;   // update / downdate of the factor (updown.hpp)
     std::unique_ptr<parsy::RowmodState> rowmod;   // row delete / row add in the factor (rowmod.hpp)
+    std::unique_ptr<parsy::EigsState> eigs;       // smallest eigenpairs of A x = lambda M x (eigs.hpp)
 
     ~parsy_plan();   // (executor.hip, where the state types are complete)
 };

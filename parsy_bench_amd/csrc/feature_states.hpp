@@ -1,5 +1,5 @@
 // The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp,
-// rowmod.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
+// rowmod.hpp, eigs.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
 // each only once one of the feature's device calls has run.
 #pragma once
 #include "apply.hpp"
@@ -8,6 +8,8 @@
 #include "rowmod.hpp"
 #include "selinv.hpp"
 #include "updown.hpp"
+
+#include <vector>
 
 namespace parsy {
 
@@ -109,6 +111,25 @@ struct RowmodState {
     int last_op = 0, last_row = -1;   // 0: none yet, 1: delete, 2: add; the row in the factor's ordering
     int reach = 0, heights = 0, row_launches = 0, column_launches = 0, rotation_launches = 0;
     int64_t entries_read = 0, entries_walked = 0;
+};
+
+// Device state of the eigensolver (eigs.hpp, eigs_kernels.hip): made by the first parsy_eigs_device call, grown on demand.
+struct EigsState {
+    explicit EigsState(ByteMeter* plan) : meter(plan) {}
+    ByteMeter meter;                  // parsy_eigs_info.device_bytes: everything here, in the plan's figure too
+    DeviceBuf<double> vf_a{&meter};   // A's and M's values on the full symmetric pattern (RefineState's CSR), gathered once
+    DeviceBuf<double> vf_m{&meter};   // per call
+    DeviceBuf<double> basis{&meter};  // V, A V and (with an M) M V: n x max_basis each, leading dimension n
+    DeviceBuf<double> blocks{&meter}; // kEigsBlocks scratch blocks of n x 16
+    DeviceBuf<double> gram{&meter};   // the Gram kernel's partials, one p x q tile set per chunk of rows
+    DeviceBuf<double> dense{&meter};  // the small matrices the kernels read or write (eigs.hpp: EigsDense)
+    DeviceBuf<unsigned long long> part{&meter};   // partial maxima: kRefinePartials per column, two sets
+    DeviceBuf<int> ctl{&meter};       // {unused, status of the solves} as refine_solve_enqueue folds it
+    // of the last call
+    int32_t iterations = 0, restarts = 0, nconv = 0, basis_cols = 0, dropped = 0;
+    int64_t solve_columns = 0;
+    // host side of the small dense work; each is read by an asynchronous upload and rewritten only behind a wait
+    std::vector<double> h_g, h_s, h_st, h_theta, h_c1, h_c2, h_eta;
 };
 
 }  // namespace parsy

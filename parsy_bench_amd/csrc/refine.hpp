@@ -48,8 +48,8 @@ ColState col_state(RefineState& R, int cap);
 // ordering on the device (plan_perm_device)
 int refine_ensure_pattern(parsy_plan* pl);
 int refine_ensure_workspace(parsy_plan* pl, int nrhs, const int** perm);
-// vf = the caller's A2-order values on the full pattern
-int refine_gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream);
+// vf = the caller's A2-order values on the full pattern (vf: nnz_full doubles; the A x = b calls pass d_vf)
+int refine_gather_values(parsy_plan* pl, const double* d_values, double* vf, hipStream_t stream);
 // r = pb - A z and the partial maxima of every column's backward error; returns the number of partials (< 0: error)
 int refine_residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* r, int nrhs, u64* part,
                             hipStream_t stream);

@@ -193,13 +193,13 @@ int refine_ensure_workspace(parsy_plan* pl, int nrhs, const int** perm) {
 
 int refine_residual_enqueue(parsy_plan* pl, const double* z, const double* pb, double* r, int nrhs, u64* part,
                             hipStream_t stream) {
-    return sym_sweep_enqueue<ResidualOut>(pl, z, pb, r, nrhs, part, stream);
+    return sym_sweep_enqueue<ResidualOut>(pl, pl->refine->d_vf, z, pb, r, nrhs, part, stream);
 }
 
-int refine_gather_values(parsy_plan* pl, const double* d_values, hipStream_t stream) {
+int refine_gather_values(parsy_plan* pl, const double* d_values, double* vf, hipStream_t stream) {
     RefineState& R = *pl->refine;
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(8192, (R.nnz_full + kRThreads - 1) / kRThreads));
-    hipLaunchKernelGGL(k_refine_gather_values, dim3((unsigned)nb), dim3(kRThreads), 0, stream, d_values, R.d_src, R.d_vf,
+    hipLaunchKernelGGL(k_refine_gather_values, dim3((unsigned)nb), dim3(kRThreads), 0, stream, d_values, R.d_src, vf,
                        R.nnz_full);
     PARSY_HIP(hipGetLastError());
     return 0;
@@ -241,7 +241,7 @@ int plan_residual(parsy_plan* pl, const double* d_values, const double* d_x, int
     const int64_t nn = (int64_t)n * nrhs;
     double *pb = R.ws.data(), *z = pb + nn, *r = pb + 2 * nn;
     const ColState c = col_state(R, R.colstate_cap);
-    if (refine_gather_values(pl, d_values, stream) != 0) return -1;
+    if (refine_gather_values(pl, d_values, R.d_vf, stream) != 0) return -1;
     enqueue_perm_gather(perm, d_x, ldx, z, nullptr, n, nrhs, stream);
     enqueue_perm_gather(perm, d_b, ldb, pb, nullptr, n, nrhs, stream);
     const int nb = refine_residual_enqueue(pl, z, pb, r, nrhs, c.part, stream);
@@ -277,7 +277,7 @@ int plan_solve_refined(parsy_plan* pl, const double* d_values, const double* d_L
     enqueue_perm_gather(perm, d_b, ldb, pb, z, n, nrhs, stream);
     if (refine_solve_enqueue(pl, d_L, z, nrhs, c.ctl, stream) != 0) return -1;
     if (residuals) {
-        if (refine_gather_values(pl, d_values, stream) != 0) return -1;
+        if (refine_gather_values(pl, d_values, R.d_vf, stream) != 0) return -1;
         hipLaunchKernelGGL(k_refine_init, dim3((nrhs + 255) / 256), dim3(256), 0, stream, c.lstres, c.active, c.steps, nrhs);
         for (;;) {
             PARSY_HIP(hipMemsetAsync(c.ctl, 0, sizeof(int), stream));

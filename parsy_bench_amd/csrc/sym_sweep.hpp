@@ -5,7 +5,9 @@
 // order: a fixed lane split and a fixed butterfly, no float atomics, bitwise the same from run to run.  Maxima are
 // reduced as the bit patterns of non-negative doubles (an unsigned max: a NaN outranks every number and so survives
 // the reduction).
-// Device code: included by those two files only.
+// The products Y = A X of the eigensolver (eigs_kernels.hip) are a third epilogue.  The gathered values are an argument:
+// the A x = b calls pass RefineState::d_vf, the eigensolver one buffer for A and one for M.
+// Device code: included by those three files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,29 @@ __device__ __forceinline__ u64 block_max(u64 v, u64* sm) {
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
     __syncthreads();
     return max(max(sm[0], sm[1]), max(sm[2], sm[3]));
+}
+
+__device__ __forceinline__ u64 abs_bits(double v) { return (u64)__double_as_longlong(fabs(v)); }
+
+// ||A||_1 of the symmetric A: the largest row sum of |vf| (row sums = column sums), G lanes per row; part[blockIdx.x].
+// (Not an epilogue of the sweep: it reads neither ci nor z and sums with +=, where the sweep's sums are fma chains.)
+template <int G>
+__global__ __launch_bounds__(kRefineThreads) void k_sym_norm1(const int64_t* __restrict__ rp, const double* __restrict__ vf,
+                                                              int n, u64* __restrict__ part) {
+    __shared__ u64 sm[4];
+    const int tid = threadIdx.x, g = tid % G;
+    constexpr int kRows = kRefineThreads / G;
+    u64 mx = 0;
+    for (int64_t row = (int64_t)blockIdx.x * kRows + tid / G; row < n; row += (int64_t)gridDim.x * kRows) {
+        double s = 0.0;
+        const int64_t e1 = rp[row + 1];
+        for (int64_t e = rp[row] + g; e < e1; e += G) s += fabs(vf[e]);
+#pragma unroll
+        for (int o = G / 2; o; o >>= 1) s += __shfl_xor(s, o);
+        mx = max(mx, abs_bits(s));
+    }
+    const u64 v = block_max(mx, sm);
+    if (tid == 0) part[blockIdx.x] = v;
 }
 
 // dporfs's constants of a sweep, nz = 1 + the most entries in a row: nz eps, nz safmin, nz safmin / eps.  An Out is an
@@ -141,9 +166,10 @@ inline int sym_sweep_blocks(int n, int rows_per_block) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(kRefinePartials, ((int64_t)n + rows_per_block - 1) / rows_per_block));
 }
 
-// dst = Out of (pb, A z) and the partial maxima of every column; returns the number of partials per column (< 0: error)
+// dst = Out of (pb, A z), A's values on the full pattern in vf, and the partial maxima of every column; returns the number
+// of partials per column (< 0: error)
 template <class Out>
-int sym_sweep_enqueue(parsy_plan* pl, const double* z, const double* pb, double* dst, int nrhs, u64* part,
+int sym_sweep_enqueue(parsy_plan* pl, const double* vf, const double* z, const double* pb, double* dst, int nrhs, u64* part,
                       hipStream_t stream) {
     const RefineState& R = *pl->refine;
     const int n = pl->S.n;
@@ -155,7 +181,7 @@ int sym_sweep_enqueue(parsy_plan* pl, const double* z, const double* pb, double*
         dispatch_int(R.group, SweepGroups(), [&](auto g) {
             dispatch_int(nrhs, std::integer_sequence<int, 1, 2, 3, 4>(), [&](auto nr) {
                 hipLaunchKernelGGL((k_sym_sweep<decltype(g)::value, decltype(nr)::value, Out>), dim3(nb), threads, 0, stream,
-                                   R.d_rp, R.d_ci, R.d_vf, z, pb, dst, n, out, part);
+                                   R.d_rp, R.d_ci, vf, z, pb, dst, n, out, part);
             });
         });
         PARSY_HIP(hipGetLastError());
@@ -170,7 +196,7 @@ int sym_sweep_enqueue(parsy_plan* pl, const double* z, const double* pb, double*
     const int nb = sym_sweep_blocks(n, kRefineThreads / L);
     const dim3 grid(nb, (nrhs + L - 1) / L);
     dispatch_int(L, std::integer_sequence<int, 8, 16, 32, 64>(), [&](auto l) {
-        hipLaunchKernelGGL((k_sym_sweep_mrhs<decltype(l)::value, Out>), grid, threads, 0, stream, R.d_rp, R.d_ci, R.d_vf,
+        hipLaunchKernelGGL((k_sym_sweep_mrhs<decltype(l)::value, Out>), grid, threads, 0, stream, R.d_rp, R.d_ci, vf,
                            pl->xt.data(), ldq, pb, dst, n, nrhs, out, part);
     });
     PARSY_HIP(hipGetLastError());
