@@ -20,6 +20,7 @@
 #include "inspector.hpp"
 #include "plan_util.hpp"
 #include "refine.hpp"
+#include "schedule_digest.hpp"
 #include "cond.hpp"
 #include "eigs.hpp"
 #include "feature_states.hpp"
@@ -519,6 +520,19 @@ int64_t parsy_debug_launches(const parsy_plan* pl, int which, int32_t* out, int6
         std::copy(row, row + parsy::kLaunchFields, out + (size_t)parsy::kLaunchFields * i);
     }
     return (int64_t)seq.size();
+}
+
+// Diagnostics (tools/schedule_digests.py): the digest of the plan's whole schedule (schedule_digest.hpp) -- one 64-bit hash
+// per data member of parsy::Schedule, in declaration order.  Returns the number of fields; out / name (either may be
+// null) receive the hash and the member's name of field `field`, where that is one.
+int parsy_debug_schedule_digest(const parsy_plan* pl, int field, uint64_t* out, const char** name) {
+    if (!pl) return -1;
+    const parsy::ScheduleDigest d = parsy::schedule_digest(pl->S, field < 0 ? (1 << 30) : field);   // (no field: the count only)
+    if (field >= 0 && field < (int)d.size()) {
+        if (out) *out = d[(size_t)field].second;
+        if (name) *name = d[(size_t)field].first;
+    }
+    return (int)d.size();
 }
 
 // Diagnostics: the launches of the last collected profiled run as rows of (kind, level << 1 | side, work items, ms).

@@ -54,11 +54,127 @@ static int find_subtrees(const std::vector<int>& parent, const std::vector<uint8
     return count;
 }
 
-void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const int* A2i,
-                    const uint8_t* active, Schedule& S, int compute_units) {
-    S = Schedule();
-    // resident workgroups of the chain kernel = 2 per CU; walkers of one batch take at most a quarter
-    if (compute_units > 0) S.walker_batch = std::max(4, std::min(kWalkerBatch, compute_units / 2));
+namespace {
+
+// ---- The knobs of build_schedule: environment variables for diagnostics and tests.  read_build_knobs reads every one of
+// them once, at the top of every build_schedule call -- nothing is kept from one plan to the next (the tests change the
+// environment between two plans).  `_set`: that the variable is set at all matters, not only its value.
+struct BuildKnobs {
+    bool big_mink_set;       // PARSY_BIG_MINK: updates from descendants at least this wide go through the BIG launches (>= 1).
+    int big_mink;            //   Set: whatever the size of the job; unset: kBigMinK from kBigAutoFlops update flops on, else never
+    bool piece_width_set;    // PARSY_PIECE_WIDTH: columns of a piece of a very wide supernode (0: never split).
+    int piece_width;         //   Set: whatever the size of the job; unset: kPieceWidth from kPieceAutoFlops update flops on, else 0
+    int push_group;          // PARSY_PUSH_GROUP (kPushGroup, >= 1): pieces whose updates of the pieces further right are merged
+    bool split_chunks_set;   // PARSY_SPLIT_CHUNKS (kSplitChunks): early wave streams longer than this many 16-wide chunks are cut
+    int split_chunks;        //   into parts.  Set: this one rule on every level; unset: levels of few tiles cut finer (kSplitFew*)
+    int split_target;        // PARSY_SPLIT_TARGET (kSplitTarget, >= 1): ... into parts of about this length
+    int split_max;           // PARSY_SPLIT_MAX (kSplitMaxParts, >= 1): ... at most this many
+    bool subtrees_set;       // PARSY_SUBTREES (kSubtreesPerCu): subtrees aimed at per compute unit (0: none).  Set: always cut, and
+    int subtrees_per_cu;     //   the factorization aims at the same number; unset: only where there are enough eligible supernodes
+    int chol_subtrees_per_cu;   // PARSY_CHOL_SUBTREES (kCholSubtreesPerCu, >= 1): the factorization's aim where PARSY_SUBTREES is unset
+    int super_r, super_c;    // PARSY_BIG_SUPER=RxC | R (1..64 each): one super-tile edge for every BIG launch; 0 (unset): per launch
+    int64_t super_min_tasks; // PARSY_BIG_SUPER_MIN (kBigSuperMinTasks): launches of at least this many single-tile tasks ...
+    double super_max_fill;   // PARSY_BIG_SUPER_FILL (percent; kBigSuperMaxFill): ... whose windows are filled less than this ...
+    int super_hi;            // PARSY_BIG_SUPER_HI (2; 1..8): ... take super-tiles of this edge
+    int dense_mode;          // PARSY_BIG_DENSE (1): 0 = never k_chol_dense, 1 = by share, 2 = wherever there is a dense entry,
+                             //   3 = as 2 but never a launch's ragged entries too, 4 = every entry of every launch (tests)
+    double dense_min_share;  // PARSY_DENSE_MIN_SHARE (percent; kDenseMinShare): share of a launch's products that must be dense
+    double dense_all_share;  // PARSY_DENSE_ALL_SHARE (percent; kDenseAllShare): ragged share up to which k_chol_dense takes it too
+    int dense_fill_min;      // PARSY_DENSE_FILL (percent of 128 x 128; kDenseMinFill), in entries: windows this full count as dense
+    bool dense_strips;       // PARSY_DENSE_STRIPS (1): 0 = no strips ride with the dense blocks
+};
+
+BuildKnobs read_build_knobs() {
+    auto percent = [](const char* name, double dflt) { return env_int(name, (int)(dflt * 100 + 0.5)); };
+    BuildKnobs K{};
+    K.big_mink_set = std::getenv("PARSY_BIG_MINK") != nullptr;
+    K.big_mink = std::max(1, env_int("PARSY_BIG_MINK", kBigMinK));
+    K.piece_width_set = std::getenv("PARSY_PIECE_WIDTH") != nullptr;
+    K.piece_width = env_int("PARSY_PIECE_WIDTH", kPieceWidth);
+    K.push_group = std::max(1, env_int("PARSY_PUSH_GROUP", kPushGroup));
+    K.split_chunks_set = std::getenv("PARSY_SPLIT_CHUNKS") != nullptr;
+    K.split_chunks = env_int("PARSY_SPLIT_CHUNKS", kSplitChunks);
+    K.split_target = std::max(1, env_int("PARSY_SPLIT_TARGET", kSplitTarget));
+    K.split_max = std::max(1, env_int("PARSY_SPLIT_MAX", kSplitMaxParts));
+    K.subtrees_set = std::getenv("PARSY_SUBTREES") != nullptr;
+    K.subtrees_per_cu = env_int("PARSY_SUBTREES", kSubtreesPerCu);
+    K.chol_subtrees_per_cu = std::max(1, env_int("PARSY_CHOL_SUBTREES", kCholSubtreesPerCu));
+    if (const char* e = std::getenv("PARSY_BIG_SUPER")) {
+        int a = 0, b = 0;
+        const int got = std::sscanf(e, "%dx%d", &a, &b);
+        if (got >= 1 && a >= 1 && a <= 64) {
+            K.super_r = a;
+            K.super_c = (got == 2 && b >= 1 && b <= 64) ? b : a;
+        }
+    }
+    K.super_min_tasks = env_int("PARSY_BIG_SUPER_MIN", kBigSuperMinTasks);
+    K.super_max_fill = percent("PARSY_BIG_SUPER_FILL", kBigSuperMaxFill) / 100.0;
+    K.super_hi = std::max(1, std::min(8, env_int("PARSY_BIG_SUPER_HI", 2)));
+    K.dense_mode = env_int("PARSY_BIG_DENSE", 1);
+    K.dense_min_share = percent("PARSY_DENSE_MIN_SHARE", kDenseMinShare) / 100.0;
+    K.dense_all_share = percent("PARSY_DENSE_ALL_SHARE", kDenseAllShare) / 100.0;
+    K.dense_fill_min = percent("PARSY_DENSE_FILL", kDenseMinFill) * kBigTile * kBigTile / 100;
+    K.dense_strips = env_int("PARSY_DENSE_STRIPS", 1) != 0;
+    return K;
+}
+
+struct BigKeyed { int64_t launch_tile; WaveEntry e; int16_t sr, sc; };  // launch id << 40 | global tile index
+
+// What the passes of build_schedule hand to each other and is not part of the Schedule.
+struct BuildState {
+    BuildKnobs knobs;
+    int compute_units = 0;
+    std::vector<int> tree;                  // the supernodal etree (Schedule::sparent)
+    std::vector<int64_t> uptr, urel;        // update lists of the supernodes: [uptr[t], uptr[t + 1]) of (descendant usn, its rows
+    std::vector<int> usn, ulb, uub;         // lb .. ub inside the target's columns, offset urel into relpos of row lb)
+    std::vector<int8_t> launch_super;       // per BIG launch (source level * 2 + push): edge of its tasks' super-tiles
+    std::vector<int64_t> level_tiles;       // 64 x 64 tiles of the tiled pieces per level of the Cholesky view
+    std::vector<int64_t> big_tile0;         // first 128 x 128 tile index of every tiled piece
+    std::vector<BigKeyed> bigk;             // the BIG entries as they are found, keyed by (launch, tile)
+};
+
+// A run of an update's rows that falls into one window of the target's rows.
+struct RowRun { int32_t win, first, len; };
+
+// Row of target piece T's panel that row k (counted from lb) of update U lands on.
+inline int rel_at(const Schedule& S, const SnDesc& T, const UpdDesc& U, int k) {
+    return U.rel < 0 ? k : S.relpos[(size_t)U.rel + k] - T.rbias;
+}
+
+// The rows [0, U.m) of update U into piece T, cut into runs per window of `window` rows of T's panel.
+void row_runs(const Schedule& S, const SnDesc& T, const UpdDesc& U, int window, std::vector<RowRun>& out) {
+    out.clear();
+    for (int k = 0; k < U.m;) {
+        const int win = rel_at(S, T, U, k) / window;
+        int k1 = k + 1;
+        while (k1 < U.m && rel_at(S, T, U, k1) / window == win) ++k1;
+        out.push_back(RowRun{win, k, k1 - k});
+        k = k1;
+    }
+}
+
+// Updates that go through the BIG launches: wide descendants, and EVERY update of a split supernode's
+// pieces (what little reaches those from narrow descendants would otherwise be a TILES launch per
+// piece, in between the PUSH launches of the side stream).
+inline bool is_big(const Schedule& S, const UpdDesc& U, int target_piece) {
+    const int real = S.csn_real[target_piece];
+    return U.rel < 0 || U.K >= S.big_min_k || S.piece0[real + 1] - S.piece0[real] > 1;
+}
+
+// BIG launch of an update from a source on level lev_s into a target on level lev_t: NEXT(lev_s) | PUSH(lev_s)
+inline int64_t big_launch_of(int lev_s, int lev_t) { return (int64_t)lev_s * 2 + (lev_s == lev_t - 1 ? 0 : 1); }
+
+// The pairs (i, j), i >= j, of the block of rows [ia, ia + mi) x [ja, ja + nj) of a source: a block that straddles the
+// diagonal has fewer than mi * nj
+double block_pairs(int ia, int mi, int ja, int nj) {
+    double pairs = 0;
+    for (int jj = ja; jj < ja + nj; ++jj) pairs += std::max(0, ia + mi - std::max(ia, jj));
+    return pairs;
+}
+
+// Reads P, lC, A2p.  Fills the pattern's sizes, S.rows and the supernode descriptors S.sn (checking the panel layout),
+// max_width / max_rows, nnzL, flops_stored, n_dslots.
+void describe_supernodes(const PatternRef& P, const size_t* lC, const int* A2p, Schedule& S) {
     const int n = P.n, ns = P.nsuper;
     S.n = n;
     S.nsuper = ns;
@@ -67,7 +183,6 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
     S.rows.assign(P.s, P.s + P.i_ptr[n]);
     S.ssize = (int64_t)P.i_ptr[n];
     S.xsize = (int64_t)lC[n];
-    // --- supernode descriptors ------------------------------------------------
     S.sn.resize(ns);
     for (int t = 0; t < ns; ++t) {
         SnDesc& d = S.sn[t];
@@ -103,12 +218,15 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             S.n_dslots += ceil_div(d.w, kTile);
         }
     }
+}
 
-    // --- update lists of the supernodes, relative indices, A scatter map -----------
-    std::vector<int64_t> uptr(ns + 1, 0);
-    std::vector<int> usn, ulb, uub;
-    if (!S.solve_only) build_update_lists(P, uptr, usn, ulb, uub);
-    std::vector<int64_t> urel(usn.size(), 0);  // per (target, descendant): offset into relpos of row lb
+// Reads P, lC, A2p / A2i, S.sn, S.rows.  Fills the update lists of the supernodes (B.uptr / usn / ulb / uub), the relative
+// indices S.relpos with B.urel, the A scatter map S.a_dst, update_flops and reread_bytes.
+void list_updates(const PatternRef& P, const size_t* lC, const int* A2p, const int* A2i, Schedule& S, BuildState& B) {
+    const int n = P.n, ns = P.nsuper;
+    B.uptr.assign(ns + 1, 0);
+    if (!S.solve_only) build_update_lists(P, B.uptr, B.usn, B.ulb, B.uub);
+    B.urel.assign(B.usn.size(), 0);  // per (target, descendant): offset into relpos of row lb
     S.a_dst.assign((size_t)S.nnzA, 0);
     std::vector<int> map(n, -1), stamp(n, -1);
     for (int t = 0; t < ns; ++t) {
@@ -124,45 +242,49 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
                 if (stamp[row] != t) throw std::runtime_error("schedule: A entry outside the pattern of L");
                 S.a_dst[q] = (int64_t)lC[col] + map[row];
             }
-        for (int64_t u = uptr[t]; u < uptr[t + 1]; ++u) {
-            const SnDesc& D = S.sn[usn[u]];
-            urel[u] = (int64_t)S.relpos.size();
-            for (int k = ulb[u]; k < D.r; ++k) {
+        for (int64_t u = B.uptr[t]; u < B.uptr[t + 1]; ++u) {
+            const SnDesc& D = S.sn[B.usn[u]];
+            B.urel[u] = (int64_t)S.relpos.size();
+            for (int k = B.ulb[u]; k < D.r; ++k) {
                 const int row = S.rows[D.pi + k];
                 if (stamp[row] != t)
                     throw std::runtime_error("schedule: descendant row missing from the target's pattern");
                 S.relpos.push_back(map[row]);
             }
-            const double K = D.w, m = D.r - ulb[u], n1 = uub[u] - ulb[u] + 1;
+            const double K = D.w, m = D.r - B.ulb[u], n1 = B.uub[u] - B.ulb[u] + 1;
             S.update_flops += K * n1 * (n1 + 1) + 2.0 * K * (m - n1) * n1;
             S.reread_bytes += 8.0 * K * m;
         }
     }
     if (S.relpos.size() > 0x7fffffffULL) throw std::runtime_error("schedule: relative index array exceeds int32");
+}
 
-    // Which form the updates take follows the size of the job (measured on MI355X, 27-point grids with
-    // nested dissection): below about 1e11 update flops a factorization is a chain of latencies and the
-    // wave streams inside the chain launches are the shortest path; above it the LDS-staged BIG launches
-    // win (56^3 grid: 11.8 vs 13.1 ms); cutting the very wide supernodes into pieces pays from about 2e12
-    // (96^3 grid: 163 vs 174 ms).  PARSY_BIG_MINK / PARSY_PIECE_WIDTH override (diagnostics, tests).
+// Reads update_flops and the knobs.  Fills the sizes chosen by the job: big_min_k, piece_width, push_group.
+// Which form the updates take follows the size of the job (measured on MI355X, 27-point grids with
+// nested dissection): below about 1e11 update flops a factorization is a chain of latencies and the
+// wave streams inside the chain launches are the shortest path; above it the LDS-staged BIG launches
+// win (56^3 grid: 11.8 vs 13.1 ms); cutting the very wide supernodes into pieces pays from about 2e12
+// (96^3 grid: 163 vs 174 ms).  PARSY_BIG_MINK / PARSY_PIECE_WIDTH override (diagnostics, tests).
+void choose_sizes(Schedule& S, const BuildKnobs& K) {
     S.big_min_k = S.update_flops >= kBigAutoFlops ? kBigMinK : INT_MAX;
     S.piece_width = S.update_flops >= kPieceAutoFlops ? kPieceWidth : 0;
-    if (std::getenv("PARSY_BIG_MINK")) S.big_min_k = std::max(1, env_int("PARSY_BIG_MINK", kBigMinK));
-    if (std::getenv("PARSY_PIECE_WIDTH")) S.piece_width = env_int("PARSY_PIECE_WIDTH", kPieceWidth);
+    if (K.big_mink_set) S.big_min_k = K.big_mink;
+    if (K.piece_width_set) S.piece_width = K.piece_width;
     if (S.piece_width > 0) S.piece_width = ceil_div(std::max(S.piece_width, kBigTile), kBigTile) * kBigTile;
     if (S.piece_width < S.big_min_k) S.piece_width = 0;  // the pieces update each other through the BIG launches
-    S.push_group = std::max(1, env_int("PARSY_PUSH_GROUP", kPushGroup));
-    // (early wave streams longer than split_chunks 16-wide chunks are cut into parts of about split_target, at most split_max)
-    const int split_chunks = env_int("PARSY_SPLIT_CHUNKS", kSplitChunks), split_target = std::max(1, env_int("PARSY_SPLIT_TARGET", kSplitTarget)),
-              split_max = std::max(1, env_int("PARSY_SPLIT_MAX", kSplitMaxParts));
-    const bool split_env = std::getenv("PARSY_SPLIT_CHUNKS") != nullptr;   // (set: one rule for every level -- diagnostics)
+    S.push_group = K.push_group;
+}
 
-    std::vector<int> tree(P.sparent, P.sparent + ns);
-    S.sparent = tree;
-    level_sets(tree, S.levelPtr, S.levelSet);
+// Reads P.sparent, S.sn, piece_width.  Fills the etree and its level sets (sparent, levelPtr / levelSet, nlevels; B.tree)
+// and the Cholesky view: the pieces of the very wide supernodes (csn, piece0, csn_real) and their levels (clevelPtr /
+// clevelSet, cnlevels, level_of).
+void cut_pieces(const PatternRef& P, Schedule& S, BuildState& B) {
+    const int ns = S.nsuper;
+    B.tree.assign(P.sparent, P.sparent + ns);
+    S.sparent = B.tree;
+    level_sets(B.tree, S.levelPtr, S.levelSet);
     S.nlevels = (int)S.levelPtr.size() - 1;
 
-    // --- Cholesky view: pieces of the very wide supernodes -------------------------------
     S.piece0.assign(ns + 1, 0);
     for (int t = 0; t < ns; ++t) {
         const SnDesc& T = S.sn[t];
@@ -194,25 +316,29 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
         std::vector<int> ctree(nc, -1);
         for (int t = 0; t < ns; ++t)
             for (int p = S.piece0[t]; p < S.piece0[t + 1]; ++p)
-                ctree[p] = (p + 1 < S.piece0[t + 1]) ? p + 1 : (tree[t] >= 0 ? S.piece0[tree[t]] : -1);
+                ctree[p] = (p + 1 < S.piece0[t + 1]) ? p + 1 : (B.tree[t] >= 0 ? S.piece0[B.tree[t]] : -1);
         level_sets(ctree, S.clevelPtr, S.clevelSet);
     }
     S.cnlevels = (int)S.clevelPtr.size() - 1;
     S.level_of.assign(nc, 0);
     for (int l = 0; l < S.cnlevels; ++l)
         for (int q = S.clevelPtr[l]; q < S.clevelPtr[l + 1]; ++q) S.level_of[S.clevelSet[q]] = l;
+}
 
-    // --- update descriptors per piece: the supernode's descendants restricted to the piece's columns
-    // (reference order), then the pieces to its left (identity row map) ------------------------
+// Reads the update lists (B), S.sn, the pieces, push_group.  Fills the update descriptors per piece (upd, upd_src, and
+// upd0 / nupd of every piece): the supernode's descendants restricted to the piece's columns (reference order), then the
+// pieces to its left (identity row map).
+void describe_updates(Schedule& S, const BuildState& B) {
+    const int ns = S.nsuper;
     for (int t = 0; t < ns && !S.solve_only; ++t) {
         const SnDesc& T = S.sn[t];
         for (int p = S.piece0[t]; p < S.piece0[t + 1]; ++p) {
             SnDesc& C = S.csn[p];
             C.upd0 = (int64_t)S.upd.size();
             const int col_lo = C.c0, col_hi = C.c0 + C.w;
-            for (int64_t u = uptr[t]; u < uptr[t + 1]; ++u) {
-                const SnDesc& D = S.sn[usn[u]];
-                int lb = ulb[u], ub = uub[u];
+            for (int64_t u = B.uptr[t]; u < B.uptr[t + 1]; ++u) {
+                const SnDesc& D = S.sn[B.usn[u]];
+                int lb = B.ulb[u], ub = B.uub[u];
                 if (S.piece0[t + 1] - S.piece0[t] > 1) {
                     while (lb <= ub && S.rows[D.pi + lb] < col_lo) ++lb;
                     while (ub >= lb && S.rows[D.pi + ub] >= col_hi) --ub;
@@ -224,9 +350,9 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
                 U.K = D.w;
                 U.m = D.r - lb;
                 U.n1 = ub - lb + 1;
-                U.rel = urel[u] + (lb - ulb[u]);
+                U.rel = B.urel[u] + (lb - B.ulb[u]);
                 S.upd.push_back(U);
-                S.upd_src.push_back(S.piece0[usn[u] + 1] - 1);
+                S.upd_src.push_back(S.piece0[B.usn[u] + 1] - 1);
             }
             // the pieces to the left: the one right before this piece by itself (it is applied by the NEXT
             // launch of its level), the earlier ones in aligned groups of push_group pieces -- adjacent
@@ -252,19 +378,25 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             C.nupd = (int)((int64_t)S.upd.size() - C.upd0);
         }
     }
-    // --- subtrees walked by one workgroup each (see schedule.hpp).  Cost in flop equivalents: what the
-    // SMALL kernel executes plus a fixed amount per supernode and update (the small ones are latency);
-    // solves: panel entries.  The cap aims at kSubtreesPerCu subtrees per compute unit.
-    // A workgroup walks the supernodes of its subtree one after the other, siblings included, which level
-    // launches would run side by side: that only pays when the bottom of the etree saturates the device anyway
-    // (measured on MI355X: 45 000 narrow supernodes: factor -3 %, backward solve -7 %, forward solve -3 %;
-    // 1 300 .. 3 300 of them: +1 .. +9 % with subtrees), so by default subtrees are cut only where the
-    // eligible supernodes number at least kSubtreeMinPerSlot per subtree aimed at.
-    // PARSY_SUBTREES=k: always cut, aiming at k subtrees per compute unit (0: never; diagnostics, tests).
-    const bool forced = std::getenv("PARSY_SUBTREES") != nullptr;
-    const int per_cu = env_int("PARSY_SUBTREES", kSubtreesPerCu);
+}
+
+// Reads the etree (B.tree), S.sn, the pieces and their updates, the knobs, B.compute_units.  Fills the subtrees walked by
+// one workgroup each (see schedule.hpp): chol_ / solve_ / bsolve_subtree, chol_cost / solve_cost and the three counts.
+// Cost in flop equivalents: what the
+// SMALL kernel executes plus a fixed amount per supernode and update (the small ones are latency);
+// solves: panel entries.  The cap aims at kSubtreesPerCu subtrees per compute unit.
+// A workgroup walks the supernodes of its subtree one after the other, siblings included, which level
+// launches would run side by side: that only pays when the bottom of the etree saturates the device anyway
+// (measured on MI355X: 45 000 narrow supernodes: factor -3 %, backward solve -7 %, forward solve -3 %;
+// 1 300 .. 3 300 of them: +1 .. +9 % with subtrees), so by default subtrees are cut only where the
+// eligible supernodes number at least kSubtreeMinPerSlot per subtree aimed at.
+// PARSY_SUBTREES=k: always cut, aiming at k subtrees per compute unit (0: never; diagnostics, tests).
+void cut_subtrees(Schedule& S, const BuildState& B) {
+    const int ns = S.nsuper;
+    const bool forced = B.knobs.subtrees_set;
+    const int per_cu = B.knobs.subtrees_per_cu;
     if (per_cu > 0) {
-        const int cus = compute_units > 0 ? compute_units : 256;
+        const int cus = B.compute_units > 0 ? B.compute_units : 256;
         std::vector<uint8_t> elig(ns, 0);
         auto cut = [&](std::vector<double>& cost, double min_cost, std::vector<int32_t>& subtree,
                        const std::vector<std::pair<int32_t, int32_t>>* slots = nullptr, int64_t min_members = -1, int aim_per_cu = 0) {
@@ -272,7 +404,7 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             int64_t members = 0;
             {   // everything that could be in a subtree at all
                 std::vector<int32_t> all;
-                find_subtrees(tree, elig, cost, 1e300, all, slots, kSubMaxSlots);
+                find_subtrees(B.tree, elig, cost, 1e300, all, slots, kSubMaxSlots);
                 for (int t = 0; t < ns; ++t)
                     if (all[t] >= 0) {
                         total += cost[t];
@@ -280,7 +412,7 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
                     }
             }
             if (!forced && members < (min_members >= 0 ? min_members : (int64_t)kSubtreeMinPerSlot * per_cu * cus)) return 0;
-            return find_subtrees(tree, elig, cost, std::max(min_cost, total / ((double)(aim_per_cu > 0 ? aim_per_cu : per_cu) * cus)), subtree, slots,
+            return find_subtrees(B.tree, elig, cost, std::max(min_cost, total / ((double)(aim_per_cu > 0 ? aim_per_cu : per_cu) * cus)), subtree, slots,
                                  kSubMaxSlots);
         };
         if (!S.solve_only) {
@@ -296,8 +428,7 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             // (the factorization's subtrees aim at more, smaller ones than the threshold above counts with: a workgroup
             // keeps a whole panel in LDS, one or two per compute unit, and the launch runs alone on the device -- Flan-class
             // 3.8 -> 2.9 ms with 64 per unit, 3.2 with 128: profiles/r05_dense_thresholds.txt.  PARSY_CHOL_SUBTREES)
-            S.n_chol_subtrees = cut(S.chol_cost, kSubtreeMinCost, S.chol_subtree, nullptr, -1,
-                                    forced ? 0 : std::max(1, env_int("PARSY_CHOL_SUBTREES", kCholSubtreesPerCu)));
+            S.n_chol_subtrees = cut(S.chol_cost, kSubtreeMinCost, S.chol_subtree, nullptr, -1, forced ? 0 : B.knobs.chol_subtrees_per_cu);
         }
         S.solve_cost.assign(ns, 0.0);
         // solves: the subtrees of TINY supernodes (one wave walks one: the wave-per-supernode solve kernel)
@@ -317,55 +448,26 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
     if (S.chol_subtree.empty()) S.chol_subtree.assign(ns, -1);
     if (S.solve_subtree.empty()) S.solve_subtree.assign(ns, -1);
     if (S.bsolve_subtree.empty()) S.bsolve_subtree.assign(ns, -1);
+}
 
-    // Updates that go through the BIG launches: wide descendants, and EVERY update of a split supernode's
-    // pieces (what little reaches those from narrow descendants would otherwise be a TILES launch per
-    // piece, in between the PUSH launches of the side stream).
-    auto is_big = [&](const UpdDesc& U, int target_piece) {
-        const int real = S.csn_real[target_piece];
-        return U.rel < 0 || U.K >= S.big_min_k || S.piece0[real + 1] - S.piece0[real] > 1;
-    };
-
-    // --- tiled supernodes: scratch slots and the per-wave update streams ---------------
-    // Every (target, descendant) update is cut along the 32-row windows of the target's tiles:
-    // the descendant rows that fall into row window I32 times those (among its first n1 rows)
-    // that fall into column window J32 are one WaveEntry of sub-tile (I32, J32), I32 >= J32.
-    // Lists keep the reference's update order, so the sum order per entry of L is fixed.
-    // Updates from wide descendants (is_big) do not enter these lists: BIG launches below.
-    S.sn_wp0.assign(nc, -1);
-    S.sn_tw0.assign(nc, -1);
-    struct Group { int32_t win, first, len; };
-    std::vector<Group> groups, cgroups;
-    std::vector<int64_t> cursor;
-    struct BigKeyed { int64_t launch_tile; WaveEntry e; int16_t sr, sc; };  // launch id << 40 | global tile index
-    std::vector<BigKeyed> bigk;
-    std::vector<int64_t> big_tile0(nc + 1, 0);  // first 128x128 tile index of every tiled piece
-    // Edge of a BIG task's super-tile in 128 x 128 tiles, rows x columns, per launch (source level, kind).  A launch
-    // with many tasks whose 128 x 128 windows are mostly ragged (a 128-row window of the target holds about 64 rows of
-    // a typical source) takes 2 x 2 super-tiles -- a source's rows inside the larger windows are cut into FULL
-    // 128 x 128 blocks in its own row order: a quarter fewer chunks for the same products -- the others (pushes
-    // between the pieces of a separator: full windows anyway; launches of few tasks: they end with their longest
-    // task) stay with single tiles.  Measured per launch on the Flan-class input (tools/big_launches.py): early levels
-    // 10.7 -> 7.8 ms, the big pushes 37 -> 34 ms, launches below ~12 000 tasks 3-10 % slower with super-tiles.
-    // PARSY_BIG_SUPER=RxC (or R) forces one size everywhere (diagnostics, tests).
-    int env_sr = 0, env_sc = 0;
-    if (const char* e = std::getenv("PARSY_BIG_SUPER")) {
-        int a = 0, b = 0;
-        const int got = std::sscanf(e, "%dx%d", &a, &b);
-        if (got >= 1 && a >= 1 && a <= 64) {
-            env_sr = a;
-            env_sc = (got == 2 && b >= 1 && b <= 64) ? b : a;
-        }
-    }
-    std::vector<int8_t> launch_super((size_t)2 * std::max(S.cnlevels, 1), 1);
-    if (env_sr == 0 && !S.solve_only) {
-        // (PARSY_BIG_SUPER_MIN / PARSY_BIG_SUPER_FILL: the two thresholds, diagnostics; fill in percent)
-        const int64_t super_min_tasks = env_int("PARSY_BIG_SUPER_MIN", kBigSuperMinTasks);
-        const double super_max_fill = env_int("PARSY_BIG_SUPER_FILL", (int)(kBigSuperMaxFill * 100 + 0.5)) / 100.0;
-        const int super_hi = std::max(1, std::min(8, env_int("PARSY_BIG_SUPER_HI", 2)));   // (diagnostics: the edge such launches take)
-        std::vector<int64_t> ltasks(launch_super.size(), 0);
-        std::vector<double> lfrag(launch_super.size(), 0.0), lchunks(launch_super.size(), 0.0);
+// Reads the pieces, their updates and levels, the knobs.  Fills B.launch_super and big_super_r / _c.
+// Edge of a BIG task's super-tile in 128 x 128 tiles, rows x columns, per launch (source level, kind).  A launch
+// with many tasks whose 128 x 128 windows are mostly ragged (a 128-row window of the target holds about 64 rows of
+// a typical source) takes 2 x 2 super-tiles -- a source's rows inside the larger windows are cut into FULL
+// 128 x 128 blocks in its own row order: a quarter fewer chunks for the same products -- the others (pushes
+// between the pieces of a separator: full windows anyway; launches of few tasks: they end with their longest
+// task) stay with single tiles.  Measured per launch on the Flan-class input (tools/big_launches.py): early levels
+// 10.7 -> 7.8 ms, the big pushes 37 -> 34 ms, launches below ~12 000 tasks 3-10 % slower with super-tiles.
+// PARSY_BIG_SUPER=RxC (or R) forces one size everywhere (diagnostics, tests).
+void choose_super_tiles(Schedule& S, BuildState& B) {
+    const BuildKnobs& K = B.knobs;
+    const int nc = (int)S.csn.size();
+    B.launch_super.assign((size_t)2 * std::max(S.cnlevels, 1), 1);
+    if (K.super_r == 0 && !S.solve_only) {
+        std::vector<int64_t> ltasks(B.launch_super.size(), 0);
+        std::vector<double> lfrag(B.launch_super.size(), 0.0), lchunks(B.launch_super.size(), 0.0);
         std::vector<int64_t> keys;
+        std::vector<RowRun> runs;
         for (int t = 0; t < nc; ++t) {
             const SnDesc& T = S.csn[t];
             if (is_small(T)) continue;
@@ -373,23 +475,14 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             keys.clear();
             for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u) {
                 const UpdDesc& U = S.upd[u];
-                if (!is_big(U, t)) continue;
-                const int lev_s = S.level_of[S.upd_src[u]];
-                const int64_t launch = (int64_t)lev_s * 2 + (lev_s == lev_t - 1 ? 0 : 1);
-                groups.clear();
-                for (int k = 0; k < U.m;) {
-                    const int win = (U.rel < 0 ? k : S.relpos[(size_t)U.rel + k] - T.rbias) / kBigTile;
-                    int k1 = k + 1;
-                    if (U.rel < 0) k1 = std::min(U.m, (win + 1) * kBigTile);
-                    else while (k1 < U.m && (S.relpos[(size_t)U.rel + k1] - T.rbias) / kBigTile == win) ++k1;
-                    groups.push_back(Group{win, k, k1 - k});
-                    k = k1;
-                }
+                if (!is_big(S, U, t)) continue;
+                const int64_t launch = big_launch_of(S.level_of[S.upd_src[u]], lev_t);
+                row_runs(S, T, U, kBigTile, runs);
                 const double chunks = ceil_div(U.K, 16);
-                for (const Group& gc : groups) {
+                for (const RowRun& gc : runs) {
                     if (gc.first >= U.n1) break;
                     const int nj = std::min(gc.len, U.n1 - gc.first);
-                    for (const Group& gr : groups) {
+                    for (const RowRun& gr : runs) {
                         if (gr.win < gc.win) continue;
                         keys.push_back((launch << 40) | ((int64_t)gc.win * nbr128 + gr.win));
                         lfrag[(size_t)launch] += chunks * ceil_div(gr.len, 16) * ceil_div(nj, 16);
@@ -401,25 +494,126 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
             for (int64_t k : keys) ltasks[(size_t)(k >> 40)]++;
         }
-        for (size_t l = 0; l < launch_super.size(); ++l)
-            if (ltasks[l] >= super_min_tasks && lfrag[l] < super_max_fill * 64.0 * lchunks[l]) launch_super[l] = (int8_t)super_hi;
+        for (size_t l = 0; l < B.launch_super.size(); ++l)
+            if (ltasks[l] >= K.super_min_tasks && lfrag[l] < K.super_max_fill * 64.0 * lchunks[l]) B.launch_super[l] = (int8_t)K.super_hi;
     }
-    S.big_super_r = env_sr;
-    S.big_super_c = env_sc;
+    S.big_super_r = K.super_r;
+    S.big_super_c = K.super_c;
+}
+
+// Reads one tiled piece t and its updates that are not BIG.  Fills its wave streams (wave_entries, wave_ptr, sn_wp0[t]).
+// Every (target, descendant) update is cut along the 32-row windows of the target's tiles:
+// the descendant rows that fall into row window I32 times those (among its first n1 rows)
+// that fall into column window J32 are one WaveEntry of sub-tile (I32, J32), I32 >= J32.
+// Lists keep the reference's update order, so the sum order per entry of L is fixed.
+// Updates from wide descendants (is_big) do not enter these lists: the BIG entries.
+void piece_wave_streams(Schedule& S, int t, std::vector<RowRun>& runs, std::vector<int64_t>& cursor) {
+    const SnDesc& T = S.csn[t];
+    const int nbc = ceil_div(T.w, kTile), nbr = ceil_div(T.r, kTile), lev_t = S.level_of[t];
+    // key of a list: ((J * nbr + I) * 2 + phase) * 4 + wave
+    const size_t nkeys = (size_t)nbc * nbr * 8;
+    auto for_each_entry = [&](auto&& fn) {
+        for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u) {
+            const UpdDesc& U = S.upd[u];
+            if (is_big(S, U, t)) continue;
+            // early: the descendant is complete before the level below the target even starts
+            const int phase = (S.level_of[S.upd_src[u]] <= lev_t - 2) ? 0 : 1;
+            row_runs(S, T, U, kSub, runs);
+            for (const RowRun& gc : runs) {
+                if (gc.first >= U.n1) break;
+                const int nj = std::min(gc.len, U.n1 - gc.first);
+                for (const RowRun& gr : runs) {
+                    if (gr.win < gc.win) continue;
+                    const int I = gr.win / 2, J = gc.win / 2;
+                    const size_t key = (((size_t)J * nbr + I) * 2 + phase) * 4 + (gr.win & 1) * 2 + (gc.win & 1);
+                    fn(key, U, gr.first, gr.len, gc.first, nj);
+                }
+            }
+        }
+    };
+    cursor.assign(nkeys + 1, 0);
+    for_each_entry([&](size_t key, const UpdDesc&, int, int, int, int) { cursor[key + 1]++; });
+    const int64_t base = (int64_t)S.wave_entries.size();
+    for (size_t k = 0; k < nkeys; ++k) cursor[k + 1] += cursor[k];
+    S.sn_wp0[t] = (int64_t)S.wave_ptr.size();
+    for (size_t k = 0; k <= nkeys; ++k) S.wave_ptr.push_back(base + cursor[k]);
+    S.wave_entries.resize((size_t)(base + cursor[nkeys]));
+    for_each_entry([&](size_t key, const UpdDesc& U, int ia, int mi, int ja, int nj) {
+        S.wave_entries[(size_t)(base + cursor[key]++)] =
+            WaveEntry{U.src, (int32_t)U.rel, U.ld, U.K, ia, ja, mi | (nj << 8)};
+    });
+}
+
+// Reads one tiled piece t's wave streams, B.level_tiles, the split knobs.  Fills the weight of its tiles (tile_w, sn_tw0[t])
+// = 16-wide k chunks of a tile's longest wave stream, and the splits of its long early streams (tile_split, split_desc,
+// split_ranges, n_split_doubles).
+void piece_tile_weights(Schedule& S, const BuildState& B, int t) {
+    const BuildKnobs& K = B.knobs;
+    const SnDesc& T = S.csn[t];
+    const int nbc = ceil_div(T.w, kTile), nbr = ceil_div(T.r, kTile), lev_t = S.level_of[t];
+    S.sn_tw0[t] = (int64_t)S.tile_w.size();
+    S.tile_w.resize(S.tile_w.size() + (size_t)nbc * nbr * 2, 0);
+    S.tile_split.resize(S.tile_w.size() / 2, -1);
+    int32_t* tw = &S.tile_w[S.sn_tw0[t]];
+    int64_t* tsplit = &S.tile_split[S.sn_tw0[t] / 2];
+    const int64_t* wp = &S.wave_ptr[S.sn_wp0[t]];
+    for (size_t tp = 0; tp < (size_t)nbc * nbr * 2; ++tp) {
+        int64_t wchunks[4];
+        for (int q = 0; q < 4; ++q) {
+            int64_t chunks = 0;
+            for (int64_t e = wp[tp * 4 + q]; e < wp[tp * 4 + q + 1]; ++e)
+                chunks += ceil_div(S.wave_entries[(size_t)e].K, 16);
+            wchunks[q] = chunks;
+            tw[tp] = std::max<int32_t>(tw[tp], (int32_t)std::min<int64_t>(chunks, INT32_MAX));
+        }
+        // A launch ends with its longest wave stream: long EARLY streams are cut into parts that
+        // separate workgroups apply to partial tiles (summed, in a fixed order, when the chain
+        // launch loads the tile).  Every wave's list is cut where its own chunk count reaches p/nparts.
+        // (PARSY_SPLIT_CHUNKS set: one rule for every level -- diagnostics)
+        const bool few = B.level_tiles[(size_t)lev_t] <= kSplitFewTiles && !K.split_chunks_set;
+        if ((tp & 1) == 0 && tw[tp] > (few ? kSplitFewChunks : K.split_chunks)) {
+            const int nparts = few ? std::min<int>(kSplitFewMaxParts, ceil_div(tw[tp], kSplitFewTarget))
+                                   : std::min<int>(K.split_max, ceil_div(tw[tp], K.split_target));
+            Schedule::SplitDesc sd{(int64_t)S.split_ranges.size(), S.n_split_doubles, nparts, 0};
+            S.n_split_doubles += (int64_t)(nparts - 1) * kTile * kTile;
+            S.split_ranges.resize(S.split_ranges.size() + (size_t)nparts * 8, 0);
+            int64_t* rg = &S.split_ranges[(size_t)sd.ranges];
+            for (int q = 0; q < 4; ++q) {
+                int64_t e = wp[tp * 4 + q], done = 0;
+                for (int part = 0; part < nparts; ++part) {
+                    rg[part * 8 + 2 * q] = e;
+                    const int64_t goal = wchunks[q] * (part + 1) / nparts;
+                    while (e < wp[tp * 4 + q + 1] && (part == nparts - 1 || done < goal))
+                        done += ceil_div(S.wave_entries[(size_t)e++].K, 16);
+                    rg[part * 8 + 2 * q + 1] = e;
+                }
+            }
+            tsplit[tp / 2] = (int64_t)S.split_desc.size();
+            S.split_desc.push_back(sd);
+        }
+    }
+}
+
+// Reads the pieces, their updates and levels.  Fills, per tiled piece: the tile flags (tflag0, n_tflags), inner_flops, the wave
+// streams, the tile weights and the splits (the two functions above); n_small / n_big; B.level_tiles.
+void build_wave_streams(Schedule& S, BuildState& B) {
+    const int nc = (int)S.csn.size();
+    S.sn_wp0.assign(nc, -1);
+    S.sn_tw0.assign(nc, -1);
     // tiles per level: a level with few of them leaves the device empty while its longest early stream runs (ex15-class:
     // 2 - 12 workgroups for 47 - 76 us per level, the critical path of the upper half of the tree) -- there the streams
     // are cut finer (kSplitFew*)
-    std::vector<int64_t> level_tiles((size_t)std::max(S.cnlevels, 1), 0);
-    if (!S.solve_only)
-        for (int t = 0; t < nc; ++t)
-            if (!is_small(S.csn[t])) {
-                const int nbc = ceil_div(S.csn[t].w, kTile), nbr = ceil_div(S.csn[t].r, kTile);
-                level_tiles[(size_t)S.level_of[t]] += (int64_t)nbc * nbr - (int64_t)nbc * (nbc - 1) / 2;
-            }
+    B.level_tiles.assign((size_t)std::max(S.cnlevels, 1), 0);
+    if (S.solve_only) return;
+    for (int t = 0; t < nc; ++t)
+        if (!is_small(S.csn[t])) {
+            const int nbc = ceil_div(S.csn[t].w, kTile), nbr = ceil_div(S.csn[t].r, kTile);
+            B.level_tiles[(size_t)S.level_of[t]] += (int64_t)nbc * nbr - (int64_t)nbc * (nbc - 1) / 2;
+        }
+    std::vector<RowRun> runs;
+    std::vector<int64_t> cursor;
     for (int t = 0; t < nc; ++t) {
         SnDesc& T = S.csn[t];
-        big_tile0[t + 1] = big_tile0[t];
-        if (S.solve_only) continue;
         if (is_small(T)) {
             S.n_small++;
             continue;
@@ -433,292 +627,251 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
             const double K = (double)jb * kTile, wb = std::min(kTile, T.w - jb * kTile);
             S.inner_flops += K * wb * (wb + 1) + 2.0 * K * (double)(T.r - jb * kTile - wb) * wb;
         }
+        piece_wave_streams(S, t, runs, cursor);
+        piece_tile_weights(S, B, t);
+    }
+}
+
+// Reads the pieces, their updates and levels, B.launch_super.  Fills the BIG entries as they are found, keyed by (launch,
+// tile): B.bigk, B.big_tile0; big_flops and tile_update_flops (the updates that are not BIG).
+// BIG: the wide descendants, cut along the 128-row windows of the target's panel
+void collect_big_entries(Schedule& S, BuildState& B) {
+    const int nc = (int)S.csn.size();
+    const int env_sr = B.knobs.super_r, env_sc = B.knobs.super_c;
+    B.big_tile0.assign((size_t)nc + 1, 0);
+    std::vector<RowRun> runs, cruns;
+    for (int t = 0; t < nc; ++t) {
+        const SnDesc& T = S.csn[t];
+        B.big_tile0[t + 1] = B.big_tile0[t];
+        if (S.solve_only || is_small(T)) continue;
         const int lev_t = S.level_of[t];
-        auto rel_at = [&](const UpdDesc& U, int k) { return U.rel < 0 ? k : S.relpos[(size_t)U.rel + k] - T.rbias; };
-        // key of a list: ((J * nbr + I) * 2 + phase) * 4 + wave
-        const size_t nkeys = (size_t)nbc * nbr * 8;
-        auto for_each_entry = [&](auto&& fn) {
-            for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u) {
-                const UpdDesc& U = S.upd[u];
-                if (is_big(U, t)) continue;
-                // early: the descendant is complete before the level below the target even starts
-                const int phase = (S.level_of[S.upd_src[u]] <= lev_t - 2) ? 0 : 1;
-                groups.clear();
-                for (int k = 0; k < U.m;) {
-                    const int win = rel_at(U, k) / kSub;
-                    int k1 = k + 1;
-                    while (k1 < U.m && rel_at(U, k1) / kSub == win) ++k1;
-                    groups.push_back(Group{win, k, k1 - k});
-                    k = k1;
-                }
-                for (const Group& gc : groups) {
-                    if (gc.first >= U.n1) break;
-                    const int nj = std::min(gc.len, U.n1 - gc.first);
-                    for (const Group& gr : groups) {
-                        if (gr.win < gc.win) continue;
-                        const int I = gr.win / 2, J = gc.win / 2;
-                        const size_t key = (((size_t)J * nbr + I) * 2 + phase) * 4 + (gr.win & 1) * 2 + (gc.win & 1);
-                        fn(key, U, gr.first, gr.len, gc.first, nj);
-                    }
-                }
-            }
-        };
-        cursor.assign(nkeys + 1, 0);
-        for_each_entry([&](size_t key, const UpdDesc&, int, int, int, int) { cursor[key + 1]++; });
-        const int64_t base = (int64_t)S.wave_entries.size();
-        for (size_t k = 0; k < nkeys; ++k) cursor[k + 1] += cursor[k];
-        S.sn_wp0[t] = (int64_t)S.wave_ptr.size();
-        for (size_t k = 0; k <= nkeys; ++k) S.wave_ptr.push_back(base + cursor[k]);
-        S.wave_entries.resize((size_t)(base + cursor[nkeys]));
-        for_each_entry([&](size_t key, const UpdDesc& U, int ia, int mi, int ja, int nj) {
-            S.wave_entries[(size_t)(base + cursor[key]++)] =
-                WaveEntry{U.src, (int32_t)U.rel, U.ld, U.K, ia, ja, mi | (nj << 8)};
-        });
-        // ---- BIG: the wide descendants, cut along the 128-row windows of the target's panel
         const int nbr128 = ceil_div(T.r, kBigTile), nbc128 = ceil_div(T.w, kBigTile);
-        big_tile0[t + 1] = big_tile0[t] + (int64_t)nbr128 * nbc128;
+        B.big_tile0[t + 1] = B.big_tile0[t] + (int64_t)nbr128 * nbc128;
         for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u) {
             const UpdDesc& U = S.upd[u];
             const double f = (double)U.K * U.n1 * (U.n1 + 1) + 2.0 * U.K * (double)(U.m - U.n1) * U.n1;
-            if (!is_big(U, t)) {
+            if (!is_big(S, U, t)) {
                 S.tile_update_flops += f;
                 continue;
             }
             S.big_flops += f;
             const int lev_s = S.level_of[S.upd_src[u]];
             if (lev_s >= lev_t) throw std::runtime_error("schedule: an update source is not below its target");
-            const int64_t launch = (int64_t)lev_s * 2 + (lev_s == lev_t - 1 ? 0 : 1);
-            const int sr = env_sr ? env_sr : launch_super[(size_t)launch], sc = env_sr ? env_sc : launch_super[(size_t)launch];
+            const int64_t launch = big_launch_of(lev_s, lev_t);
+            const int sr = env_sr ? env_sr : B.launch_super[(size_t)launch], sc = env_sr ? env_sc : B.launch_super[(size_t)launch];
             // A task owns a SUPER-TILE of sr x sc 128 x 128 tiles of the target.  The source's rows inside the
             // super-tile's row window (a run of its panel rows) times its rows inside the column window are cut into
             // 128 x 128 blocks IN THE SOURCE'S ROW ORDER -- full blocks but for the last of a run -- one entry each:
             // a 128-row window of the target holds only about 64 rows of a typical source (a face of a sub-box on a
             // separator plane), so per-tile windows were two-thirds ragged (tools/big_stats.py).  The blocks of one
             // source touch different entries of L; the sources stay in update order.
-            auto make_groups = [&](int win_rows, std::vector<Group>& out) {
-                out.clear();
-                for (int k = 0; k < U.m;) {
-                    const int win = rel_at(U, k) / win_rows;
-                    int k1 = k + 1;
-                    if (U.rel < 0) k1 = std::min(U.m, (win + 1) * win_rows);
-                    else while (k1 < U.m && rel_at(U, k1) / win_rows == win) ++k1;
-                    out.push_back(Group{win, k, k1 - k});
-                    k = k1;
-                }
-            };
-            make_groups(kBigTile * sr, groups);
-            if (sc == sr) cgroups = groups;
-            else make_groups(kBigTile * sc, cgroups);
-            for (const Group& gc : cgroups) {
+            row_runs(S, T, U, kBigTile * sr, runs);
+            if (sc == sr) cruns = runs;
+            else row_runs(S, T, U, kBigTile * sc, cruns);
+            for (const RowRun& gc : cruns) {
                 if (gc.first >= U.n1) break;
                 const int njt = std::min(gc.len, U.n1 - gc.first);
-                for (const Group& gr : groups) {
+                for (const RowRun& gr : runs) {
                     // (the target's rows ascend with the source's: a window strictly above the diagonal holds nothing)
                     if ((int64_t)(gr.win + 1) * sr * kBigTile - 1 < (int64_t)gc.win * sc * kBigTile) continue;
-                    const int64_t tile = big_tile0[t] + (int64_t)gc.win * sc * nbr128 + (int64_t)gr.win * sr;
+                    const int64_t tile = B.big_tile0[t] + (int64_t)gc.win * sc * nbr128 + (int64_t)gr.win * sr;
                     for (int cb = 0; cb < njt; cb += kBigTile)
                         for (int rb = 0; rb < gr.len; rb += kBigTile) {
                             const int mi = std::min(kBigTile, gr.len - rb), nj = std::min(kBigTile, njt - cb);
                             const int ia = gr.first + rb, ja = gc.first + cb;
                             if (ia + mi - 1 < ja) continue;   // block strictly above the diagonal
-                            bigk.push_back(BigKeyed{(launch << 40) | tile,
-                                                    WaveEntry{U.src, (int32_t)std::max<int64_t>(U.rel, 0), U.ld, U.K, ia, ja,
-                                                              mi | (nj << 8) | ((U.rel < 0) << 16)},
-                                                    (int16_t)sr, (int16_t)sc});
+                            B.bigk.push_back(BigKeyed{(launch << 40) | tile,
+                                                      WaveEntry{U.src, (int32_t)std::max<int64_t>(U.rel, 0), U.ld, U.K, ia, ja,
+                                                                mi | (nj << 8) | ((U.rel < 0) << 16)},
+                                                      (int16_t)sr, (int16_t)sc});
                         }
                 }
             }
         }
-        // weight of every tile = 16-wide k chunks of its longest wave stream
-        S.sn_tw0[t] = (int64_t)S.tile_w.size();
-        S.tile_w.resize(S.tile_w.size() + (size_t)nbc * nbr * 2, 0);
-        S.tile_split.resize(S.tile_w.size() / 2, -1);
-        int32_t* tw = &S.tile_w[S.sn_tw0[t]];
-        int64_t* tsplit = &S.tile_split[S.sn_tw0[t] / 2];
-        const int64_t* wp = &S.wave_ptr[S.sn_wp0[t]];
-        for (size_t tp = 0; tp < (size_t)nbc * nbr * 2; ++tp) {
-            int64_t wchunks[4];
-            for (int q = 0; q < 4; ++q) {
-                int64_t chunks = 0;
-                for (int64_t e = wp[tp * 4 + q]; e < wp[tp * 4 + q + 1]; ++e)
-                    chunks += ceil_div(S.wave_entries[(size_t)e].K, 16);
-                wchunks[q] = chunks;
-                tw[tp] = std::max<int32_t>(tw[tp], (int32_t)std::min<int64_t>(chunks, INT32_MAX));
-            }
-            // A launch ends with its longest wave stream: long EARLY streams are cut into parts that
-            // separate workgroups apply to partial tiles (summed, in a fixed order, when the chain
-            // launch loads the tile).  Every wave's list is cut where its own chunk count reaches p/nparts.
-            const bool few = level_tiles[(size_t)lev_t] <= kSplitFewTiles && !split_env;
-            if ((tp & 1) == 0 && tw[tp] > (few ? kSplitFewChunks : split_chunks)) {
-                const int nparts = few ? std::min<int>(kSplitFewMaxParts, ceil_div(tw[tp], kSplitFewTarget))
-                                       : std::min<int>(split_max, ceil_div(tw[tp], split_target));
-                Schedule::SplitDesc sd{(int64_t)S.split_ranges.size(), S.n_split_doubles, nparts, 0};
-                S.n_split_doubles += (int64_t)(nparts - 1) * kTile * kTile;
-                S.split_ranges.resize(S.split_ranges.size() + (size_t)nparts * 8, 0);
-                int64_t* rg = &S.split_ranges[(size_t)sd.ranges];
-                for (int q = 0; q < 4; ++q) {
-                    int64_t e = wp[tp * 4 + q], done = 0;
-                    for (int part = 0; part < nparts; ++part) {
-                        rg[part * 8 + 2 * q] = e;
-                        const int64_t goal = wchunks[q] * (part + 1) / nparts;
-                        while (e < wp[tp * 4 + q + 1] && (part == nparts - 1 || done < goal))
-                            done += ceil_div(S.wave_entries[(size_t)e++].K, 16);
-                        rg[part * 8 + 2 * q + 1] = e;
-                    }
-                }
-                tsplit[tp / 2] = (int64_t)S.split_desc.size();
-                S.split_desc.push_back(sd);
-            }
-        }
     }
-    // ---- BIG tasks: one per (launch, tile), entries in update order (stable sort)
-    if (!bigk.empty()) {
-        std::stable_sort(bigk.begin(), bigk.end(),
-                         [](const BigKeyed& a, const BigKeyed& b) { return a.launch_tile < b.launch_tile; });
-        // Dense entries: full 128 x 128 blocks of the source's rows (on or below the target's diagonal; a block that
-        // straddles it -- the diagonal blocks of the pushes between a separator's pieces -- is multiplied whole and its
-        // upper part dropped when the tile is updated: 1.4 % more products there, and no ragged launch of a few hundred
-        // diagonal blocks behind every such push).  A launch hands them to k_chol_dense when
-        // they carry at least kDenseMinShare of its products; decided per launch over ALL targets, so that the order of
-        // sums does not depend on which pieces a rank owns.
-        auto is_full = [](const WaveEntry& E) {
-            const int mi = E.mn & 255, nj = (E.mn >> 8) & 255;
-            return mi == kBigTile && nj == kBigTile && E.K >= kDenseChunk;
-        };
-        const int dense_mode = env_int("PARSY_BIG_DENSE", 1);
-        std::vector<double> lprod(launch_super.size(), 0.0), ldense(launch_super.size(), 0.0);
-        auto products_of = [](const WaveEntry& E) {
-            const int mi = E.mn & 255, nj = (E.mn >> 8) & 255;
-            return (double)ceil_div(E.K, 4) * ceil_div(mi, 16) * ceil_div(nj, 16);
-        };
-        for (const BigKeyed& b : bigk) {
-            const size_t l = (size_t)(b.launch_tile >> 40);
-            lprod[l] += products_of(b.e);
-            if (is_full(b.e)) ldense[l] += products_of(b.e);
-        }
-        // per launch: 0 = k_chol_big only; 1 = full blocks to k_chol_dense, the rest to k_chol_big; 2 = everything to
-        // k_chol_dense (it multiplies a ragged window as a whole block and drops what the window does not have) --
-        // where the ragged rest is so small (the last, partial row block of the pushes between a separator's pieces: a
-        // handful of tasks) that a launch of its own would cost more than the wasted products: measured 0.07 - 0.1 ms
-        // per such launch, 110 of them per Flan-class factorization
-        std::vector<uint8_t> launch_dense(launch_super.size(), 0);
-        for (size_t l = 0; l < launch_dense.size(); ++l) {
-            if (dense_mode == 4) {   // (tests: every entry of every launch through k_chol_dense, ragged windows and all)
-                launch_dense[l] = lprod[l] > 0 ? 2 : 0;
-                continue;
-            }
-            if (dense_mode == 0 || ldense[l] <= 0) continue;
-            if (dense_mode >= 2 || ldense[l] >= kDenseMinShare * lprod[l]) launch_dense[l] = 1;
-            if (launch_dense[l] && lprod[l] - ldense[l] <= kDenseAllShare * lprod[l] && dense_mode != 3) launch_dense[l] = 2;
-        }
-        // (PARSY_DENSE_MIN_SHARE / PARSY_DENSE_ALL_SHARE / PARSY_DENSE_FILL, percent: the thresholds, diagnostics)
-        const double min_share = env_int("PARSY_DENSE_MIN_SHARE", (int)(kDenseMinShare * 100 + 0.5)) / 100.0;
-        const double all_share = env_int("PARSY_DENSE_ALL_SHARE", (int)(kDenseAllShare * 100 + 0.5)) / 100.0;
-        const int fill_min = env_int("PARSY_DENSE_FILL", (int)(kDenseMinFill * 100 + 0.5)) * kBigTile * kBigTile / 100;
-        for (size_t l = 0; l < launch_dense.size(); ++l) {   // (re-decide with the thresholds of the environment)
-            if (dense_mode == 4 || dense_mode == 0 || ldense[l] <= 0) continue;
-            launch_dense[l] = (dense_mode >= 2 || ldense[l] >= min_share * lprod[l]) ? 1 : 0;
-            if (launch_dense[l] && lprod[l] - ldense[l] <= all_share * lprod[l] && dense_mode != 3) launch_dense[l] = 2;
-        }
-        // mode 1: full blocks, and windows filled well enough that a whole-block product beats the ragged kernel's rate
-        auto is_dense = [&](const WaveEntry& E, int mode) {
-            if (mode == 2) return E.K >= kDenseChunk;
-            const int mi = E.mn & 255, nj = (E.mn >> 8) & 255;
-            return mode == 1 && E.K >= kDenseChunk && mi * nj >= fill_min;
-        };
-        S.big_entries.resize(bigk.size());
-        const bool dense_strips = env_int("PARSY_DENSE_STRIPS", 1) != 0;
-        std::map<std::pair<int64_t, int64_t>, size_t> strip_of;   // (source, ia << 32 | ja) of a task's full dense blocks
-        std::vector<uint8_t> absorbed;
-        int t = 0;
-        for (size_t i = 0; i < bigk.size();) {
-            size_t j = i;
-            while (j < bigk.size() && bigk[j].launch_tile == bigk[i].launch_tile) ++j;
-            const int64_t launch = bigk[i].launch_tile >> 40, tile = bigk[i].launch_tile & ((1LL << 40) - 1);
-            // dense entries first, each part in update order
-            size_t at = i;
-            int64_t weight = 0, dweight = 0, dchunks = 0;
-            const int lmode = launch_dense[(size_t)launch];
-            if (lmode)
-                for (size_t q = i; q < j; ++q)
-                    if (is_dense(bigk[q].e, lmode)) {
-                        S.big_entries[at++] = bigk[q].e;
-                        dchunks += ceil_div(bigk[q].e.K, kDenseChunk);
-                        dweight += ceil_div(bigk[q].e.K, 16) + 2;
-                        {   // (the pairs (i, j), i >= j, of the block: a block that straddles the diagonal has fewer)
-                            const WaveEntry& E = bigk[q].e;
-                            const int mi = E.mn & 255, nj = (E.mn >> 8) & 255;
-                            double pairs = 0;
-                            for (int jj = E.ja; jj < E.ja + nj; ++jj) pairs += std::max(0, E.ia + mi - std::max(E.ia, jj));
-                            S.dense_flops += 2.0 * E.K * pairs;
-                        }
-                    }
-            const size_t mid = at;
-            // Strips: the remainder of a source's row run right behind a full block (<= kStripMax rows x the block's 128
-            // columns) or of its column run beside it (the block's 128 rows x <= kStripMax columns) rides with the block
-            // -- k_chol_dense has that block's operands staged and fetches 16 rows more per chunk, where k_chol_big
-            // staged the 128-wide window again for a sliver of products (Flan-class: 62 000 such entries, a third of the
-            // bytes the ragged launches staged; tools/pair_stats.py).  PARSY_DENSE_STRIPS=0: never.
-            int32_t nstrips = 0;
-            absorbed.assign(j - i, 0);
-            if (lmode && dense_strips && mid > i) {
-                strip_of.clear();
-                for (size_t d = i; d < mid; ++d) {
-                    const WaveEntry& E = S.big_entries[d];
-                    if ((E.mn & 0xffff) == (kBigTile | (kBigTile << 8))) strip_of[{E.src, ((int64_t)E.ia << 32) | (uint32_t)E.ja}] = d;
-                }
-                for (size_t q = i; q < j && !strip_of.empty(); ++q) {
-                    const WaveEntry& R = bigk[q].e;
-                    if (is_dense(R, lmode)) continue;
-                    const int mi = R.mn & 255, nj = (R.mn >> 8) & 255;
-                    const bool row_strip = mi <= kStripMax && nj == kBigTile, col_strip = nj <= kStripMax && mi == kBigTile;
-                    if (!row_strip && !col_strip) continue;
-                    const auto it = strip_of.find({R.src, ((int64_t)(R.ia - (row_strip ? kBigTile : 0)) << 32) |
-                                                          (uint32_t)(R.ja - (col_strip ? kBigTile : 0))});
-                    if (it == strip_of.end()) continue;
-                    WaveEntry& E = S.big_entries[it->second];
-                    if (E.K != R.K || ((E.mn >> 16) & 1) != ((R.mn >> 16) & 1) || E.rel != R.rel || E.ld != R.ld) continue;
-                    if ((row_strip ? big_strip_rows(E) : big_strip_cols(E)) != 0) continue;
-                    if (big_strip_rows(E) == 0 && big_strip_cols(E) == 0) ++nstrips;
-                    E.mn |= row_strip ? mi << 17 : nj << 22;
-                    absorbed[q - i] = 1;
-                    {
-                        double pairs = 0;
-                        for (int jj = R.ja; jj < R.ja + nj; ++jj) pairs += std::max(0, R.ia + mi - std::max(R.ia, jj));
-                        S.dense_flops += 2.0 * R.K * pairs;
-                    }
-                    dweight += ceil_div(R.K, 64);
-                }
-            }
-            for (size_t q = i; q < j; ++q)
-                if (!is_dense(bigk[q].e, lmode) && !absorbed[q - i]) {
-                    S.big_entries[at++] = bigk[q].e;
-                    weight += ceil_div(bigk[q].e.K, 16) + 4;
-                }
-            const size_t jend = at;     // (entries that ride with a dense block leave unused slots up to j)
-            S.n_dense_entries += (int64_t)(mid - i);
-            S.n_strip_entries += nstrips;
-            while (t + 1 < nc && big_tile0[t + 1] <= tile) ++t;   // tiles ascend within a launch ...
-            if (tile < big_tile0[t]) {                             // ... and start over with the next one
-                t = 0;
-                while (big_tile0[t + 1] <= tile) ++t;
-            }
-            const int nbr128 = ceil_div(S.csn[t].r, kBigTile);
-            const int64_t local = tile - big_tile0[t];
-            S.big_all.push_back(Schedule::BigTask{t, (int32_t)(local % nbr128) * kBigTile,
-                                                  (int32_t)(local / nbr128) * kBigTile,
-                                                  (int32_t)std::min<int64_t>(weight, INT32_MAX), (int64_t)i, (int64_t)jend,
-                                                  (int32_t)(launch >> 1), (int32_t)((launch & 1) == 0), bigk[i].sr, bigk[i].sc,
-                                                  (int64_t)mid, (int32_t)std::min<int64_t>(dweight, INT32_MAX),
-                                                  (int32_t)std::min<int64_t>(dchunks, INT32_MAX), nstrips});
-            i = j;
-        }
-    }
+}
 
+// Reads B.bigk (sorted by launch) and the dense knobs.  Returns per launch: 0 = k_chol_big only; 1 = full blocks to
+// k_chol_dense, the rest to k_chol_big; 2 = everything to
+// k_chol_dense (it multiplies a ragged window as a whole block and drops what the window does not have) --
+// where the ragged rest is so small (the last, partial row block of the pushes between a separator's pieces: a
+// handful of tasks) that a launch of its own would cost more than the wasted products: measured 0.07 - 0.1 ms
+// per such launch, 110 of them per Flan-class factorization.
+// Dense entries: full 128 x 128 blocks of the source's rows (on or below the target's diagonal; a block that
+// straddles it -- the diagonal blocks of the pushes between a separator's pieces -- is multiplied whole and its
+// upper part dropped when the tile is updated: 1.4 % more products there, and no ragged launch of a few hundred
+// diagonal blocks behind every such push).  A launch hands them to k_chol_dense when
+// they carry at least kDenseMinShare of its products; decided per launch over ALL targets, so that the order of
+// sums does not depend on which pieces a rank owns.
+std::vector<uint8_t> dense_share_per_launch(const BuildState& B) {
+    const BuildKnobs& K = B.knobs;
+    std::vector<double> lprod(B.launch_super.size(), 0.0), ldense(B.launch_super.size(), 0.0);
+    for (const BigKeyed& b : B.bigk) {
+        const WaveEntry& E = b.e;
+        const size_t l = (size_t)(b.launch_tile >> 40);
+        const double products = (double)ceil_div(E.K, 4) * ceil_div(entry_rows(E), 16) * ceil_div(entry_cols(E), 16);
+        lprod[l] += products;
+        if (entry_rows(E) == kBigTile && entry_cols(E) == kBigTile && E.K >= kDenseChunk) ldense[l] += products;
+    }
+    std::vector<uint8_t> launch_dense(B.launch_super.size(), 0);
+    for (size_t l = 0; l < launch_dense.size(); ++l) {
+        if (K.dense_mode == 4) {   // (tests: every entry of every launch through k_chol_dense, ragged windows and all)
+            launch_dense[l] = lprod[l] > 0 ? 2 : 0;
+            continue;
+        }
+        if (K.dense_mode == 0 || ldense[l] <= 0) continue;
+        if (K.dense_mode >= 2 || ldense[l] >= K.dense_min_share * lprod[l]) launch_dense[l] = 1;
+        if (launch_dense[l] && lprod[l] - ldense[l] <= K.dense_all_share * lprod[l] && K.dense_mode != 3) launch_dense[l] = 2;
+    }
+    return launch_dense;
+}
+
+// Reads B.bigk, B.big_tile0, the dense knobs.  Fills the BIG tasks, one per (launch, tile), entries in update order (stable
+// sort): big_entries, big_all, dense_flops, n_dense_entries, n_strip_entries.
+void build_big_tasks(Schedule& S, BuildState& B) {
+    std::vector<BigKeyed>& bigk = B.bigk;
+    if (bigk.empty()) return;
+    const int nc = (int)S.csn.size();
+    std::stable_sort(bigk.begin(), bigk.end(),
+                     [](const BigKeyed& a, const BigKeyed& b) { return a.launch_tile < b.launch_tile; });
+    const std::vector<uint8_t> launch_dense = dense_share_per_launch(B);
+    // mode 1: full blocks, and windows filled well enough that a whole-block product beats the ragged kernel's rate
+    const int fill_min = B.knobs.dense_fill_min;
+    auto is_dense = [fill_min](const WaveEntry& E, int mode) {
+        if (mode == 2) return E.K >= kDenseChunk;
+        return mode == 1 && E.K >= kDenseChunk && entry_rows(E) * entry_cols(E) >= fill_min;
+    };
+    S.big_entries.resize(bigk.size());
+    std::map<std::pair<int64_t, int64_t>, size_t> strip_of;   // (source, ia << 32 | ja) of a task's full dense blocks
+    std::vector<uint8_t> absorbed;
+    int t = 0;
+    for (size_t i = 0; i < bigk.size();) {
+        size_t j = i;
+        while (j < bigk.size() && bigk[j].launch_tile == bigk[i].launch_tile) ++j;
+        const int64_t launch = bigk[i].launch_tile >> 40, tile = bigk[i].launch_tile & ((1LL << 40) - 1);
+        // dense entries first, each part in update order
+        size_t at = i;
+        int64_t weight = 0, dweight = 0, dchunks = 0;
+        const int lmode = launch_dense[(size_t)launch];
+        if (lmode)
+            for (size_t q = i; q < j; ++q) {
+                const WaveEntry& E = bigk[q].e;
+                if (!is_dense(E, lmode)) continue;
+                S.big_entries[at++] = E;
+                dchunks += ceil_div(E.K, kDenseChunk);
+                dweight += ceil_div(E.K, 16) + 2;
+                S.dense_flops += 2.0 * E.K * block_pairs(E.ia, entry_rows(E), E.ja, entry_cols(E));
+            }
+        const size_t mid = at;
+        // Strips: the remainder of a source's row run right behind a full block (<= kStripMax rows x the block's 128
+        // columns) or of its column run beside it (the block's 128 rows x <= kStripMax columns) rides with the block
+        // -- k_chol_dense has that block's operands staged and fetches 16 rows more per chunk, where k_chol_big
+        // staged the 128-wide window again for a sliver of products (Flan-class: 62 000 such entries, a third of the
+        // bytes the ragged launches staged; tools/pair_stats.py).  PARSY_DENSE_STRIPS=0: never.
+        int32_t nstrips = 0;
+        absorbed.assign(j - i, 0);
+        if (lmode && B.knobs.dense_strips && mid > i) {
+            strip_of.clear();
+            for (size_t d = i; d < mid; ++d) {
+                const WaveEntry& E = S.big_entries[d];
+                if ((E.mn & 0xffff) == (kBigTile | (kBigTile << 8))) strip_of[{E.src, ((int64_t)E.ia << 32) | (uint32_t)E.ja}] = d;
+            }
+            for (size_t q = i; q < j && !strip_of.empty(); ++q) {
+                const WaveEntry& R = bigk[q].e;
+                if (is_dense(R, lmode)) continue;
+                const int mi = entry_rows(R), nj = entry_cols(R);
+                const bool row_strip = mi <= kStripMax && nj == kBigTile, col_strip = nj <= kStripMax && mi == kBigTile;
+                if (!row_strip && !col_strip) continue;
+                const auto it = strip_of.find({R.src, ((int64_t)(R.ia - (row_strip ? kBigTile : 0)) << 32) |
+                                                      (uint32_t)(R.ja - (col_strip ? kBigTile : 0))});
+                if (it == strip_of.end()) continue;
+                WaveEntry& E = S.big_entries[it->second];
+                if (E.K != R.K || big_ident(E) != big_ident(R) || E.rel != R.rel || E.ld != R.ld) continue;
+                if ((row_strip ? big_strip_rows(E) : big_strip_cols(E)) != 0) continue;
+                if (big_strip_rows(E) == 0 && big_strip_cols(E) == 0) ++nstrips;
+                E.mn |= row_strip ? mi << 17 : nj << 22;
+                absorbed[q - i] = 1;
+                S.dense_flops += 2.0 * R.K * block_pairs(R.ia, mi, R.ja, nj);
+                dweight += ceil_div(R.K, 64);
+            }
+        }
+        for (size_t q = i; q < j; ++q)
+            if (!is_dense(bigk[q].e, lmode) && !absorbed[q - i]) {
+                S.big_entries[at++] = bigk[q].e;
+                weight += ceil_div(bigk[q].e.K, 16) + 4;
+            }
+        const size_t jend = at;     // (entries that ride with a dense block leave unused slots up to j)
+        S.n_dense_entries += (int64_t)(mid - i);
+        S.n_strip_entries += nstrips;
+        while (t + 1 < nc && B.big_tile0[t + 1] <= tile) ++t;   // tiles ascend within a launch ...
+        if (tile < B.big_tile0[t]) {                             // ... and start over with the next one
+            t = 0;
+            while (B.big_tile0[t + 1] <= tile) ++t;
+        }
+        const int nbr128 = ceil_div(S.csn[t].r, kBigTile);
+        const int64_t local = tile - B.big_tile0[t];
+        S.big_all.push_back(Schedule::BigTask{t, (int32_t)(local % nbr128) * kBigTile,
+                                              (int32_t)(local / nbr128) * kBigTile,
+                                              (int32_t)std::min<int64_t>(weight, INT32_MAX), (int64_t)i, (int64_t)jend,
+                                              (int32_t)(launch >> 1), (int32_t)((launch & 1) == 0), bigk[i].sr, bigk[i].sc,
+                                              (int64_t)mid, (int32_t)std::min<int64_t>(dweight, INT32_MAX),
+                                              (int32_t)std::min<int64_t>(dchunks, INT32_MAX), nstrips});
+        i = j;
+    }
+}
+
+}  // namespace
+
+void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const int* A2i,
+                    const uint8_t* active, Schedule& S, int compute_units) {
+    S = Schedule();
+    BuildState B;
+    B.knobs = read_build_knobs();
+    B.compute_units = compute_units;
+    // resident workgroups of the chain kernel = 2 per CU; walkers of one batch take at most a quarter
+    if (compute_units > 0) S.walker_batch = std::max(4, std::min(kWalkerBatch, compute_units / 2));
+    describe_supernodes(P, lC, A2p, S);
+    list_updates(P, lC, A2p, A2i, S, B);
+    choose_sizes(S, B.knobs);
+    cut_pieces(P, S, B);
+    describe_updates(S, B);
+    cut_subtrees(S, B);
+    choose_super_tiles(S, B);
+    build_wave_streams(S, B);
+    collect_big_entries(S, B);
+    build_big_tasks(S, B);
     build_launches(S, active);
 }
 
-static void build_solve_one(Schedule& S, bool sharded);
+
+// ---- The knobs of build_launches (environment; diagnostics and tests), read by read_launch_knobs at the top of EVERY
+// build_launches call: the tests change the environment between two set_active calls on one plan.
+struct LaunchKnobs {
+    bool force_unfused;          // PARSY_FORCE_UNFUSED=1: the solve's fallback form everywhere (per-block-column launches): the
+                                 //   path taken when a chain launch would not be resident.  Used by the tests.
+    int big_group;               // PARSY_BIG_GROUP (kBigGroup): edge of the super-tiles whose BIG tasks share an XCD (0: never group)
+    int chain_split;             // PARSY_CHAIN_SPLIT (2 from kChainSplitAutoFlops update flops on, else 0): 0 = one chain launch per
+                                 //   level, 1 = two for the pieces of split supernodes, 2 = two for every tiled supernode
+    int bsolve_below;            // PARSY_BSOLVE_BELOW (1): 0 = never split the rows below off, 2 = for every wide supernode with rows below
+    bool sub_tier_min_trees_set; // PARSY_SUB_TIER_MIN_TREES (kSubTierMinTrees): trees a band of levels must leave (0: no bands).
+    int sub_tier_min_trees;      //   Set: bands whatever the density of the factor (tests)
+    int solve_one;               // PARSY_SOLVE_ONE (1): 0 = never a ONE-launch solve, 1 = by size, 2 = whatever the size (tests)
+};
+
+static LaunchKnobs read_launch_knobs(const Schedule& S) {
+    LaunchKnobs K{};
+    const char* fu = std::getenv("PARSY_FORCE_UNFUSED");
+    K.force_unfused = fu && fu[0] == '1';
+    K.big_group = env_int("PARSY_BIG_GROUP", kBigGroup);
+    K.chain_split = env_int("PARSY_CHAIN_SPLIT", S.update_flops >= kChainSplitAutoFlops ? 2 : 0);
+    K.bsolve_below = env_int("PARSY_BSOLVE_BELOW", 1);
+    K.sub_tier_min_trees_set = std::getenv("PARSY_SUB_TIER_MIN_TREES") != nullptr;
+    K.sub_tier_min_trees = env_int("PARSY_SUB_TIER_MIN_TREES", kSubTierMinTrees);
+    K.solve_one = env_int("PARSY_SOLVE_ONE", 1);
+    return K;
+}
+
+static void build_solve_one(Schedule& S, const LaunchKnobs& K, bool sharded);
 
 // The lists of the solves' subtree launches for many right-hand sides (schedule.hpp: SubMember, SubTree, SubTier).
 // append_sub_tier lays out one tier from its trees (supernodes in index order: descendants first).  A row below a member
@@ -844,14 +997,9 @@ static bool append_sub_tier(Schedule& S, const std::vector<std::vector<int32_t>>
 // Tiers above: bands of levels whose active supernodes are all at most kSubTierMaxWidth wide, every supernode not yet in a
 // tier in the tree of its highest ancestor inside the band; a band grows while that leaves at least kSubTierMinTrees
 // trees (PARSY_SUB_TIER_MIN_TREES; 0: no bands) whose slots fit.
-static void build_sub_tiers(Schedule& S) {
-    S.sub_members.clear();
-    S.sub_trees.clear();
-    S.sub_slots.clear();
-    S.sub_out_rows.clear();
-    S.sub_tiers.clear();
-    S.sub_max_slots = 0;
-    S.sub_cover_level = -1;
+// Reads the forward solve's subtree launch (solve_small_list / _ranges), S.active, the etree levels.  Fills sub_members,
+// sub_trees, sub_slots, sub_out_rows, sub_tiers, sub_max_slots, sub_cover_level (all empty / reset when it is called).
+static void build_sub_tiers(Schedule& S, const LaunchKnobs& K) {
     const int ns = S.nsuper;
     std::vector<uint8_t> covered((size_t)ns, 0);
     {
@@ -863,14 +1011,14 @@ static void build_sub_tiers(Schedule& S) {
         for (const auto& tr : trees)
             for (int32_t t : tr) covered[(size_t)t] = 1;
     }
-    const int min_trees = env_int("PARSY_SUB_TIER_MIN_TREES", kSubTierMinTrees);
+    const int min_trees = K.sub_tier_min_trees;
     if (min_trees <= 0) return;
     // Bands pay where the level launches they replace are chains of latencies -- factors of few entries per row (2-D
     // problems: parabolic_fem-class, 67 entries per row: levels 3-6 of 64 right-hand sides 307 -> 133 us forward).  The
     // trees of a 3-D factor carry hundreds of outside rows each (Flan-class: 442 slots = 63 KB of LDS per wave, two waves
     // per compute unit: 4.4 ms for what the level kernels do in 2.1), so there only the subtrees keep this form (3.7 ->
     // 2.1 ms).  PARSY_SUB_TIER_MIN_TREES set: whatever the factor (tests).
-    if (std::getenv("PARSY_SUB_TIER_MIN_TREES") == nullptr && S.xsize >= (int64_t)kSubTierMaxDensity * S.n) return;
+    if (!K.sub_tier_min_trees_set && S.xsize >= (int64_t)kSubTierMaxDensity * S.n) return;
     std::vector<int> level((size_t)ns, 0);
     for (int l = 0; l < S.nlevels; ++l)
         for (int q = S.levelPtr[l]; q < S.levelPtr[l + 1]; ++q) level[(size_t)S.levelSet[q]] = l;
@@ -993,15 +1141,53 @@ static Launch back_block_launch(int32_t first, int32_t count, int32_t level, int
     return L;
 }
 
-void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pieces) {
-    const int ns = S.nsuper;
-    // PARSY_FORCE_UNFUSED=1 schedules the solve's fallback form everywhere (per-block-column
-    // launches): the path taken when a chain launch would not be resident.  Used by the tests.
-    const char* fu = std::getenv("PARSY_FORCE_UNFUSED");
-    const bool force_unfused = fu && fu[0] == '1';
-    // chain launches take their work by ticket (producers first): any number of workgroups is fine
-    const int max_chain = force_unfused ? -1 : INT_MAX;
+namespace {
+
+using BigTaskList = std::vector<const Schedule::BigTask*>;
+
+// What the passes of build_launches hand to each other and is not part of the Schedule.
+struct LaunchState {
+    LaunchKnobs knobs;
+    std::vector<Launch> early;             // the side-stream launches, spliced into S.chol when every level is there
+    std::vector<size_t> level_begin;       // index in S.chol where each level's main-stream launches start
+    std::vector<BigTaskList> big_next, big_push;   // BIG tasks of every (source level, kind), active targets only
+};
+
+// Everything build_launches fills, empty again: the lists and counters of the three launch sequences.
+void reset_launch_lists(Schedule& S) {
+    S.n_chain_launches = 0;
     S.n_solve_chain_launches = 0;
+    S.n_solve_wide = 0;
+    S.n_bpart_slots = 0;
+    S.small_list.clear();
+    S.small_ranges.clear();
+    S.tiles.clear();
+    S.big_tasks.clear();
+    S.chol.clear();
+    S.solve_small_list.clear();
+    S.solve_small_ranges.clear();
+    S.solve_panels.clear();
+    S.solve_mtasks.clear();
+    S.solve_fix_list.clear();
+    S.solve_wide_list.clear();
+    S.solve.clear();
+    S.sub_members.clear();
+    S.sub_trees.clear();
+    S.sub_slots.clear();
+    S.sub_out_rows.clear();
+    S.sub_tiers.clear();
+    S.sub_max_slots = 0;
+    S.sub_cover_level = -1;
+    S.bsolve_blocks.clear();
+    S.bsolve_pairs.clear();
+    S.bsolve_below.clear();
+    S.bsolve_ranges.clear();
+    S.bsolve.clear();
+}
+
+// Reads the masks.  Fills S.active, S.active_piece, and solve_subtree / bsolve_subtree: the subtrees the mask contains whole.
+void apply_masks(Schedule& S, const uint8_t* active, const uint8_t* active_pieces) {
+    const int ns = S.nsuper;
     S.active.assign(ns, 1);
     if (active) S.active.assign(active, active + ns);
     // the factorization goes by PIECES of the Cholesky view (a multi-device run deals the pieces of a split
@@ -1028,286 +1214,259 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             for (int t = 0; t < ns; ++t)
                 if ((*sub)[t] >= 0 && !whole[(size_t)(*sub)[t]]) (*sub)[t] = -1;
         }
-    S.small_list.clear();
-    S.tiles.clear();
-    S.n_chain_launches = 0;
-    S.chol.clear();
-    S.solve_small_list.clear();
-    S.solve_panels.clear();
-    S.solve_mtasks.clear();
-    S.solve_fix_list.clear();
-    S.solve_wide_list.clear();
-    S.solve.clear();
-    S.n_solve_wide = 0;
+}
 
-    // Side-stream launches -- TILES(lev): the early wave streams of level lev's tiles, PUSH(s): the BIG
-    // updates from level s's supernodes into targets at levels >= s + 2 -- are enqueued right before the
-    // main-stream launches of the level in between (lev - 1 = s + 1), so that they run while the main
-    // stream works through that level's chain; Launch::level = lev = s + 2 is the level whose main-stream
-    // launches wait for them.
-    S.big_tasks.clear();
-    std::vector<Launch> early_launches;
-    std::vector<size_t> level_begin;  // index in S.chol where each level's launches start
-    std::vector<int> bigs, sbigs;
-    // BIG tasks of every (source level, kind), active targets only, heaviest first
-    std::vector<std::vector<const Schedule::BigTask*>> big_next(S.cnlevels), big_push(S.cnlevels);
-    for (const Schedule::BigTask& b : S.big_all)
-        if (S.active_piece[b.sn]) (b.next ? big_next : big_push)[b.src_level].push_back(&b);
-    // Order of a BIG launch's tasks.  Workgroups are dealt round-robin over the 8 XCDs (block b runs on the
-    // XCD of every block b + 8k; observed placement, used for speed only) and each XCD has its own L2, so
-    // tiles that read the same rows of a source should share an XCD at the same time: the tasks are grouped
-    // into g x g super-tiles of one target's tile grid (g row windows + g column windows of the source feed
-    // g*g tasks), the groups are dealt to 8 sequences -- heaviest group first, each to the least loaded
-    // sequence -- and sequence x fills the positions 8s + x (shorter sequences are padded with empty tasks,
-    // which return at once).  Small launches keep the plain heaviest-first order.  PARSY_BIG_GROUP=g
-    // (0: never group).
-    const int big_group = env_int("PARSY_BIG_GROUP", kBigGroup);
-    // (dense: the tasks' dense parts for k_chol_dense -- TileDesc::part = its 8-wide k chunks --, else their ragged rests)
-    auto emit_big = [&](const std::vector<const Schedule::BigTask*>& all, Launch L, bool dense) {
-        std::vector<const Schedule::BigTask*> v;
-        for (const Schedule::BigTask* b : all)
-            if (dense ? b->em > b->e0 : b->e1 > b->em) v.push_back(b);
-        if (v.empty()) return L;
-        L.first = (int32_t)S.big_tasks.size();
-        auto wt = [dense](const Schedule::BigTask* b) { return dense ? b->dweight : b->weight; };
-        auto desc = [dense](const Schedule::BigTask* b) {
-            return dense ? TileDesc{b->sn, b->row0, b->col0, b->dchunks | (b->strips > 0 ? kDenseStripTask : 0), b->e0, b->em}
-                         : TileDesc{b->sn, b->row0, b->col0, 0, b->em, b->e1};
-        };
-        auto by_weight = [&](const Schedule::BigTask* a, const Schedule::BigTask* b) { return wt(a) > wt(b); };
-        // group edge: as large as leaves every XCD at least kBigGroupsPerXcd groups to balance with
-        int g = big_group;
-        // (a group of g x g tiles holds g * g / (sr * sc) tasks)
-        const int per_task = v[0]->sr * v[0]->sc;
-        while (g > 1 && (int64_t)v.size() * per_task < (int64_t)8 * kBigGroupsPerXcd * g * g) g /= 2;
-        if (g < std::max(v[0]->sr, v[0]->sc)) g = 1;
-        if (g <= 1) {
-            std::stable_sort(v.begin(), v.end(), by_weight);
-            for (const Schedule::BigTask* b : v) S.big_tasks.push_back(desc(b));
-            L.count = (int32_t)v.size();
-            return L;
-        }
-        struct Group { int64_t key, weight; int32_t maxw; std::vector<const Schedule::BigTask*> tasks; };
-        std::vector<const Schedule::BigTask*> seq[8];
-        int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        auto least = [&] {
-            int x = 0;
-            for (int q = 1; q < 8; ++q)
-                if (load[q] < load[x]) x = q;
-            return x;
-        };
-        // the bulk goes in g x g groups; the lightest kBigTailGroups groups are dealt again at half the edge
-        // (and so on down to single tasks), so that the sequences end together
-        std::vector<const Schedule::BigTask*> rest(v);
-        for (; !rest.empty(); g /= 2) {
-            if (g <= 1) {
-                std::stable_sort(rest.begin(), rest.end(), by_weight);
-                for (const Schedule::BigTask* b : rest) {
-                    const int x = least();
-                    seq[x].push_back(b);
-                    load[x] += wt(b);
-                }
-                break;
-            }
-            std::vector<std::pair<int64_t, const Schedule::BigTask*>> keyed;
-            keyed.reserve(rest.size());
-            for (const Schedule::BigTask* b : rest) {
-                const int64_t gi = b->row0 / (kBigTile * g), gj = b->col0 / (kBigTile * g);
-                keyed.push_back({((int64_t)b->sn << 32) | (gj << 16) | gi, b});
-            }
-            std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-            std::vector<Group> groups;
-            for (const auto& kb : keyed) {
-                if (groups.empty() || groups.back().key != kb.first) groups.push_back(Group{kb.first, 0, 0, {}});
-                Group& G = groups.back();
-                G.tasks.push_back(kb.second);
-                G.weight += wt(kb.second);
-                G.maxw = std::max(G.maxw, wt(kb.second));
-            }
-            std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) {
-                return a.maxw != b.maxw ? a.maxw > b.maxw : a.weight > b.weight;
-            });
-            const size_t bulk = groups.size() > (size_t)kBigTailGroups ? groups.size() - kBigTailGroups : 0;
-            rest.clear();
-            for (size_t q = 0; q < groups.size(); ++q) {
-                Group& G = groups[q];
-                if (q >= bulk) {
-                    rest.insert(rest.end(), G.tasks.begin(), G.tasks.end());
-                    continue;
-                }
-                const int x = least();
-                std::stable_sort(G.tasks.begin(), G.tasks.end(), by_weight);
-                seq[x].insert(seq[x].end(), G.tasks.begin(), G.tasks.end());
-                load[x] += G.weight;
-            }
-        }
-        size_t len = 0;
-        for (int x = 0; x < 8; ++x) len = std::max(len, seq[x].size());
-        for (size_t s = 0; s < len; ++s)
-            for (int x = 0; x < 8; ++x) {
-                if (s < seq[x].size()) {
-                    S.big_tasks.push_back(desc(seq[x][s]));
-                } else {
-                    S.big_tasks.push_back(TileDesc{0, 0, 0, 0, 0, 0});  // padding: no entries
-                }
-            }
-        L.count = (int32_t)(8 * len);
+// Order of a BIG launch's tasks: appends the tasks of `all` that have a dense part (dense: for k_chol_dense -- TileDesc::part
+// = its 8-wide k chunks --), else those that have a ragged rest, to S.big_tasks; returns L with first / count filled in.
+// Workgroups are dealt round-robin over the 8 XCDs (block b runs on the
+// XCD of every block b + 8k; observed placement, used for speed only) and each XCD has its own L2, so
+// tiles that read the same rows of a source should share an XCD at the same time: the tasks are grouped
+// into g x g super-tiles of one target's tile grid (g row windows + g column windows of the source feed
+// g*g tasks), the groups are dealt to 8 sequences -- heaviest group first, each to the least loaded
+// sequence -- and sequence x fills the positions 8s + x (shorter sequences are padded with empty tasks,
+// which return at once).  Small launches keep the plain heaviest-first order.  PARSY_BIG_GROUP=g
+// (0: never group).
+Launch emit_big(Schedule& S, int big_group, const BigTaskList& all, Launch L, bool dense) {
+    BigTaskList v;
+    for (const Schedule::BigTask* b : all)
+        if (dense ? b->em > b->e0 : b->e1 > b->em) v.push_back(b);
+    if (v.empty()) return L;
+    L.first = (int32_t)S.big_tasks.size();
+    auto wt = [dense](const Schedule::BigTask* b) { return dense ? b->dweight : b->weight; };
+    auto desc = [dense](const Schedule::BigTask* b) {
+        return dense ? TileDesc{b->sn, b->row0, b->col0, b->dchunks | (b->strips > 0 ? kDenseStripTask : 0), b->e0, b->em}
+                     : TileDesc{b->sn, b->row0, b->col0, 0, b->em, b->e1};
+    };
+    auto by_weight = [&](const Schedule::BigTask* a, const Schedule::BigTask* b) { return wt(a) > wt(b); };
+    // group edge: as large as leaves every XCD at least kBigGroupsPerXcd groups to balance with
+    int g = big_group;
+    // (a group of g x g tiles holds g * g / (sr * sc) tasks)
+    const int per_task = v[0]->sr * v[0]->sc;
+    while (g > 1 && (int64_t)v.size() * per_task < (int64_t)8 * kBigGroupsPerXcd * g * g) g /= 2;
+    if (g < std::max(v[0]->sr, v[0]->sc)) g = 1;
+    if (g <= 1) {
+        std::stable_sort(v.begin(), v.end(), by_weight);
+        for (const Schedule::BigTask* b : v) S.big_tasks.push_back(desc(b));
+        L.count = (int32_t)v.size();
         return L;
+    }
+    struct Group { int64_t key, weight; int32_t maxw; BigTaskList tasks; };
+    BigTaskList seq[8];
+    int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto least = [&] {
+        int x = 0;
+        for (int q = 1; q < 8; ++q)
+            if (load[q] < load[x]) x = q;
+        return x;
     };
-    // The active supernodes of every subtree in index order (descendants first), subtrees by falling cost:
-    // fn(supernode) appends to the kind's list; returns the (begin, end) pairs of the list positions.
-    auto subtree_ranges = [&](const std::vector<int32_t>& subtree, int count, const std::vector<double>& cost,
-                              auto&& position, auto&& append, std::vector<int32_t>& ranges, bool chol = false) {
-        std::vector<std::vector<int32_t>> members((size_t)count);
-        std::vector<double> total((size_t)count, 0.0);
-        for (int t = 0; t < ns; ++t)
-            if (subtree[t] >= 0 && (chol ? S.active_piece[S.piece0[t]] : S.active[t])) {
-                members[(size_t)subtree[t]].push_back(t);
-                total[(size_t)subtree[t]] += cost[t];
+    // the bulk goes in g x g groups; the lightest kBigTailGroups groups are dealt again at half the edge
+    // (and so on down to single tasks), so that the sequences end together
+    BigTaskList rest(v);
+    for (; !rest.empty(); g /= 2) {
+        if (g <= 1) {
+            std::stable_sort(rest.begin(), rest.end(), by_weight);
+            for (const Schedule::BigTask* b : rest) {
+                const int x = least();
+                seq[x].push_back(b);
+                load[x] += wt(b);
             }
-        std::vector<int32_t> order;
-        for (int k = 0; k < count; ++k)
-            if (!members[(size_t)k].empty()) order.push_back(k);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return total[(size_t)a] > total[(size_t)b]; });
-        for (int k : order) {
-            ranges.push_back(position());
-            for (int32_t t : members[(size_t)k]) append(t);
-            ranges.push_back(position());
+            break;
         }
-        return (int32_t)order.size();
-    };
-    S.small_ranges.clear();
-    S.solve_small_ranges.clear();
-    S.bsolve_ranges.clear();
-    S.sub_members.clear();
-    S.sub_trees.clear();
-    S.sub_slots.clear();
-    S.sub_out_rows.clear();
-    S.sub_max_slots = 0;
-    S.bsolve_blocks.clear();
-    S.bsolve_pairs.clear();
-    for (int lev = 0; lev < S.cnlevels && !S.solve_only; ++lev) {
-        level_begin.push_back(S.chol.size());
-        bigs.clear();
-        // ---- Cholesky -------------------------------------------------------------
-        if (lev == 0 && S.n_chol_subtrees > 0) {
-            // the subtrees of SMALL supernodes, one workgroup each: LDS and stage sized for the largest member
-            Launch L = subtrees_launch(kLaunchSmall);
-            L.count = subtree_ranges(
-                S.chol_subtree, S.n_chol_subtrees, S.chol_cost, [&] { return (int32_t)S.small_list.size(); },
-                [&](int32_t t) {
-                    const SnDesc& T = S.csn[S.piece0[t]];
-                    S.small_list.push_back(S.piece0[t]);
-                    L.lds_bytes = std::max<int32_t>(L.lds_bytes, T.w * T.r * (int)sizeof(double));
-                    for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
-                        L.stage = std::max<int32_t>(L.stage, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
-                },
-                S.small_ranges, true);
-            if (L.count > 0) S.chol.push_back(L);
+        std::vector<std::pair<int64_t, const Schedule::BigTask*>> keyed;
+        keyed.reserve(rest.size());
+        for (const Schedule::BigTask* b : rest) {
+            const int64_t gi = b->row0 / (kBigTile * g), gj = b->col0 / (kBigTile * g);
+            keyed.push_back({((int64_t)b->sn << 32) | (gj << 16) | gi, b});
         }
-        {
-            Launch L = small_launch((int32_t)S.small_list.size(), lev);
-            for (int q = S.clevelPtr[lev]; q < S.clevelPtr[lev + 1]; ++q) {
-                const int t = S.clevelSet[q];
-                if (!S.active_piece[t] || S.chol_subtree[S.csn_real[t]] >= 0) continue;
-                const SnDesc& T = S.csn[t];
-                if (is_small(T)) {
-                    S.small_list.push_back(t);
-                    L.lds_bytes = std::max<int32_t>(L.lds_bytes, T.w * T.r * (int)sizeof(double));
-                    // the stage size of the SMALL launch: the largest descendant block,
-                    // capped (kernel: kSmallStage = 2048 doubles)
-                    for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
-                        L.stage = std::max<int32_t>(L.stage, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
+        std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        std::vector<Group> groups;
+        for (const auto& kb : keyed) {
+            if (groups.empty() || groups.back().key != kb.first) groups.push_back(Group{kb.first, 0, 0, {}});
+            Group& G = groups.back();
+            G.tasks.push_back(kb.second);
+            G.weight += wt(kb.second);
+            G.maxw = std::max(G.maxw, wt(kb.second));
+        }
+        std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) {
+            return a.maxw != b.maxw ? a.maxw > b.maxw : a.weight > b.weight;
+        });
+        const size_t bulk = groups.size() > (size_t)kBigTailGroups ? groups.size() - kBigTailGroups : 0;
+        rest.clear();
+        for (size_t q = 0; q < groups.size(); ++q) {
+            Group& G = groups[q];
+            if (q >= bulk) {
+                rest.insert(rest.end(), G.tasks.begin(), G.tasks.end());
+                continue;
+            }
+            const int x = least();
+            std::stable_sort(G.tasks.begin(), G.tasks.end(), by_weight);
+            seq[x].insert(seq[x].end(), G.tasks.begin(), G.tasks.end());
+            load[x] += G.weight;
+        }
+    }
+    size_t len = 0;
+    for (int x = 0; x < 8; ++x) len = std::max(len, seq[x].size());
+    for (size_t s = 0; s < len; ++s)
+        for (int x = 0; x < 8; ++x) {
+            if (s < seq[x].size()) {
+                S.big_tasks.push_back(desc(seq[x][s]));
+            } else {
+                S.big_tasks.push_back(TileDesc{0, 0, 0, 0, 0, 0});  // padding: no entries
+            }
+        }
+    L.count = (int32_t)(8 * len);
+    return L;
+}
+
+// The active supernodes of every subtree in index order (descendants first), subtrees by falling cost:
+// append(supernode) appends to the kind's list, position() is the list's length; fills the (begin, end) pairs of the list
+// positions into `ranges` and returns the number of subtrees that have an active member.
+template <class Position, class Append>
+int32_t subtree_ranges(const Schedule& S, const std::vector<int32_t>& subtree, int count, const std::vector<double>& cost,
+                       Position&& position, Append&& append, std::vector<int32_t>& ranges, bool chol = false) {
+    std::vector<std::vector<int32_t>> members((size_t)count);
+    std::vector<double> total((size_t)count, 0.0);
+    for (int t = 0; t < S.nsuper; ++t)
+        if (subtree[t] >= 0 && (chol ? S.active_piece[S.piece0[t]] : S.active[t])) {
+            members[(size_t)subtree[t]].push_back(t);
+            total[(size_t)subtree[t]] += cost[t];
+        }
+    std::vector<int32_t> order;
+    for (int k = 0; k < count; ++k)
+        if (!members[(size_t)k].empty()) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return total[(size_t)a] > total[(size_t)b]; });
+    for (int k : order) {
+        ranges.push_back(position());
+        for (int32_t t : members[(size_t)k]) append(t);
+        ranges.push_back(position());
+    }
+    return (int32_t)order.size();
+}
+
+// SMALL: piece t joins launch L -- dynamic LDS for the largest panel, and the stage size: the largest descendant block,
+// capped (kernel: kSmallStage = 2048 doubles)
+void add_small(Schedule& S, int t, Launch& L) {
+    const SnDesc& T = S.csn[t];
+    S.small_list.push_back(t);
+    L.lds_bytes = std::max<int32_t>(L.lds_bytes, T.w * T.r * (int)sizeof(double));
+    for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
+        L.stage = std::max<int32_t>(L.stage, std::min<int64_t>((int64_t)S.upd[u].m * S.upd[u].K, 2048));
+}
+
+// SMALL launches of level lev (in front of level 0: the subtrees of SMALL supernodes, one workgroup each).  Fills small_list,
+// small_ranges, S.chol; returns the level's tiled pieces in `tiled`.
+void small_launches(Schedule& S, int lev, std::vector<int>& tiled) {
+    tiled.clear();
+    if (lev == 0 && S.n_chol_subtrees > 0) {
+        Launch L = subtrees_launch(kLaunchSmall);
+        L.count = subtree_ranges(
+            S, S.chol_subtree, S.n_chol_subtrees, S.chol_cost, [&] { return (int32_t)S.small_list.size(); },
+            [&](int32_t t) { add_small(S, S.piece0[t], L); }, S.small_ranges, true);
+        if (L.count > 0) S.chol.push_back(L);
+    }
+    Launch L = small_launch((int32_t)S.small_list.size(), lev);
+    for (int q = S.clevelPtr[lev]; q < S.clevelPtr[lev + 1]; ++q) {
+        const int t = S.clevelSet[q];
+        if (!S.active_piece[t] || S.chol_subtree[S.csn_real[t]] >= 0) continue;
+        if (is_small(S.csn[t])) add_small(S, t, L);
+        else tiled.push_back(t);
+    }
+    L.count = (int32_t)S.small_list.size() - L.first;
+    if (L.count > 0) S.chol.push_back(L);
+}
+
+// PUSH(lev): this level's wide supernodes update everything at least two levels up (side
+// stream, once the level is complete); NEXT(lev - 1): the level below updates this level's tiles.
+// Side-stream launches -- TILES(lev): the early wave streams of level lev's tiles, PUSH(s): the BIG
+// updates from level s's supernodes into targets at levels >= s + 2 -- are enqueued right before the
+// main-stream launches of the level in between (lev - 1 = s + 1), so that they run while the main
+// stream works through that level's chain; Launch::level = lev = s + 2 is the level whose main-stream
+// launches wait for them.
+void push_next_launches(Schedule& S, LaunchState& LS, int lev) {
+    const int g = LS.knobs.big_group;
+    if (lev + 2 < S.cnlevels) {
+        Launch Ld = emit_big(S, g, LS.big_push[lev], side_launch(kLaunchDense, 0, lev + 2, lev), true);
+        if (Ld.count > 0) LS.early.push_back(Ld);
+        Launch Lp = emit_big(S, g, LS.big_push[lev], side_launch(kLaunchBig, 0, lev + 2, lev), false);
+        if (Lp.count > 0) LS.early.push_back(Lp);
+    }
+    if (lev > 0) {
+        Launch Ld = emit_big(S, g, LS.big_next[lev - 1], main_launch(kLaunchDense, 0, lev), true);
+        if (Ld.count > 0) S.chol.push_back(Ld);
+        Launch Ln = emit_big(S, g, LS.big_next[lev - 1], main_launch(kLaunchBig, 0, lev), false);
+        if (Ln.count > 0) S.chol.push_back(Ln);
+    }
+}
+
+// TILES: the early part of the external updates of level lev's tiled pieces, longest streams first (side stream)
+void tiles_launch(Schedule& S, LaunchState& LS, int lev, const std::vector<int>& tiled) {
+    Launch Lt = side_launch(kLaunchTiles, (int32_t)S.tiles.size(), lev, lev - 2);
+    std::vector<std::pair<int32_t, TileDesc>> wt;  // (weight, tile)
+    for (int t : tiled) {
+        const SnDesc& T = S.csn[t];
+        const int nbc = ceil_div(T.w, kTile), nbr = ceil_div(T.r, kTile);
+        const int32_t* tw = &S.tile_w[S.sn_tw0[t]];
+        for (int J = 0; J < nbc; ++J)
+            for (int I = J; I < nbr; ++I) {
+                const int32_t wgt = tw[((size_t)J * nbr + I) * 2];
+                if (wgt <= 0) continue;
+                const int64_t si = S.tile_split[S.sn_tw0[t] / 2 + (size_t)J * nbr + I];
+                if (si < 0) {
+                    wt.push_back({wgt, TileDesc{t, I * kTile, J * kTile, 0,
+                                                S.sn_wp0[t] + (((int64_t)J * nbr + I) * 2) * 4, -1}});
                 } else {
-                    bigs.push_back(t);
+                    const Schedule::SplitDesc& sd = S.split_desc[(size_t)si];
+                    for (int part = 0; part < sd.nparts; ++part)
+                        wt.push_back({ceil_div(wgt, sd.nparts),
+                                      TileDesc{t, I * kTile, J * kTile, part | (sd.nparts << 8),
+                                               sd.ranges + part * 8, sd.sp}});
                 }
             }
-            L.count = (int32_t)S.small_list.size() - L.first;
-            if (L.count > 0) S.chol.push_back(L);
-        }
-        // ---- PUSH(lev): this level's wide supernodes update everything at least two levels up (side
-        // stream, once the level is complete); NEXT(lev - 1): the level below updates this level's tiles
-        if (lev + 2 < S.cnlevels) {
-            Launch Ld = emit_big(big_push[lev], side_launch(kLaunchDense, 0, lev + 2, lev), true);
-            if (Ld.count > 0) early_launches.push_back(Ld);
-            Launch Lp = emit_big(big_push[lev], side_launch(kLaunchBig, 0, lev + 2, lev), false);
-            if (Lp.count > 0) early_launches.push_back(Lp);
-        }
-        if (lev > 0) {
-            Launch Ld = emit_big(big_next[lev - 1], main_launch(kLaunchDense, 0, lev), true);
-            if (Ld.count > 0) S.chol.push_back(Ld);
-            Launch Ln = emit_big(big_next[lev - 1], main_launch(kLaunchBig, 0, lev), false);
-            if (Ln.count > 0) S.chol.push_back(Ln);
-        }
-        if (!bigs.empty()) {
-            // ---- TILES: the early part of the external updates, longest streams first ------
-            {
-                Launch Lt = side_launch(kLaunchTiles, (int32_t)S.tiles.size(), lev, lev - 2);
-                std::vector<std::pair<int32_t, TileDesc>> wt;  // (weight, tile)
-                for (int t : bigs) {
-                    const SnDesc& T = S.csn[t];
-                    const int nbc = ceil_div(T.w, kTile), nbr = ceil_div(T.r, kTile);
-                    const int32_t* tw = &S.tile_w[S.sn_tw0[t]];
-                    for (int J = 0; J < nbc; ++J)
-                        for (int I = J; I < nbr; ++I) {
-                            const int32_t wgt = tw[((size_t)J * nbr + I) * 2];
-                            if (wgt <= 0) continue;
-                            const int64_t si = S.tile_split[S.sn_tw0[t] / 2 + (size_t)J * nbr + I];
-                            if (si < 0) {
-                                wt.push_back({wgt, TileDesc{t, I * kTile, J * kTile, 0,
-                                                            S.sn_wp0[t] + (((int64_t)J * nbr + I) * 2) * 4, -1}});
-                            } else {
-                                const Schedule::SplitDesc& sd = S.split_desc[(size_t)si];
-                                for (int part = 0; part < sd.nparts; ++part)
-                                    wt.push_back({ceil_div(wgt, sd.nparts),
-                                                  TileDesc{t, I * kTile, J * kTile, part | (sd.nparts << 8),
-                                                           sd.ranges + part * 8, sd.sp}});
-                            }
-                        }
-                }
-                std::stable_sort(wt.begin(), wt.end(),
-                                 [](const auto& a, const auto& b) { return a.first > b.first; });
-                for (auto& x : wt) S.tiles.push_back(x.second);
-                Lt.count = (int32_t)S.tiles.size() - Lt.first;
-                if (Lt.count > 0) early_launches.push_back(Lt);
-            }
-            // ---- CHAIN: every tile of the level's tiled supernodes, producers before consumers.
-            // Group J of a supernode: the walker (J = 0 only: it owns every diagonal tile), the two tiles
-            // the walker needs prepared for its step J -- (J+1,J) and (J+1,J+1) -- and then the other
-            // tiles of block column J, which wait for diagonal tile J.
-            // On large jobs the chain takes two launches per level: the tiles of the diagonal squares with the walkers
-            // first, the tiles of the rows below the squares afterwards.  In one launch those tiles -- hundreds to
-            // thousands per piece of a top separator -- were dispatched long before the walker reached their block
-            // column and waited for it holding a workgroup slot (72 KB of LDS: one of the two k_chol_big workgroups of
-            // the PUSH launch that runs beside the chain cannot be resident on that compute unit meanwhile); in a launch
-            // of their own every diagonal tile is there when they start, no flag is waited for, and the kernel of the
-            // second launch (k_chol_chain_rows: no walker, no prepared tile) gets by with 52 KB of LDS: three workgroups
-            // per compute unit.  Flan-class input: 371.2 -> 365.8 ms with the same kernel for both launches, 347.6 ms
-            // with k_chol_chain_rows; 27-point grids 56^3 ... 80^3: -3 ... -6 %; 48^3: +-0, 40^3: +9 %, nd24k-class
-            // 3.92 -> 4.21 ms (small jobs without BIG launches: the chain is the critical path), so the split is taken
-            // from kChainSplitAutoFlops update flops on.  Splitting only the pieces of split supernodes loses everywhere
-            // (mode 1).  PARSY_CHAIN_SPLIT=0: never; 2: always (diagnostics).
-            const int chain_split_mode = env_int("PARSY_CHAIN_SPLIT", S.update_flops >= kChainSplitAutoFlops ? 2 : 0);
-            auto splits = [&](int t) {
-                const int real = S.csn_real[t];
-                return chain_split_mode == 2 || (chain_split_mode == 1 && S.piece0[real + 1] - S.piece0[real] > 1);
-            };
-            bool chain_split = false;
-            for (int t : bigs) chain_split = chain_split || splits(t);
-            for (int part = 0; part < (chain_split ? 2 : 1); ++part) {
-            // part 1: only tiles below the squares (k_chol_chain_rows: three workgroups per compute unit)
-            Launch Lc = chain_launch((int32_t)S.tiles.size(), lev, S.n_chain_launches++, part == 1);
-            // Walkers stay resident for their whole chain, so the block-column-major interleaving is
-            // done per batch of at most walker_batch supernodes: what a walker waits for then lies at most
-            // one batch of tiles ahead of it in ticket order, and the walkers of the batches in flight
-            // never take more than a fraction of the resident workgroups.
-            for (size_t b0 = 0; b0 < bigs.size(); b0 += (size_t)S.walker_batch) {
-              const size_t b1 = std::min(bigs.size(), b0 + (size_t)S.walker_batch);
-              int maxnb = 0;
-              for (size_t q = b0; q < b1; ++q) maxnb = std::max(maxnb, ceil_div(S.csn[bigs[q]].w, kTile));
-              for (int J = 0; J < maxnb; ++J)
+    }
+    std::stable_sort(wt.begin(), wt.end(),
+                     [](const auto& a, const auto& b) { return a.first > b.first; });
+    for (auto& x : wt) S.tiles.push_back(x.second);
+    Lt.count = (int32_t)S.tiles.size() - Lt.first;
+    if (Lt.count > 0) LS.early.push_back(Lt);
+}
+
+// CHAIN: every tile of the level's tiled supernodes, producers before consumers.
+// Group J of a supernode: the walker (J = 0 only: it owns every diagonal tile), the two tiles
+// the walker needs prepared for its step J -- (J+1,J) and (J+1,J+1) -- and then the other
+// tiles of block column J, which wait for diagonal tile J.
+// On large jobs the chain takes two launches per level: the tiles of the diagonal squares with the walkers
+// first, the tiles of the rows below the squares afterwards.  In one launch those tiles -- hundreds to
+// thousands per piece of a top separator -- were dispatched long before the walker reached their block
+// column and waited for it holding a workgroup slot (72 KB of LDS: one of the two k_chol_big workgroups of
+// the PUSH launch that runs beside the chain cannot be resident on that compute unit meanwhile); in a launch
+// of their own every diagonal tile is there when they start, no flag is waited for, and the kernel of the
+// second launch (k_chol_chain_rows: no walker, no prepared tile) gets by with 52 KB of LDS: three workgroups
+// per compute unit.  Flan-class input: 371.2 -> 365.8 ms with the same kernel for both launches, 347.6 ms
+// with k_chol_chain_rows; 27-point grids 56^3 ... 80^3: -3 ... -6 %; 48^3: +-0, 40^3: +9 %, nd24k-class
+// 3.92 -> 4.21 ms (small jobs without BIG launches: the chain is the critical path), so the split is taken
+// from kChainSplitAutoFlops update flops on.  Splitting only the pieces of split supernodes loses everywhere
+// (mode 1).  PARSY_CHAIN_SPLIT=0: never; 2: always (diagnostics).
+void chain_launches(Schedule& S, int chain_split_mode, int lev, const std::vector<int>& tiled) {
+    auto splits = [&S, chain_split_mode](int t) {
+        const int real = S.csn_real[t];
+        return chain_split_mode == 2 || (chain_split_mode == 1 && S.piece0[real + 1] - S.piece0[real] > 1);
+    };
+    bool chain_split = false;
+    for (int t : tiled) chain_split = chain_split || splits(t);
+    for (int part = 0; part < (chain_split ? 2 : 1); ++part) {
+        // part 1: only tiles below the squares (k_chol_chain_rows: three workgroups per compute unit)
+        Launch Lc = chain_launch((int32_t)S.tiles.size(), lev, S.n_chain_launches++, part == 1);
+        // Walkers stay resident for their whole chain, so the block-column-major interleaving is
+        // done per batch of at most walker_batch supernodes: what a walker waits for then lies at most
+        // one batch of tiles ahead of it in ticket order, and the walkers of the batches in flight
+        // never take more than a fraction of the resident workgroups.
+        for (size_t b0 = 0; b0 < tiled.size(); b0 += (size_t)S.walker_batch) {
+            const size_t b1 = std::min(tiled.size(), b0 + (size_t)S.walker_batch);
+            int maxnb = 0;
+            for (size_t q = b0; q < b1; ++q) maxnb = std::max(maxnb, ceil_div(S.csn[tiled[q]].w, kTile));
+            for (int J = 0; J < maxnb; ++J)
                 for (size_t q = b0; q < b1; ++q) {
-                    const int t = bigs[q];
+                    const int t = tiled[q];
                     const SnDesc& T = S.csn[t];
                     const int nbc = ceil_div(T.w, kTile), nbr = ceil_div(T.r, kTile);
                     if (J >= nbc) continue;
@@ -1327,39 +1486,66 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                     }
                     for (int I = next_diag ? J + 2 : J + 1; I < nbr; ++I) push(I, J);
                 }
-            }
-            Lc.count = (int32_t)S.tiles.size() - Lc.first;
-            if (Lc.count > 0) S.chol.push_back(Lc);
-            else --S.n_chain_launches;
-            }
         }
+        Lc.count = (int32_t)S.tiles.size() - Lc.first;
+        if (Lc.count > 0) S.chol.push_back(Lc);
+        else --S.n_chain_launches;
     }
-    // splice the side launches in front of the level before the one that waits for them (stable: PUSH
-    // before TILES of the same level)
-    // chol_level_begin[lev]: where level lev's launches start in S.chol (its side launches first) -- the steps
-    // of a factorization that is run level by level (parsy_factor_level)
-    S.chol_level_begin.assign(level_begin.begin(), level_begin.end());
-    if (!early_launches.empty()) {
+}
+
+// Splices the side launches (LS.early) into S.chol in front of the level before the one that waits for them (stable: PUSH
+// before TILES of the same level).  Fills
+// chol_level_begin[lev]: where level lev's launches start in S.chol (its side launches first) -- the steps
+// of a factorization that is run level by level (parsy_factor_level)
+void splice_side_launches(Schedule& S, LaunchState& LS) {
+    S.chol_level_begin.assign(LS.level_begin.begin(), LS.level_begin.end());
+    if (!LS.early.empty()) {
         std::vector<Launch> merged;
         size_t e = 0;
-        std::stable_sort(early_launches.begin(), early_launches.end(),
-                         [](const Launch& a, const Launch& b) { return a.level < b.level; });
+        std::stable_sort(LS.early.begin(), LS.early.end(), [](const Launch& a, const Launch& b) { return a.level < b.level; });
         for (int lev = 0; lev < S.cnlevels; ++lev) {
             S.chol_level_begin[(size_t)lev] = merged.size();
-            while (e < early_launches.size() && early_launches[e].level - 1 <= lev) merged.push_back(early_launches[e++]);
-            const size_t b0 = level_begin[lev], b1 = lev + 1 < S.cnlevels ? level_begin[lev + 1] : S.chol.size();
+            while (e < LS.early.size() && LS.early[e].level - 1 <= lev) merged.push_back(LS.early[e++]);
+            const size_t b0 = LS.level_begin[lev], b1 = lev + 1 < S.cnlevels ? LS.level_begin[lev + 1] : S.chol.size();
             merged.insert(merged.end(), S.chol.begin() + b0, S.chol.begin() + b1);
         }
         S.chol.swap(merged);
     }
     S.chol_level_begin.push_back(S.chol.size());
+}
+
+// The launches of the factorization, level by level of the Cholesky view.  Fills small_list / small_ranges, tiles, big_tasks,
+// S.chol, chol_level_begin, n_chain_launches.
+void cholesky_launches(Schedule& S, LaunchState& LS) {
+    // BIG tasks of every (source level, kind), active targets only, heaviest first
+    LS.big_next.assign((size_t)S.cnlevels, {});
+    LS.big_push.assign((size_t)S.cnlevels, {});
+    for (const Schedule::BigTask& b : S.big_all)
+        if (S.active_piece[b.sn]) (b.next ? LS.big_next : LS.big_push)[b.src_level].push_back(&b);
+    std::vector<int> tiled;
+    for (int lev = 0; lev < S.cnlevels && !S.solve_only; ++lev) {
+        LS.level_begin.push_back(S.chol.size());
+        small_launches(S, lev, tiled);
+        push_next_launches(S, LS, lev);
+        if (tiled.empty()) continue;
+        tiles_launch(S, LS, lev, tiled);
+        chain_launches(S, LS.knobs.chain_split, lev, tiled);
+    }
+    splice_side_launches(S, LS);
+}
+
+// Forward solve, level by level.  Fills solve_small_list / _ranges, solve_panels, solve_mtasks, solve_wide_list,
+// solve_fix_list, S.solve, n_solve_wide; takes ticket counters from n_solve_chain_launches.
+void forward_solve_launches(Schedule& S, const LaunchKnobs& K) {
+    // chain launches take their work by ticket (producers first): any number of workgroups is fine
+    const int max_chain = K.force_unfused ? -1 : INT_MAX;
+    std::vector<int> sbigs;
     for (int lev = 0; lev < S.nlevels; ++lev) {
         sbigs.clear();
-        // ---- forward solve ----------------------------------------------------------
         if (lev == 0 && S.n_solve_subtrees > 0) {
             Launch L = subtrees_launch(kLaunchSolveSmall);
             L.count = subtree_ranges(
-                S.solve_subtree, S.n_solve_subtrees, S.solve_cost, [&] { return (int32_t)S.solve_small_list.size(); },
+                S, S.solve_subtree, S.n_solve_subtrees, S.solve_cost, [&] { return (int32_t)S.solve_small_list.size(); },
                 [&](int32_t t) {
                     S.solve_small_list.push_back(t);
                     L.width = std::max<int32_t>(L.width, S.sn[t].w);
@@ -1393,149 +1579,156 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
                 S.solve.push_back(L);
             }
         }
-        if (!sbigs.empty()) {
-            S.n_solve_wide += (int)sbigs.size();
-            int chain_wgs = 0;
-            for (int t : sbigs) chain_wgs += ceil_div(S.sn[t].r, kSolveRows);
-            if (chain_wgs <= max_chain) {
-                // one launch: every 256-row chunk of every wide supernode of the level
-                Launch Lc = level_chain_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev, S.n_solve_chain_launches++,
-                                               (int32_t)S.solve_mtasks.size());
-                for (int t : sbigs)
-                    for (int c = 0; c * kSolveRows < S.sn[t].r; ++c)
-                        S.solve_panels.push_back(PanelDesc{t, c, c * kSolveRows, 0});
-                Lc.count = (int32_t)S.solve_panels.size() - Lc.first;
-                // the same launch for many right-hand sides (k_solve_blocks_mrhs): the block columns of the triangles
-                // first (producers, ascending), then the row chunks below the supernodes' own columns
-                for (int t : sbigs)
-                    for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) S.solve_mtasks.push_back(PanelDesc{t, jb, -1, 0});
-                for (int t : sbigs)
-                    for (int c = 0, row0 = S.sn[t].w; row0 < S.sn[t].r; ++c, row0 += kSolveRowsMrhs)
-                        S.solve_mtasks.push_back(PanelDesc{t, c, row0, 0});
-                Lc.task_count = (int32_t)S.solve_mtasks.size() - Lc.task_first;
-                S.solve.push_back(Lc);
-                for (int t : sbigs) {
-                    for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) {
-                        S.solve_wide_list.push_back(t);
-                        S.solve_wide_list.push_back(jb);
-                    }
+        if (sbigs.empty()) continue;
+        S.n_solve_wide += (int)sbigs.size();
+        int chain_wgs = 0;
+        for (int t : sbigs) chain_wgs += ceil_div(S.sn[t].r, kSolveRows);
+        if (chain_wgs <= max_chain) {
+            // one launch: every 256-row chunk of every wide supernode of the level
+            Launch Lc = level_chain_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev, S.n_solve_chain_launches++,
+                                           (int32_t)S.solve_mtasks.size());
+            for (int t : sbigs)
+                for (int c = 0; c * kSolveRows < S.sn[t].r; ++c)
+                    S.solve_panels.push_back(PanelDesc{t, c, c * kSolveRows, 0});
+            Lc.count = (int32_t)S.solve_panels.size() - Lc.first;
+            // the same launch for many right-hand sides (k_solve_blocks_mrhs): the block columns of the triangles
+            // first (producers, ascending), then the row chunks below the supernodes' own columns
+            for (int t : sbigs)
+                for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) S.solve_mtasks.push_back(PanelDesc{t, jb, -1, 0});
+            for (int t : sbigs)
+                for (int c = 0, row0 = S.sn[t].w; row0 < S.sn[t].r; ++c, row0 += kSolveRowsMrhs)
+                    S.solve_mtasks.push_back(PanelDesc{t, c, row0, 0});
+            Lc.task_count = (int32_t)S.solve_mtasks.size() - Lc.task_first;
+            S.solve.push_back(Lc);
+            for (int t : sbigs) {
+                for (int jb = 0; jb * kTile < S.sn[t].w; ++jb) {
+                    S.solve_wide_list.push_back(t);
+                    S.solve_wide_list.push_back(jb);
                 }
-            } else {
-                int maxnb = 0;
-                for (int t : sbigs) maxnb = std::max(maxnb, ceil_div(S.sn[t].w, kTile));
-                for (int jb = 0; jb < maxnb; ++jb) {
-                    Launch Lp = main_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev);
-                    for (int t : sbigs) {
-                        const SnDesc& T = S.sn[t];
-                        if (ceil_div(T.w, kTile) <= jb) continue;
-                        const int wb = std::min(kTile, T.w - jb * kTile);
-                        S.solve_panels.push_back(PanelDesc{t, jb, -1, 0});
-                        for (int row0 = jb * kTile + wb; row0 < T.r; row0 += kSolveRows)
-                            S.solve_panels.push_back(PanelDesc{t, jb, row0, 0});
-                    }
-                    Lp.count = (int32_t)S.solve_panels.size() - Lp.first;
-                    S.solve.push_back(Lp);
-                }
-                S.solve_fix_list.insert(S.solve_fix_list.end(), sbigs.begin(), sbigs.end());
             }
+        } else {
+            int maxnb = 0;
+            for (int t : sbigs) maxnb = std::max(maxnb, ceil_div(S.sn[t].w, kTile));
+            for (int jb = 0; jb < maxnb; ++jb) {
+                Launch Lp = main_launch(kLaunchSolvePanel, (int32_t)S.solve_panels.size(), lev);
+                for (int t : sbigs) {
+                    const SnDesc& T = S.sn[t];
+                    if (ceil_div(T.w, kTile) <= jb) continue;
+                    const int wb = std::min(kTile, T.w - jb * kTile);
+                    S.solve_panels.push_back(PanelDesc{t, jb, -1, 0});
+                    for (int row0 = jb * kTile + wb; row0 < T.r; row0 += kSolveRows)
+                        S.solve_panels.push_back(PanelDesc{t, jb, row0, 0});
+                }
+                Lp.count = (int32_t)S.solve_panels.size() - Lp.first;
+                S.solve.push_back(Lp);
+            }
+            S.solve_fix_list.insert(S.solve_fix_list.end(), sbigs.begin(), sbigs.end());
         }
     }
-    build_sub_tiers(S);
-    // ---- backward solve: root level first.  Per level one chain launch for the block columns of
-    // the wide supernodes (last block column first: block jb waits for the published x of blocks
-    // jb+1.. of its supernode; every workgroup of the launch must be resident) and one launch for the
-    // supernodes of a single block; when the chain would not be resident, one launch per block-column
-    // index from the last one down.
-    S.bsolve.clear();
-    S.bsolve_below.clear();
-    S.n_bpart_slots = 0;
-    // PARSY_BSOLVE_BELOW=0: never split the rows below off; 2: for every wide supernode with rows below (tests)
-    const int below_mode = env_int("PARSY_BSOLVE_BELOW", 1);
-    auto in_level_launches = [&](int t) { return S.active[t] && S.bsolve_subtree[t] < 0; };
-    // the supernodes of one block column of a level: the tiny ones (one wave each: Launch::width_class = 1) in a launch
-    // of their own when there are enough of them, the others one workgroup each
-    auto narrow_launches = [&](int lev) {
-        std::vector<int32_t> tiny, tiny2, narrow;
-        for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
-            const int t = S.levelSet[q];
-            if (!in_level_launches(t) || S.sn[t].w > kTile) continue;
-            (S.sn[t].w <= kTinyWidth ? tiny : S.sn[t].w <= kTinyWidth2 ? tiny2 : narrow).push_back(t);
+    if (!S.solve_fix_list.empty())
+        S.solve.push_back(fixup_launch((int32_t)S.solve_fix_list.size(), S.nlevels));
+}
+
+// backward solve: the supernodes that the level launches solve (the others: the subtree launch)
+inline bool in_level_launches(const Schedule& S, int t) { return S.active[t] && S.bsolve_subtree[t] < 0; }
+
+// Backward solve: the supernodes of one block column of a level: the tiny ones (one wave each: Launch::width_class = 1) in a
+// launch of their own when there are enough of them, the others one workgroup each
+void back_narrow_launches(Schedule& S, int lev) {
+    std::vector<int32_t> tiny, tiny2, narrow;
+    for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
+        const int t = S.levelSet[q];
+        if (!in_level_launches(S, t) || S.sn[t].w > kTile) continue;
+        (S.sn[t].w <= kTinyWidth ? tiny : S.sn[t].w <= kTinyWidth2 ? tiny2 : narrow).push_back(t);
+    }
+    // (a group too small for a launch of its own joins the next wider one; the second width class of the
+    // one-wave kernel pays from a few hundred supernodes on: Flan-class backward solve 7.60 -> 7.32 ms, but
+    // +6 % on the nd24k-class input with an extra launch per level)
+    if (tiny2.size() < 512 && !narrow.empty()) {
+        narrow.insert(narrow.end(), tiny2.begin(), tiny2.end());
+        tiny2.clear();
+    }
+    if (tiny.size() < 64 && !(tiny2.empty() && narrow.empty())) {
+        (tiny2.empty() ? narrow : tiny2).insert((tiny2.empty() ? narrow : tiny2).end(), tiny.begin(), tiny.end());
+        tiny.clear();
+    }
+    for (const std::vector<int32_t>* group : {&tiny, &tiny2, &narrow}) {
+        if (group->empty()) continue;
+        Launch Ln = back_block_launch((int32_t)S.bsolve_blocks.size(), (int32_t)group->size(), lev,
+                                      group == &tiny ? 1 : group == &tiny2 ? 2 : 0);
+        for (int32_t t : *group) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
+        S.bsolve.push_back(Ln);
+    }
+}
+
+// Backward solve of level lev's wide supernodes in one chain launch (and, where it pays, a BACK_BELOW launch in front of it).
+// One right-hand side: a block column's sums over the rows BELOW the supernode's own columns (x final there)
+// need no hand-off, but in the chain launch only the block column's own four waves stream them -- a level of
+// few, tall supernodes (the separators below the root: 53 workgroups for 0.9 GB of panel) ran at 1.2 TB/s.
+// There the rows below go to a launch of their own, 512-row chunks over the whole device, partial sums into
+// slots that the chain adds up in a fixed order (bitwise reproducible).
+void back_chain_launch(Schedule& S, int below_mode, int lev) {
+    Launch Lc = level_chain_launch(kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), lev, S.n_solve_chain_launches++,
+                                   (int32_t)S.bsolve_pairs.size());
+    int64_t groups_here = 0;
+    for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
+        const int t = S.levelSet[q];
+        if (S.active[t] && S.sn[t].w > kTile) groups_here += ceil_div(ceil_div(S.sn[t].w, kTile), kBackGroup);
+    }
+    const bool below_level = below_mode >= 2 || (below_mode == 1 && groups_here <= kBelowMaxGroups);
+    Launch Lw = main_launch(kLaunchBackBelow, (int32_t)S.bsolve_below.size(), lev);
+    for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
+        const int t = S.levelSet[q];
+        const int nbc = ceil_div(S.sn[t].w, kTile);
+        if (!S.active[t] || nbc < 2) continue;
+        const int below = S.sn[t].r - S.sn[t].w;
+        int32_t slot1 = 0;
+        if (below_level && below >= (below_mode >= 2 ? 1 : kBelowRows) &&
+            S.n_bpart_slots + (int64_t)nbc * ceil_div(below, kBelowRows) < 0x7fffffffLL) {
+            const int nch = ceil_div(below, kBelowRows);
+            slot1 = (int32_t)S.n_bpart_slots + 1;
+            for (int jb = 0; jb < nbc; ++jb)
+                for (int c = 0; c < nch; ++c)
+                    S.bsolve_below.push_back(PanelDesc{t, jb, S.sn[t].w + c * kBelowRows, (int32_t)(S.n_bpart_slots + (int64_t)jb * nch + c)});
+            S.n_bpart_slots += (int64_t)nbc * nch;
         }
-        // (a group too small for a launch of its own joins the next wider one; the second width class of the
-        // one-wave kernel pays from a few hundred supernodes on: Flan-class backward solve 7.60 -> 7.32 ms, but
-        // +6 % on the nd24k-class input with an extra launch per level)
-        if (tiny2.size() < 512 && !narrow.empty()) {
-            narrow.insert(narrow.end(), tiny2.begin(), tiny2.end());
-            tiny2.clear();
-        }
-        if (tiny.size() < 64 && !(tiny2.empty() && narrow.empty())) {
-            (tiny2.empty() ? narrow : tiny2).insert((tiny2.empty() ? narrow : tiny2).end(), tiny.begin(), tiny.end());
-            tiny.clear();
-        }
-        for (const std::vector<int32_t>* group : {&tiny, &tiny2, &narrow}) {
-            if (group->empty()) continue;
-            Launch Ln = back_block_launch((int32_t)S.bsolve_blocks.size(), (int32_t)group->size(), lev,
-                                          group == &tiny ? 1 : group == &tiny2 ? 2 : 0);
-            for (int32_t t : *group) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
-            S.bsolve.push_back(Ln);
-        }
-    };
+        for (int jb = nbc - 1; jb >= 0; --jb) S.bsolve_blocks.push_back(PanelDesc{t, jb, 0, 0});
+        for (int jb = nbc - 1; jb >= 0; jb -= kBackGroup)
+            S.bsolve_pairs.push_back(PanelDesc{t, jb, std::min(kBackGroup, jb + 1), slot1});
+    }
+    Lw.count = (int32_t)S.bsolve_below.size() - Lw.first;
+    if (Lw.count > 0) S.bsolve.push_back(Lw);
+    Lc.count = (int32_t)S.bsolve_blocks.size() - Lc.first;
+    Lc.task_count = (int32_t)S.bsolve_pairs.size() - Lc.task_first;
+    S.bsolve.push_back(Lc);
+}
+
+// Backward solve: root level first.  Per level one chain launch for the block columns of
+// the wide supernodes (last block column first: block jb waits for the published x of blocks
+// jb+1.. of its supernode; every workgroup of the launch must be resident) and one launch for the
+// supernodes of a single block; when the chain would not be resident, one launch per block-column
+// index from the last one down.  Fills bsolve_blocks, bsolve_pairs, bsolve_below, bsolve_ranges, n_bpart_slots, S.bsolve.
+void backward_solve_launches(Schedule& S, const LaunchKnobs& K) {
+    const int max_chain = K.force_unfused ? -1 : INT_MAX;
     for (int lev = S.nlevels - 1; lev >= 0; --lev) {
         int maxnb = 0, wide_blocks = 0;
         for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
             const int t = S.levelSet[q];
-            if (!in_level_launches(t)) continue;
+            if (!in_level_launches(S, t)) continue;
             const int nbc = ceil_div(S.sn[t].w, kTile);
             maxnb = std::max(maxnb, nbc);
             if (nbc > 1) wide_blocks += nbc;
         }
         if (wide_blocks > 0 && wide_blocks <= max_chain) {
-            Launch Lc = level_chain_launch(kLaunchBackBlock, (int32_t)S.bsolve_blocks.size(), lev, S.n_solve_chain_launches++,
-                                           (int32_t)S.bsolve_pairs.size());
-            // One right-hand side: a block column's sums over the rows BELOW the supernode's own columns (x final there)
-            // need no hand-off, but in the chain launch only the block column's own four waves stream them -- a level of
-            // few, tall supernodes (the separators below the root: 53 workgroups for 0.9 GB of panel) ran at 1.2 TB/s.
-            // There the rows below go to a launch of their own, 512-row chunks over the whole device, partial sums into
-            // slots that the chain adds up in a fixed order (bitwise reproducible).
-            int64_t groups_here = 0;
-            for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
-                const int t = S.levelSet[q];
-                if (S.active[t] && S.sn[t].w > kTile) groups_here += ceil_div(ceil_div(S.sn[t].w, kTile), kBackGroup);
-            }
-            const bool below_level = below_mode >= 2 || (below_mode == 1 && groups_here <= kBelowMaxGroups);
-            Launch Lw = main_launch(kLaunchBackBelow, (int32_t)S.bsolve_below.size(), lev);
-            for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
-                const int t = S.levelSet[q];
-                const int nbc = ceil_div(S.sn[t].w, kTile);
-                if (!S.active[t] || nbc < 2) continue;
-                const int below = S.sn[t].r - S.sn[t].w;
-                int32_t slot1 = 0;
-                if (below_level && below >= (below_mode >= 2 ? 1 : kBelowRows) &&
-                    S.n_bpart_slots + (int64_t)nbc * ceil_div(below, kBelowRows) < 0x7fffffffLL) {
-                    const int nch = ceil_div(below, kBelowRows);
-                    slot1 = (int32_t)S.n_bpart_slots + 1;
-                    for (int jb = 0; jb < nbc; ++jb)
-                        for (int c = 0; c < nch; ++c)
-                            S.bsolve_below.push_back(PanelDesc{t, jb, S.sn[t].w + c * kBelowRows, (int32_t)(S.n_bpart_slots + (int64_t)jb * nch + c)});
-                    S.n_bpart_slots += (int64_t)nbc * nch;
-                }
-                for (int jb = nbc - 1; jb >= 0; --jb) S.bsolve_blocks.push_back(PanelDesc{t, jb, 0, 0});
-                for (int jb = nbc - 1; jb >= 0; jb -= kBackGroup)
-                    S.bsolve_pairs.push_back(PanelDesc{t, jb, std::min(kBackGroup, jb + 1), slot1});
-            }
-            Lw.count = (int32_t)S.bsolve_below.size() - Lw.first;
-            if (Lw.count > 0) S.bsolve.push_back(Lw);
-            Lc.count = (int32_t)S.bsolve_blocks.size() - Lc.first;
-            Lc.task_count = (int32_t)S.bsolve_pairs.size() - Lc.task_first;
-            S.bsolve.push_back(Lc);
-            narrow_launches(lev);
+            back_chain_launch(S, K.bsolve_below, lev);
+            back_narrow_launches(S, lev);
             continue;
         }
         for (int jb = maxnb - 1; jb >= 1; --jb) {
             Launch Lb = back_block_launch((int32_t)S.bsolve_blocks.size(), 0, lev, 0);
             for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
                 const int t = S.levelSet[q];
-                if (in_level_launches(t) && ceil_div(S.sn[t].w, kTile) > jb) S.bsolve_blocks.push_back(PanelDesc{t, jb, 0, 0});
+                if (in_level_launches(S, t) && ceil_div(S.sn[t].w, kTile) > jb) S.bsolve_blocks.push_back(PanelDesc{t, jb, 0, 0});
             }
             Lb.count = (int32_t)S.bsolve_blocks.size() - Lb.first;
             if (Lb.count > 0) S.bsolve.push_back(Lb);
@@ -1544,12 +1737,12 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             Launch Lb = back_block_launch((int32_t)S.bsolve_blocks.size(), 0, lev, 0);
             for (int q = S.levelPtr[lev]; q < S.levelPtr[lev + 1]; ++q) {
                 const int t = S.levelSet[q];
-                if (in_level_launches(t) && ceil_div(S.sn[t].w, kTile) > 1) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
+                if (in_level_launches(S, t) && ceil_div(S.sn[t].w, kTile) > 1) S.bsolve_blocks.push_back(PanelDesc{t, 0, 0, 0});
             }
             Lb.count = (int32_t)S.bsolve_blocks.size() - Lb.first;
             if (Lb.count > 0) S.bsolve.push_back(Lb);
         }
-        narrow_launches(lev);
+        back_narrow_launches(S, lev);
     }
     if (S.n_bsolve_subtrees > 0) {
         // the subtrees last: every ancestor outside them is final; inside, a workgroup walks from the subtree's
@@ -1558,7 +1751,7 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
         L.width_class = 1;   // (tiny supernodes: one wave per subtree)
         std::vector<int32_t> members;
         L.count = subtree_ranges(
-            S.bsolve_subtree, S.n_bsolve_subtrees, S.solve_cost,
+            S, S.bsolve_subtree, S.n_bsolve_subtrees, S.solve_cost,
             [&] {
                 for (size_t q = members.size(); q-- > 0;) S.bsolve_blocks.push_back(PanelDesc{members[q], 0, 0, 0});
                 members.clear();
@@ -1567,10 +1760,22 @@ void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pi
             [&](int32_t t) { members.push_back(t); }, S.bsolve_ranges);
         if (L.count > 0) S.bsolve.push_back(L);
     }
-    if (!S.solve_fix_list.empty())
-        S.solve.push_back(fixup_launch((int32_t)S.solve_fix_list.size(), S.nlevels));
-    build_solve_one(S, active != nullptr || active_pieces != nullptr);
 }
+
+}  // namespace
+
+void build_launches(Schedule& S, const uint8_t* active, const uint8_t* active_pieces) {
+    LaunchState LS;
+    LS.knobs = read_launch_knobs(S);
+    reset_launch_lists(S);
+    apply_masks(S, active, active_pieces);
+    cholesky_launches(S, LS);
+    forward_solve_launches(S, LS.knobs);
+    build_sub_tiers(S, LS.knobs);
+    backward_solve_launches(S, LS.knobs);
+    build_solve_one(S, LS.knobs, active != nullptr || active_pieces != nullptr);
+}
+
 
 // ONE-launch solves (schedule.hpp: Schedule::OneLists).  The lists of the launch that holds the supernodes of `member`:
 // the supernodes are taken block column by block column (<= 64 columns, a window of the supernode's panel like a piece of
@@ -1632,12 +1837,12 @@ static void build_one_lists(const Schedule& S, const std::vector<uint8_t>& membe
 }
 
 // Which solves go into ONE launch (schedule.hpp).  PARSY_SOLVE_ONE=0: never, 1: by size, 2: whatever the size (tests).
-static void build_solve_one(Schedule& S, bool sharded) {
+static void build_solve_one(Schedule& S, const LaunchKnobs& K, bool sharded) {
     const int ns = S.nsuper;
     S.solve_one = S.solve_one_back = S.one_subtrees = S.one_forced = S.one_big = false;
     S.one_f.clear();
     S.one_b.clear();
-    const int mode = env_int("PARSY_SOLVE_ONE", 1);
+    const int mode = K.solve_one;
     if (mode == 0 || sharded || ns == 0 || (int)S.levelSet.size() != ns) return;   // (a rank's share of the supernodes: level launches)
     // with subtree launches: the supernodes outside them (the launch must be the first of `solve` / the last of `bsolve`)
     const bool sub = S.n_solve_subtrees > 0 || S.n_bsolve_subtrees > 0;

@@ -97,6 +97,8 @@ struct WaveEntry {    // one (descendant, 32x32 sub-tile) pair of the tile kerne
 // kStripMax rows right behind the block, times the block's column window -- and / or of its column run: k_chol_dense
 // multiplies them with the operands it has staged for the block, plus a strip of 16 rows per chunk.
 constexpr int kStripMax = 16;
+inline int entry_rows(const WaveEntry& E) { return E.mn & 255; }          // rows in the row window
+inline int entry_cols(const WaveEntry& E) { return (E.mn >> 8) & 255; }   // rows in the column window
 inline bool big_ident(const WaveEntry& E) { return (E.mn >> 16) & 1; }
 inline int big_strip_rows(const WaveEntry& E) { return (E.mn >> 17) & 31; }
 inline int big_strip_cols(const WaveEntry& E) { return (E.mn >> 22) & 31; }

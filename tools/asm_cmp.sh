@@ -9,7 +9,7 @@
 set -u
 A=$(cd "$1" && pwd); B=$(cd "$2" && pwd); W=${3:-$(mktemp -d)}
 HIPCC=${HIPCC:-$(command -v hipcc || echo /opt/rocm/bin/hipcc)}
-FILES="chol_kernels trsv_kernels trsv_sub_kernels selinv_kernels refine_kernels grad_kernels executor capi_exec capi_hostcalls mg"
+FILES="chol_kernels trsv_kernels trsv_sub_kernels selinv_kernels refine_kernels grad_kernels cond_kernels apply_kernels updown_kernels rowmod_kernels eigs_kernels executor capi_exec capi_hostcalls mg"
 mkdir -p "$W/a" "$W/b"
 : > "$W/empty.hip"
 asm() {  # tree, side, file

@@ -1,6 +1,7 @@
 """The launch tables (parsy_debug_launches: one row of parsy::Launch's fields per launch of the factorization, the forward
 and the backward solve) of host-only plans, one SHA-256 per plan over the three tables -- what a change of the launch
-record or of the schedule builder is compared by (profiles/launch_record_evidence.md).  Needs no device.
+record is compared by (profiles/launch_record_evidence.md).  A change of the schedule builder is compared by
+tools/schedule_digests.py, which hashes every array of the schedule, these tables among them.  Needs no device.
 Usage: launch_tables.py [--rows]     (--rows: the tables themselves)"""
 import ctypes as C
 import hashlib
