@@ -17,7 +17,10 @@ _PAD = 37          # ld = n + 37
 _TAIL = 11         # Y is allocated 11 entries too long
 NRHS = [1, 3, 8, 16, 17, 64, 70]
 NMAX = 70
-PATTERNS = ["tiny2d", "random", "dense150", "tridiag300", "diag37"]
+# edges / tall / chain: the engineered shapes of selinv_ref.py -- supernode widths 1, 17, 63, 65 and 129 against the product
+# kernels' four columns per step and 64-row lanes
+SHAPED = ["edges", "tall", "chain"]
+PATTERNS = ["tiny2d", "random", "dense150", "tridiag300", "diag37"] + SHAPED
 _PLANS, _ENTRIES, _REFS = {}, {}, {}
 
 
@@ -29,6 +32,9 @@ def _plan(api, name):
             sym = I.analyze(M.random_spd(300, density=0.03, seed=5), None)
         elif name in ("dense150", "tridiag300", "diag37"):
             sym = edge(name)[1]
+        elif name in SHAPED:
+            import selinv_ref
+            sym = selinv_ref.build(name)[2]
         else:
             sym = problem(name)[2]
         lv = np.random.default_rng(len(name)).standard_normal(int(sym.xsize))
