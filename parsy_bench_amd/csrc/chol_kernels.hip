@@ -16,6 +16,7 @@
 
 #include "device_util.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace parsy {
 
@@ -70,9 +71,7 @@ void launch_scatter_a(const double* values, const int64_t* a_dst, double* L, int
     if (nnz <= 0) return;
     int64_t blocks = (nnz + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
-    witness_launch(kWScatterA);
-    hipLaunchKernelGGL(k_scatter_a, dim3((unsigned)blocks), dim3(kThreads), 0, stream, values, a_dst,
-                       L, nnz);
+    launch_witnessed<k_scatter_a, kWScatterA>(dim3((unsigned)blocks), dim3(kThreads), 0, stream, values, a_dst, L, nnz);
 }
 
 // ---------------------------------------------------------------------------
@@ -480,10 +479,9 @@ void launch_chol_small(const DevicePattern& P, int first, int count, int lds_byt
     const size_t lds = (size_t)((lds_bytes + 15) & ~15) + 2 * (size_t)stage_cap * sizeof(double) +
                        4 * kSmallRelCap * sizeof(int32_t) + (kPotrfScratch + kTile) * sizeof(double);
     // subtree launch: `first` counts (begin, end) pairs of small_ranges, which index the whole list
-    witness_launch(kWCholSmall);
-    hipLaunchKernelGGL(k_chol_small, dim3(count), dim3(kThreads), lds, stream, P.csn, P.upd, P.relpos,
-                       subtrees ? P.small_list : P.small_list + first,
-                       subtrees ? P.small_ranges + 2 * first : nullptr, L, P.info, stage_cap);
+    launch_witnessed<k_chol_small, kWCholSmall>(dim3(count), dim3(kThreads), lds, stream, P.csn, P.upd, P.relpos,
+        subtrees ? P.small_list : P.small_list + first, subtrees ? P.small_ranges + 2 * first : nullptr, L, P.info,
+        stage_cap);
 }
 
 // ---------------------------------------------------------------------------
@@ -2392,9 +2390,8 @@ __global__ __launch_bounds__(kDenseThreads, 2) void k_chol_dense(const SnDesc* _
 
 void launch_chol_dense(const DevicePattern& P, int first, int count, double* L, hipStream_t stream) {
     if (count <= 0) return;
-    witness_launch(kWCholDense);
-    hipLaunchKernelGGL(k_chol_dense, dim3(count), dim3(kDenseThreads), 0, stream, P.csn, P.relpos, P.big_entries,
-                       P.big_tasks + first, L);
+    launch_witnessed<k_chol_dense, kWCholDense>(dim3(count), dim3(kDenseThreads), 0, stream, P.csn, P.relpos,
+        P.big_entries, P.big_tasks + first, L);
 }
 
 #ifdef PARSY_DENSESTAMPS
@@ -2438,16 +2435,14 @@ extern "C" void parsy_debug_tilephase(unsigned long long* out, int reset) {
 
 void launch_chol_big(const DevicePattern& P, int first, int count, double* L, hipStream_t stream) {
     if (count <= 0) return;
-    witness_launch(kWCholBig);
-    hipLaunchKernelGGL(k_chol_big, dim3(count), dim3(kBigThreads), 0, stream, P.csn, P.relpos, P.big_entries,
-                       P.big_tasks + first, L);
+    launch_witnessed<k_chol_big, kWCholBig>(dim3(count), dim3(kBigThreads), 0, stream, P.csn, P.relpos, P.big_entries,
+        P.big_tasks + first, L);
 }
 
 void launch_chol_tiles(const DevicePattern& P, int first, int count, double* L, hipStream_t stream) {
     if (count <= 0) return;
-    witness_launch(kWCholTiles);
-    hipLaunchKernelGGL(k_chol_tiles, dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos, P.wave_entries,
-                       P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L);
+    launch_witnessed<k_chol_tiles, kWCholTiles>(dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos, P.wave_entries,
+        P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L);
 }
 
 // Resident workgroups of the chain kernel per CU as the runtime sees them (registers, LDS); 0 on error.
@@ -2461,15 +2456,13 @@ void launch_chol_chain(const DevicePattern& P, int first, int count, int ticket,
                        hipStream_t stream) {
     if (count <= 0) return;
     if (rows) {
-        witness_launch(kWCholChainRows);
-        hipLaunchKernelGGL(k_chol_chain_rows, dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos, P.wave_entries,
-                           P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L, P.info, P.tflags,
-                           P.n_tflags, P.tickets + ticket, epoch);
+        launch_witnessed<k_chol_chain_rows, kWCholChainRows>(dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos,
+            P.wave_entries, P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L, P.info, P.tflags,
+            P.n_tflags, P.tickets + ticket, epoch);
     } else {
-        witness_launch(kWCholChain);
-        hipLaunchKernelGGL(k_chol_chain, dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos, P.wave_entries,
-                           P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L, P.info, P.tflags,
-                           P.n_tflags, P.tickets + ticket, epoch);
+        launch_witnessed<k_chol_chain, kWCholChain>(dim3(count), dim3(kThreads), 0, stream, P.csn, P.relpos,
+            P.wave_entries, P.wave_ptr, P.split_ranges, P.tile_scratch, P.tiles + first, L, P.info, P.tflags,
+            P.n_tflags, P.tickets + ticket, epoch);
     }
 }
 

@@ -514,6 +514,33 @@ static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream
     return 0;
 }
 
+// The gates of the solves' kernel variants (SolveGates, kernels.hpp), from the environment.
+SolveGates read_solve_gates() {
+    SolveGates g;
+    auto num = [](const char* name, int& v) {
+        const char* e = std::getenv(name);
+        if (e && *e) v = std::atoi(e);
+        return e && *e;
+    };
+    int m = 0;
+    num("PARSY_MRHS_MIN", m);
+    if (m > 0) {
+        g.mrhs_min = m;
+        g.chain_mrhs_min = std::min(m, g.chain_mrhs_min);
+    }
+    num("PARSY_BMRHS_MIN", g.bmrhs_min);
+    const char* w = std::getenv("PARSY_BMRHS_WIDE_ONLY");
+    g.bmrhs_wide_only = !(w && w[0] == '0');
+    num("PARSY_BCHAIN_MIN_BLOCKS", g.bchain_min_blocks);
+    num("PARSY_SMALL_MRHS_HALVES_MIN", g.small_halves_min);
+    num("PARSY_SUB_MRHS_MIN", g.sub_mrhs_min);
+    g.xt_min_set = num("PARSY_XT_MIN", g.xt_min);
+    const char* st = std::getenv("PARSY_DEBUG_SOLVE_STALL");
+    g.wait_bias = (st && st[0] == '1') ? (1 << 20) : 0;
+    num("PARSY_SUB_ABL", g.sub_abl);
+    return g;
+}
+
 // Argument checks of a device solve (`who`: the C ABI call the messages name).  A solve that starts here abandons one in
 // steps of levels that was never finished and reads the gates of its kernel variants, once for all its launches.
 static int solve_start(parsy_plan* pl, const char* who, bool args_ok, const char* need, bool starts = true) {

@@ -1,4 +1,4 @@
-// Launch wrappers of the HIP kernels (chol_kernels.hip, trsv_kernels.hip).
+// Launch wrappers of the HIP kernels (chol_kernels.hip, trsv_*kernels.hip).
 // All pointers are device pointers; launches are asynchronous on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>

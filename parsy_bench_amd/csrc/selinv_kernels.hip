@@ -40,7 +40,7 @@ constexpr int kChunk = 32;              // rows of R_b per step of the small pat
 constexpr int kLdC = kChunk + 1;
 constexpr int kLogParts = 256;          // workgroups of the log-determinant's first pass
 
-// ---- T = L_bb^-1 in LDS, one wave: the blocked inversion of the solves' k_diag_inverse (trsv_kernels.hip), spelled out
+// ---- T = L_bb^-1 in LDS, one wave: the blocked inversion of the solves' k_diag_inverse (trsv_aux_kernels.hip), spelled out
 // here a second time -- one shared inline function changed the instruction schedule of both (mm16 / put16: device_util.hpp)
 // M (64 x kLd doubles of LDS) := inv(L_bb), lower triangle, zeros above, an identity past wb.  Lanes 0..63 of one wave.
 __device__ void tinv64(double* __restrict__ M, const double* __restrict__ G, int r, int j0, int wb) {

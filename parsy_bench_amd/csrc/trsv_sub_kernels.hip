@@ -27,6 +27,7 @@
 
 #include "device_util.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace parsy {
 
@@ -495,10 +496,9 @@ void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doubl
     size_t lds;
     sub_grid(T, nrhs, ngroups, grid, block, per_wave, lds);
     const bool tr = ldq > 0;
-    witness_launch(kWSolveSubMrhs);
-    hipLaunchKernelGGL(k_solve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
-                       reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs,
-                       (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, P.gates.sub_abl);
+    launch_witnessed<k_solve_sub_mrhs, kWSolveSubMrhs>(grid, block, lds, stream, P.sub_members, P.sub_trees,
+        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs,
+        (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, P.gates.sub_abl);
 }
 
 void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const double* L, double* x, int nrhs, int ldx,
@@ -508,10 +508,9 @@ void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doub
     dim3 grid, block;
     size_t lds;
     sub_grid(T, nrhs, ngroups, grid, block, per_wave, lds);
-    witness_launch(kWBsolveSubMrhs);
-    hipLaunchKernelGGL(k_bsolve_sub_mrhs, grid, block, lds, stream, P.sub_members, P.sub_trees,
-                       reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs, 1u,
-                       (int64_t)ldx, P.gates.sub_abl);
+    launch_witnessed<k_bsolve_sub_mrhs, kWBsolveSubMrhs>(grid, block, lds, stream, P.sub_members, P.sub_trees,
+        reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs, 1u,
+        (int64_t)ldx, P.gates.sub_abl);
 }
 
 // Once per plan: a workgroup of four waves on the largest trees may need more than 64 KB of LDS -- ask for it (up to

@@ -25,7 +25,7 @@ for _ in range(3):
     torch.cuda.synchronize()
 print("backward solve ms", plan.last_solve_ms())
 st = np.zeros(512 * 8, dtype=np.uint64)
-N.lib().parsy_debug_blkstamps(C.c_void_p(st.ctypes.data))
+N.lib().parsy_debug_bblkstamps(C.c_void_p(st.ctypes.data))
 st = st.reshape(512, 8).astype(np.int64)
 ok = np.where((st[:, 3] > 0) & (st[:, 0] > 0))[0]
 us = lambda v: v / 100.0          # 100-MHz clock
