@@ -487,6 +487,43 @@ int64_t parsy_debug_big_windows(const parsy_plan* pl, int64_t* out, int64_t cap)
     return n;
 }
 
+// Diagnostics (tools/recut_stats.py, tests/test_recut_host.py): the BIG tasks of the plan, in the order of the two exports
+// above, as rows of (launch = 2 * source level + push, piece, conflict domain (0: tile cut), row0, col0, entries, dense
+// entries, issued fragment-chunks, 16-wide k chunks, of which in dense entries).  Issued fragment-chunks: per 16-wide k chunk of an entry the 16 x 16
+// fragments that are multiplied -- a dense entry its whole 128 x 128 block (64) and 8 per strip that rides with it, a
+// ragged entry those its window touches.
+int64_t parsy_debug_big_tasks(const parsy_plan* pl, int64_t* out, int64_t cap) {
+    if (!pl) return -1;
+    const parsy::Schedule& S = pl->S;
+    int64_t n = 0;
+    for (const parsy::Schedule::BigTask& b : S.big_all) {
+        if (out && n < cap) {
+            int64_t frag_chunks = 0, chunks = 0, dense_chunks = 0;
+            for (int64_t e = b.e0; e < b.e1; ++e) {
+                const parsy::WaveEntry& E = S.big_entries[(size_t)e];
+                const int64_t kc = (E.K + 15) / 16, mi = E.mn & 255, nj = (E.mn >> 8) & 255;
+                chunks += kc;
+                if (e < b.em) dense_chunks += kc;
+                frag_chunks += kc * (e < b.em ? 64 + 8 * (parsy::big_strip_rows(E) > 0) + 8 * (parsy::big_strip_cols(E) > 0)
+                                              : ((mi + 15) / 16) * ((nj + 15) / 16));
+            }
+            int64_t* o = out + 10 * n;
+            o[0] = b.src_level * 2 + (b.next ? 0 : 1);
+            o[1] = b.sn;
+            o[2] = b.domain;
+            o[3] = b.row0;
+            o[4] = b.col0;
+            o[5] = b.e1 - b.e0;
+            o[6] = b.em - b.e0;
+            o[7] = frag_chunks;
+            o[8] = chunks;
+            o[9] = dense_chunks;
+        }
+        ++n;
+    }
+    return n;
+}
+
 // Diagnostics: the tasks of the DENSE launches in launch order as rows of (launch index, 8-wide k chunks).
 int64_t parsy_debug_dense_tasks(const parsy_plan* pl, int32_t* out, int64_t cap) {
     if (!pl) return -1;

@@ -1,6 +1,7 @@
 // Host-side construction of the device schedule (see schedule.hpp).
 #include "schedule.hpp"
 
+#include <array>
 #include <cstdio>
 #include <map>
 #include <algorithm>
@@ -82,6 +83,7 @@ struct BuildKnobs {
     double dense_all_share;  // PARSY_DENSE_ALL_SHARE (percent; kDenseAllShare): ragged share up to which k_chol_dense takes it too
     int dense_fill_min;      // PARSY_DENSE_FILL (percent of 128 x 128; kDenseMinFill), in entries: windows this full count as dense
     bool dense_strips;       // PARSY_DENSE_STRIPS (1): 0 = no strips ride with the dense blocks
+    bool big_recut;          // PARSY_BIG_RECUT (1): 0 = every BIG update is cut on the target's tile grid (find_conflict_domains)
 };
 
 BuildKnobs read_build_knobs() {
@@ -115,10 +117,13 @@ BuildKnobs read_build_knobs() {
     K.dense_all_share = percent("PARSY_DENSE_ALL_SHARE", kDenseAllShare) / 100.0;
     K.dense_fill_min = percent("PARSY_DENSE_FILL", kDenseMinFill) * kBigTile * kBigTile / 100;
     K.dense_strips = env_int("PARSY_DENSE_STRIPS", 1) != 0;
+    K.big_recut = env_int("PARSY_BIG_RECUT", 1) != 0;
     return K;
 }
 
-struct BigKeyed { int64_t launch_tile; WaveEntry e; int16_t sr, sc; };  // launch id << 40 | global tile index
+// launch id << 40 | global tile index; window: 0 = a task of the tile cut, else domain << 32 | column window << 16 | row window
+// of a re-cut domain (launch_tile then names the piece's first tile)
+struct BigKeyed { int64_t launch_tile, window; WaveEntry e; int16_t sr, sc; };
 
 // What the passes of build_schedule hand to each other and is not part of the Schedule.
 struct BuildState {
@@ -130,6 +135,8 @@ struct BuildState {
     std::vector<int8_t> launch_super;       // per BIG launch (source level * 2 + push): edge of its tasks' super-tiles
     std::vector<int64_t> level_tiles;       // 64 x 64 tiles of the tiled pieces per level of the Cholesky view
     std::vector<int64_t> big_tile0;         // first 128 x 128 tile index of every tiled piece
+    std::vector<int32_t> upd_domain;        // per update: 0 = cut on the target's tile grid; else the re-cut conflict domain it is a
+                                            //   member of = 1 + (the domain's first update - the target's first update)
     std::vector<BigKeyed> bigk;             // the BIG entries as they are found, keyed by (launch, tile)
 };
 
@@ -632,8 +639,158 @@ void build_wave_streams(Schedule& S, BuildState& B) {
     }
 }
 
-// Reads the pieces, their updates and levels, B.launch_super.  Fills the BIG entries as they are found, keyed by (launch,
-// tile): B.bigk, B.big_tile0; big_flops and tile_update_flops (the updates that are not BIG).
+// The blocks of update U into piece T under the TILE cut, a task per super-tile of sr x sc 128 x 128 tiles of the target:
+// fn(row window, column window, ia, mi, ja, nj).
+// The source's rows inside the super-tile's row window (a run of its panel rows) times its rows inside the column window
+// are cut into 128 x 128 blocks IN THE SOURCE'S ROW ORDER -- full blocks but for the last of a run -- one entry each:
+// a 128-row window of the target holds only about 64 rows of a typical source (a face of a sub-box on a
+// separator plane), so per-tile windows were two-thirds ragged (tools/big_stats.py).
+template <class Fn>
+void tile_cut_blocks(const Schedule& S, const SnDesc& T, const UpdDesc& U, int sr, int sc, std::vector<RowRun>& runs,
+                     std::vector<RowRun>& cruns, Fn&& fn) {
+    row_runs(S, T, U, kBigTile * sr, runs);
+    if (sc == sr) cruns = runs;
+    else row_runs(S, T, U, kBigTile * sc, cruns);
+    for (const RowRun& gc : cruns) {
+        if (gc.first >= U.n1) break;
+        const int njt = std::min(gc.len, U.n1 - gc.first);
+        for (const RowRun& gr : runs) {
+            // (the target's rows ascend with the source's: a window strictly above the diagonal holds nothing)
+            if ((int64_t)(gr.win + 1) * sr * kBigTile - 1 < (int64_t)gc.win * sc * kBigTile) continue;
+            for (int cb = 0; cb < njt; cb += kBigTile)
+                for (int rb = 0; rb < gr.len; rb += kBigTile) {
+                    const int mi = std::min(kBigTile, gr.len - rb), nj = std::min(kBigTile, njt - cb);
+                    const int ia = gr.first + rb, ja = gc.first + cb;
+                    if (ia + mi - 1 < ja) continue;   // block strictly above the diagonal
+                    fn(gr.win, gc.win, ia, mi, ja, nj);
+                }
+        }
+    }
+}
+
+// The blocks of update U under the RE-CUT of a conflict domain whose members all have U's rows (find_conflict_domains): the
+// domain's index is then the source's own row order, cut into windows of kBigTile consecutive positions; a task is one
+// (row window, column window), a block is one 128 x 128 square of the source's rows x its first n1 rows:
+// fn(row window, column window, ia, mi, ja, nj, rides).
+// A remainder of <= kStripMax rows (columns) right behind (beside) a full block goes to that block's task where strips
+// ride with dense blocks (`strips`): the strip pairing of build_big_tasks looks for it there.  The corner of two
+// remainders stays a task of its own: it rides with nothing, and a second entry would double its neighbour's length.
+template <class Fn>
+void recut_blocks(const UpdDesc& U, bool strips, Fn&& fn) {
+    strips = strips && U.K >= kDenseChunk;
+    for (int ja = 0; ja < U.n1; ja += kBigTile)
+        for (int ia = ja; ia < U.m; ia += kBigTile) {   // (ia < ja: strictly above the diagonal)
+            const int mi = std::min(kBigTile, U.m - ia), nj = std::min(kBigTile, U.n1 - ja);
+            const bool row_strip = strips && mi <= kStripMax && nj == kBigTile && ia >= ja + kBigTile;
+            const bool col_strip = strips && !row_strip && nj <= kStripMax && mi == kBigTile && ja >= kBigTile;
+            fn(ia / kBigTile - row_strip, ja / kBigTile - col_strip, ia, mi, ja, nj, row_strip || col_strip);
+        }
+}
+
+// Issued work of one block at the measured rates, in ns (the decision of find_conflict_domains):
+// k_chol_dense multiplies the whole 128 x 128 block per 8-wide k chunk whatever the window holds, a strip that rides with
+// a full block costs an eighth of that, k_chol_big pays a fixed part per 16-wide chunk and a part per 16 x 16 fragment.
+int64_t issued_ns(const BuildKnobs& K, int mi, int nj, int k, bool rides) {
+    if (rides) return (int64_t)ceil_div(k, kDenseChunk) * kIssueStripNs;
+    const bool dense = K.dense_mode != 0 && k >= kDenseChunk && (K.dense_mode == 4 || mi * nj >= K.dense_fill_min);
+    if (dense) return (int64_t)ceil_div(k, kDenseChunk) * kIssueDenseNs;
+    return (int64_t)ceil_div(k, 16) * (kIssueRaggedNs + (int64_t)kIssueFragmentNs * ceil_div(mi, 16) * ceil_div(nj, 16));
+}
+
+// Reads the pieces, their updates and levels, B.launch_super, the knobs.  Fills B.upd_domain.
+// CONFLICT DOMAINS.  The tile grid exists to fix the order of sums: an entry (r, c) of L is written by source A only
+// if both r and c are rows of A, so two sources of one launch meet on a target piece only if they share a row that is
+// one of the piece's columns.  Per BIG launch and target piece -- over all sources, whatever is active, so that every
+// rank of a distributed run decides alike -- the sources that share a column (transitively) are one domain; different
+// domains write disjoint entries even inside one tile.  A domain whose members all have the SAME rows in the piece (a
+// single source; the two sides of a separator plane) is cut in the members' own row order instead of on the grid
+// (recut_blocks): windows of 128 positions are full but for the last, where a 128-row window of the target held about 64
+// rows.  Taken only where it issues less work (issued_ns), a function of the pattern and the knobs alone; every other
+// domain keeps the tile cut.  PARSY_BIG_RECUT=0: the tile cut everywhere.
+void find_conflict_domains(Schedule& S, BuildState& B) {
+    const BuildKnobs& K = B.knobs;
+    const int nc = (int)S.csn.size();
+    B.upd_domain.assign(S.upd.size(), 0);
+    if (S.solve_only || !K.big_recut) return;
+    std::vector<std::pair<int64_t, int64_t>> big;   // (launch, update) of one piece's BIG updates
+    std::vector<int64_t> owner;                     // per column of the piece: launch << 32 | first member that names it
+    std::vector<int32_t> root;                      // union-find over the members of one launch, the smallest index on top
+    std::vector<std::pair<int32_t, int32_t>> members;   // (domain, member), sorted
+    std::vector<RowRun> runs, cruns;
+    auto find = [&](int32_t x) {
+        while (root[(size_t)x] != x) x = root[(size_t)x] = root[(size_t)root[(size_t)x]];
+        return x;
+    };
+    for (int t = 0; t < nc; ++t) {
+        const SnDesc& T = S.csn[t];
+        if (is_small(T)) continue;
+        big.clear();
+        for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u)
+            if (is_big(S, S.upd[u], t)) big.push_back({big_launch_of(S.level_of[S.upd_src[u]], S.level_of[t]), u});
+        std::stable_sort(big.begin(), big.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        owner.assign((size_t)T.w, -1);
+        for (size_t i = 0; i < big.size();) {
+            size_t j = i;
+            while (j < big.size() && big[j].first == big[i].first) ++j;
+            const int64_t launch = big[i].first;
+            const int32_t nm = (int32_t)(j - i);
+            root.resize((size_t)nm);
+            for (int32_t q = 0; q < nm; ++q) {
+                root[(size_t)q] = q;
+                const UpdDesc& U = S.upd[big[i + q].second];
+                for (int k = 0; k < U.n1; ++k) {
+                    const int c = rel_at(S, T, U, k);
+                    if (c < 0 || c >= T.w) throw std::runtime_error("schedule: a column row of an update lies outside its target");
+                    int64_t& o = owner[(size_t)c];
+                    if (o < 0 || (o >> 32) != launch) {
+                        o = (launch << 32) | q;
+                        continue;
+                    }
+                    const int32_t a = find(q), b = find((int32_t)(o & 0xffffffff));
+                    if (a < b) root[(size_t)b] = a;
+                    else root[(size_t)a] = b;
+                }
+            }
+            const int sr = K.super_r ? K.super_r : B.launch_super[(size_t)launch];
+            const int sc = K.super_r ? K.super_c : B.launch_super[(size_t)launch];
+            members.clear();
+            for (int32_t q = 0; q < nm; ++q) members.push_back({find(q), q});
+            std::sort(members.begin(), members.end());
+            for (size_t d0 = 0, d1; d0 < members.size(); d0 = d1) {
+                const int32_t q = members[d0].first;   // (= its first member: the smallest index is on top)
+                for (d1 = d0; d1 < members.size() && members[d1].first == q; ++d1) {}
+                // every member with q's rows?
+                const UpdDesc& U0 = S.upd[big[i + q].second];
+                bool same = true;
+                for (size_t d = d0 + 1; d < d1 && same; ++d) {
+                    const UpdDesc& U = S.upd[big[i + members[d].second].second];
+                    same = U.m == U0.m && U.n1 == U0.n1;
+                    for (int k = 0; k < U.m && same; ++k) same = rel_at(S, T, U, k) == rel_at(S, T, U0, k);
+                }
+                if (!same) continue;
+                int64_t tile_ns = 0, recut_ns = 0;
+                for (size_t d = d0; d < d1; ++d) {
+                    const UpdDesc& U = S.upd[big[i + members[d].second].second];
+                    tile_cut_blocks(S, T, U, sr, sc, runs, cruns, [&](int, int, int, int mi, int, int nj) {
+                        tile_ns += issued_ns(K, mi, nj, U.K, false);
+                    });
+                    recut_blocks(U, K.dense_strips && K.dense_mode != 0, [&](int, int, int, int mi, int, int nj, bool rides) {
+                        recut_ns += issued_ns(K, mi, nj, U.K, rides);
+                    });
+                }
+                if (recut_ns >= tile_ns) continue;
+                const int64_t first = big[i + q].second - T.upd0;
+                if (first >= 0x7fffffff) throw std::runtime_error("schedule: too many updates of one piece");
+                for (size_t d = d0; d < d1; ++d) B.upd_domain[(size_t)big[i + members[d].second].second] = (int32_t)first + 1;
+            }
+            i = j;
+        }
+    }
+}
+
+// Reads the pieces, their updates and levels, B.launch_super, B.upd_domain.  Fills the BIG entries as they are found, keyed
+// by (launch, tile) or (launch, piece, domain, window): B.bigk, B.big_tile0; big_flops and tile_update_flops (the updates
+// that are not BIG).
 // BIG: the wide descendants, cut along the 128-row windows of the target's panel
 void collect_big_entries(Schedule& S, BuildState& B) {
     const int nc = (int)S.csn.size();
@@ -659,34 +816,25 @@ void collect_big_entries(Schedule& S, BuildState& B) {
             if (lev_s >= lev_t) throw std::runtime_error("schedule: an update source is not below its target");
             const int64_t launch = big_launch_of(lev_s, lev_t);
             const int sr = env_sr ? env_sr : B.launch_super[(size_t)launch], sc = env_sr ? env_sc : B.launch_super[(size_t)launch];
-            // A task owns a SUPER-TILE of sr x sc 128 x 128 tiles of the target.  The source's rows inside the
-            // super-tile's row window (a run of its panel rows) times its rows inside the column window are cut into
-            // 128 x 128 blocks IN THE SOURCE'S ROW ORDER -- full blocks but for the last of a run -- one entry each:
-            // a 128-row window of the target holds only about 64 rows of a typical source (a face of a sub-box on a
-            // separator plane), so per-tile windows were two-thirds ragged (tools/big_stats.py).  The blocks of one
-            // source touch different entries of L; the sources stay in update order.
-            row_runs(S, T, U, kBigTile * sr, runs);
-            if (sc == sr) cruns = runs;
-            else row_runs(S, T, U, kBigTile * sc, cruns);
-            for (const RowRun& gc : cruns) {
-                if (gc.first >= U.n1) break;
-                const int njt = std::min(gc.len, U.n1 - gc.first);
-                for (const RowRun& gr : runs) {
-                    // (the target's rows ascend with the source's: a window strictly above the diagonal holds nothing)
-                    if ((int64_t)(gr.win + 1) * sr * kBigTile - 1 < (int64_t)gc.win * sc * kBigTile) continue;
-                    const int64_t tile = B.big_tile0[t] + (int64_t)gc.win * sc * nbr128 + (int64_t)gr.win * sr;
-                    for (int cb = 0; cb < njt; cb += kBigTile)
-                        for (int rb = 0; rb < gr.len; rb += kBigTile) {
-                            const int mi = std::min(kBigTile, gr.len - rb), nj = std::min(kBigTile, njt - cb);
-                            const int ia = gr.first + rb, ja = gc.first + cb;
-                            if (ia + mi - 1 < ja) continue;   // block strictly above the diagonal
-                            B.bigk.push_back(BigKeyed{(launch << 40) | tile,
-                                                      WaveEntry{U.src, (int32_t)std::max<int64_t>(U.rel, 0), U.ld, U.K, ia, ja,
-                                                                mi | (nj << 8) | ((U.rel < 0) << 16)},
-                                                      (int16_t)sr, (int16_t)sc});
-                        }
-                }
+            auto entry = [&](int ia, int mi, int ja, int nj) {
+                return WaveEntry{U.src, (int32_t)std::max<int64_t>(U.rel, 0), U.ld, U.K, ia, ja, mi | (nj << 8) | ((U.rel < 0) << 16)};
+            };
+            const int64_t domain = B.upd_domain[(size_t)u];
+            if (domain) {
+                // a re-cut domain: a task owns one (row window, column window) of the members' own row order
+                if (U.m / kBigTile >= 0xffff) throw std::runtime_error("schedule: too many windows of one update");
+                recut_blocks(U, B.knobs.dense_strips && B.knobs.dense_mode != 0, [&](int wr, int wc, int ia, int mi, int ja, int nj, bool) {
+                    B.bigk.push_back(BigKeyed{(launch << 40) | B.big_tile0[t], (domain << 32) | ((int64_t)wc << 16) | wr,
+                                              entry(ia, mi, ja, nj), 1, 1});
+                });
+                continue;
             }
+            // A task owns a SUPER-TILE of sr x sc 128 x 128 tiles of the target (tile_cut_blocks).  The blocks of one
+            // source touch different entries of L; the sources stay in update order.
+            tile_cut_blocks(S, T, U, sr, sc, runs, cruns, [&](int wr, int wc, int ia, int mi, int ja, int nj) {
+                const int64_t tile = B.big_tile0[t] + (int64_t)wc * sc * nbr128 + (int64_t)wr * sr;
+                B.bigk.push_back(BigKeyed{(launch << 40) | tile, 0, entry(ia, mi, ja, nj), (int16_t)sr, (int16_t)sc});
+            });
         }
     }
 }
@@ -733,7 +881,9 @@ void build_big_tasks(Schedule& S, BuildState& B) {
     if (bigk.empty()) return;
     const int nc = (int)S.csn.size();
     std::stable_sort(bigk.begin(), bigk.end(),
-                     [](const BigKeyed& a, const BigKeyed& b) { return a.launch_tile < b.launch_tile; });
+                     [](const BigKeyed& a, const BigKeyed& b) {
+                         return a.launch_tile != b.launch_tile ? a.launch_tile < b.launch_tile : a.window < b.window;
+                     });
     const std::vector<uint8_t> launch_dense = dense_share_per_launch(B);
     // mode 1: full blocks, and windows filled well enough that a whole-block product beats the ragged kernel's rate
     const int fill_min = B.knobs.dense_fill_min;
@@ -747,16 +897,25 @@ void build_big_tasks(Schedule& S, BuildState& B) {
     int t = 0;
     for (size_t i = 0; i < bigk.size();) {
         size_t j = i;
-        while (j < bigk.size() && bigk[j].launch_tile == bigk[i].launch_tile) ++j;
+        while (j < bigk.size() && bigk[j].launch_tile == bigk[i].launch_tile && bigk[j].window == bigk[i].window) ++j;
         const int64_t launch = bigk[i].launch_tile >> 40, tile = bigk[i].launch_tile & ((1LL << 40) - 1);
         // dense entries first, each part in update order
         size_t at = i;
         int64_t weight = 0, dweight = 0, dchunks = 0;
         const int lmode = launch_dense[(size_t)launch];
+        // (A task of a re-cut domain holds a remainder only beside its full block -- recut_blocks -- so there it rides
+        // with the block also in a launch that hands k_chol_dense everything: as an entry of its own it would be
+        // multiplied as a whole block and double the task's length.)
+        const bool strips_ride = bigk[i].window != 0 && lmode == 2 && B.knobs.dense_strips;
+        auto dense_here = [&](const WaveEntry& E) {
+            if (!is_dense(E, lmode)) return false;
+            const int mi = entry_rows(E), nj = entry_cols(E);
+            return !(strips_ride && ((mi <= kStripMax && nj == kBigTile) || (nj <= kStripMax && mi == kBigTile)));
+        };
         if (lmode)
             for (size_t q = i; q < j; ++q) {
                 const WaveEntry& E = bigk[q].e;
-                if (!is_dense(E, lmode)) continue;
+                if (!dense_here(E)) continue;
                 S.big_entries[at++] = E;
                 dchunks += ceil_div(E.K, kDenseChunk);
                 dweight += ceil_div(E.K, 16) + 2;
@@ -778,7 +937,7 @@ void build_big_tasks(Schedule& S, BuildState& B) {
             }
             for (size_t q = i; q < j && !strip_of.empty(); ++q) {
                 const WaveEntry& R = bigk[q].e;
-                if (is_dense(R, lmode)) continue;
+                if (dense_here(R)) continue;
                 const int mi = entry_rows(R), nj = entry_cols(R);
                 const bool row_strip = mi <= kStripMax && nj == kBigTile, col_strip = nj <= kStripMax && mi == kBigTile;
                 if (!row_strip && !col_strip) continue;
@@ -796,7 +955,7 @@ void build_big_tasks(Schedule& S, BuildState& B) {
             }
         }
         for (size_t q = i; q < j; ++q)
-            if (!is_dense(bigk[q].e, lmode) && !absorbed[q - i]) {
+            if (!dense_here(bigk[q].e) && !absorbed[q - i]) {
                 S.big_entries[at++] = bigk[q].e;
                 weight += ceil_div(bigk[q].e.K, 16) + 4;
             }
@@ -810,12 +969,15 @@ void build_big_tasks(Schedule& S, BuildState& B) {
         }
         const int nbr128 = ceil_div(S.csn[t].r, kBigTile);
         const int64_t local = tile - B.big_tile0[t];
-        S.big_all.push_back(Schedule::BigTask{t, (int32_t)(local % nbr128) * kBigTile,
-                                              (int32_t)(local / nbr128) * kBigTile,
+        // (a re-cut domain's task: its window of the domain's index, in units of kBigTile positions)
+        const int64_t window = bigk[i].window;
+        const int32_t row0 = window ? (int32_t)(window & 0xffff) * kBigTile : (int32_t)(local % nbr128) * kBigTile;
+        const int32_t col0 = window ? (int32_t)((window >> 16) & 0xffff) * kBigTile : (int32_t)(local / nbr128) * kBigTile;
+        S.big_all.push_back(Schedule::BigTask{t, row0, col0,
                                               (int32_t)std::min<int64_t>(weight, INT32_MAX), (int64_t)i, (int64_t)jend,
                                               (int32_t)(launch >> 1), (int32_t)((launch & 1) == 0), bigk[i].sr, bigk[i].sc,
                                               (int64_t)mid, (int32_t)std::min<int64_t>(dweight, INT32_MAX),
-                                              (int32_t)std::min<int64_t>(dchunks, INT32_MAX), nstrips});
+                                              (int32_t)std::min<int64_t>(dchunks, INT32_MAX), nstrips, (int32_t)(window >> 32)});
         i = j;
     }
 }
@@ -838,6 +1000,7 @@ void build_schedule(const PatternRef& P, const size_t* lC, const int* A2p, const
     cut_subtrees(S, B);
     choose_super_tiles(S, B);
     build_wave_streams(S, B);
+    find_conflict_domains(S, B);
     collect_big_entries(S, B);
     build_big_tasks(S, B);
     build_launches(S, active);
@@ -1250,7 +1413,7 @@ Launch emit_big(Schedule& S, int big_group, const BigTaskList& all, Launch L, bo
         L.count = (int32_t)v.size();
         return L;
     }
-    struct Group { int64_t key, weight; int32_t maxw; BigTaskList tasks; };
+    struct Group { std::pair<int64_t, int64_t> key; int64_t weight; int32_t maxw; BigTaskList tasks; };
     BigTaskList seq[8];
     int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto least = [&] {
@@ -1272,11 +1435,12 @@ Launch emit_big(Schedule& S, int big_group, const BigTaskList& all, Launch L, bo
             }
             break;
         }
-        std::vector<std::pair<int64_t, const Schedule::BigTask*>> keyed;
+        using GroupKey = std::pair<int64_t, int64_t>;   // (piece, domain), window group
+        std::vector<std::pair<GroupKey, const Schedule::BigTask*>> keyed;
         keyed.reserve(rest.size());
         for (const Schedule::BigTask* b : rest) {
             const int64_t gi = b->row0 / (kBigTile * g), gj = b->col0 / (kBigTile * g);
-            keyed.push_back({((int64_t)b->sn << 32) | (gj << 16) | gi, b});
+            keyed.push_back({GroupKey{((int64_t)b->sn << 32) | b->domain, (gj << 32) | gi}, b});
         }
         std::stable_sort(keyed.begin(), keyed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
         std::vector<Group> groups;
@@ -2442,13 +2606,35 @@ int64_t check_schedule(const Schedule& S, std::string& what) {
                 }
         }
     }
+    // What fixes the order of sums within a launch: no two tasks write the same entry of L.  Tasks of the tile cut own
+    // disjoint super-tiles.  Tasks of re-cut conflict domains: per launch and piece every column belongs to at most one
+    // domain (the tile cut counts as one), a domain's members all have the same rows, its tasks have pairwise
+    // disjoint windows of that index, and every entry's rows lie in its task's window.
+    std::vector<int32_t> col_domain;                  // of the current (launch, piece): -1 = not named yet
+    std::map<int32_t, int64_t> domain_upd;            // ... domain -> its first update seen: the rows every member must have
+    std::vector<std::array<int32_t, 3>> domain_wins;  // ... (domain, row0, col0) of its tasks
+    const Schedule::BigTask* group = nullptr;
+    auto close_group = [&]() {
+        std::sort(domain_wins.begin(), domain_wins.end());
+        if (std::adjacent_find(domain_wins.begin(), domain_wins.end()) != domain_wins.end())
+            fail("two BIG tasks of piece " + std::to_string(group->sn) + " own the same window of a conflict domain");
+        domain_wins.clear();
+        domain_upd.clear();
+    };
     for (const Schedule::BigTask& b : S.big_all) {
         const SnDesc& T = S.csn[b.sn];
         if (b.src_level >= S.level_of[b.sn] || (b.next != 0) != (b.src_level == S.level_of[b.sn] - 1))
             fail("BIG task of piece " + std::to_string(b.sn) + " is filed under the wrong source level");
+        if (!group || group->sn != b.sn || group->src_level != b.src_level || group->next != b.next) {
+            if (group) close_group();
+            group = &b;
+            col_domain.assign((size_t)T.w, -1);
+        }
         const int win_r = kBigTile * b.sr, win_c = kBigTile * b.sc;
-        if (b.sr < 1 || b.sc < 1 || b.row0 % win_r || b.col0 % win_c || b.row0 + win_r <= b.col0 || b.row0 >= T.r || b.col0 >= T.w)
+        if (b.domain < 0 || b.sr < 1 || b.sc < 1 || b.row0 % win_r || b.col0 % win_c || b.row0 + win_r <= b.col0 ||
+            (b.domain ? b.sr != 1 || b.sc != 1 : b.row0 >= T.r || b.col0 >= T.w))
             fail("BIG task of piece " + std::to_string(b.sn) + " has a bad tile origin");
+        if (b.domain) domain_wins.push_back({b.domain, b.row0, b.col0});
         for (int64_t e = b.e0; e < b.e1; ++e) {
             const WaveEntry& E = S.big_entries[(size_t)e];
             int64_t u = -1;
@@ -2464,14 +2650,41 @@ int64_t check_schedule(const Schedule& S, std::string& what) {
                 fail("BIG entry " + std::to_string(e) + " of piece " + std::to_string(b.sn) + " has a bad window or source");
                 continue;
             }
-            // the rows it names land in the task's tile
             auto rel_at = [&](int k) { return ident ? k : S.relpos[(size_t)S.upd[u].rel + k] - T.rbias; };
-            if (rel_at(E.ia) / win_r != b.row0 / win_r || rel_at(E.ia + mi + ms - 1) / win_r != b.row0 / win_r ||
-                rel_at(E.ja) / win_c != b.col0 / win_c || rel_at(E.ja + nj + ns - 1) / win_c != b.col0 / win_c)
-                fail("BIG entry " + std::to_string(e) + " names rows outside its task's tile");
+            for (int k = E.ja; k < E.ja + nj + ns; ++k) {
+                int32_t& d = col_domain[(size_t)rel_at(k)];
+                if (d >= 0 && d != b.domain)
+                    fail("column " + std::to_string(rel_at(k)) + " of piece " + std::to_string(b.sn) + " belongs to two conflict domains of a launch");
+                d = b.domain;
+            }
+            if (!b.domain) {
+                // tile cut: the rows it names land in the task's tile
+                if (rel_at(E.ia) / win_r != b.row0 / win_r || rel_at(E.ia + mi + ms - 1) / win_r != b.row0 / win_r ||
+                    rel_at(E.ja) / win_c != b.col0 / win_c || rel_at(E.ja + nj + ns - 1) / win_c != b.col0 / win_c)
+                    fail("BIG entry " + std::to_string(e) + " names rows outside its task's tile");
+            } else {
+                // re-cut: the rows it names lie in the task's window of the domain's index (a remainder of <= kStripMax
+                // positions at the end of the index may sit in the window before it: recut_blocks) ...
+                const UpdDesc& U = S.upd[u];
+                auto inside = [](int first, int count, int win0, int len) {
+                    const int end = first + count, wend = win0 + kBigTile;
+                    return first >= win0 && (end <= wend || (end <= len && len - wend <= kStripMax));
+                };
+                if (!inside(E.ia, mi + ms, b.row0, U.m) || !inside(E.ja, nj + ns, b.col0, U.n1))
+                    fail("BIG entry " + std::to_string(e) + " names rows outside its task's window");
+                // ... and that index is every member's own row order
+                const UpdDesc& U0 = S.upd[(size_t)domain_upd.emplace(b.domain, u).first->second];
+                bool same = U.m == U0.m && U.n1 == U0.n1 && (U.rel < 0) == (U0.rel < 0);
+                if (&U != &U0 && !ident) {
+                    for (int k = E.ia; k < E.ia + mi + ms && same; ++k) same = S.relpos[(size_t)U.rel + k] == S.relpos[(size_t)U0.rel + k];
+                    for (int k = E.ja; k < E.ja + nj + ns && same; ++k) same = S.relpos[(size_t)U.rel + k] == S.relpos[(size_t)U0.rel + k];
+                }
+                if (!same) fail("BIG entry " + std::to_string(e) + ": the members of its conflict domain do not have the same rows");
+            }
             covered[(size_t)u] += block_flops(E);
         }
     }
+    if (group) close_group();
     {
         // the BIG / DENSE launches hold every non-empty part (dense: [e0, em), ragged: [em, e1)) of every task of an
         // active target exactly once, under its (source level, kind), the dense part in a launch enqueued BEFORE the

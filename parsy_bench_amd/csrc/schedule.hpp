@@ -97,6 +97,10 @@ struct WaveEntry {    // one (descendant, 32x32 sub-tile) pair of the tile kerne
 // kStripMax rows right behind the block, times the block's column window -- and / or of its column run: k_chol_dense
 // multiplies them with the operands it has staged for the block, plus a strip of 16 rows per chunk.
 constexpr int kStripMax = 16;
+// Issued work at the measured rates (ns), by which a conflict domain chooses between the tile cut and the re-cut
+// (schedule.cpp: issued_ns): a k_chol_dense chunk of 8 k, a strip riding with it, a k_chol_big chunk of 16 k = a fixed
+// part + a part per 16 x 16 fragment (1.0 + 2.1 * fragments / 35 us, fitted to one Flan-class launch).
+constexpr int kIssueDenseNs = 2090, kIssueStripNs = 260, kIssueRaggedNs = 1000, kIssueFragmentNs = 60;
 inline int entry_rows(const WaveEntry& E) { return E.mn & 255; }          // rows in the row window
 inline int entry_cols(const WaveEntry& E) { return (E.mn >> 8) & 255; }   // rows in the column window
 inline bool big_ident(const WaveEntry& E) { return (E.mn >> 16) & 1; }
@@ -318,7 +322,12 @@ struct Schedule {
     struct BigTask { int32_t sn, row0, col0, weight; int64_t e0, e1; int32_t src_level, next;
                      int32_t sr, sc;      // sr x sc: the super-tile's edge in 128 x 128 tiles
                      int64_t em; int32_t dweight, dchunks;
-                     int32_t strips; };   // dense entries of it that carry a strip (WaveEntry::mn)
+                     int32_t strips;      // dense entries of it that carry a strip (WaveEntry::mn)
+                     // 0: a task of the tile cut, (row0, col0) the origin of its super-tile in the target's panel.  Else the
+                     // re-cut conflict domain of its piece and launch it belongs to (1 + the domain's first update, counted from
+                     // the piece's first): its entries are blocks of the members' own row order, (row0, col0) = kBigTile x its
+                     // (row window, column window) of that order -- the kernels read neither.
+                     int32_t domain; };
     std::vector<BigTask> big_all;         // every task, grouped by (src_level, next)
     std::vector<TileDesc> big_tasks;      // tasks of the launches (active targets): k_chol_big: wp, sp = the ragged part [em, e1) of a
                                           // task; k_chol_dense: its dense part [e0, em), part = its 8-wide k chunks

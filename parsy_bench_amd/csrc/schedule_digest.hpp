@@ -34,9 +34,9 @@ struct Fnv1a {
             bytes(raw, sizeof(T));
         }
     }
-    void value(const Schedule::BigTask& b) {   // (padding behind `strips`: member by member)
+    void value(const Schedule::BigTask& b) {   // (padding between the members: member by member)
         value(b.sn), value(b.row0), value(b.col0), value(b.weight), value(b.e0), value(b.e1), value(b.src_level), value(b.next);
-        value(b.sr), value(b.sc), value(b.em), value(b.dweight), value(b.dchunks), value(b.strips);
+        value(b.sr), value(b.sc), value(b.em), value(b.dweight), value(b.dchunks), value(b.strips), value(b.domain);
     }
     template <class T>
     void vec(const std::vector<T>& v) {

@@ -56,6 +56,7 @@ lib.parsy_debug_dense_tasks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 nt = lib.parsy_debug_dense_tasks(h, None, 0)
 dt = np.zeros((nt, 2), dtype=np.int32)
 lib.parsy_debug_dense_tasks(h, dt.ctypes.data, nt)
+dt[:, 1] &= (1 << 30) - 1   # (TileDesc::part of a dense task: its chunk count, bit 30 = it carries strips)
 tot_bal = tot_mk = 0.0
 rows = []
 for lid in np.unique(dt[:, 0]):
