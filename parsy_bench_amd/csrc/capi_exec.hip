@@ -488,7 +488,8 @@ int64_t parsy_debug_big_windows(const parsy_plan* pl, int64_t* out, int64_t cap)
 }
 
 // Diagnostics (tools/recut_stats.py, tests/test_recut_host.py): the BIG tasks of the plan, in the order of the two exports
-// above, as rows of (launch = 2 * source level + push, piece, conflict domain (0: tile cut), row0, col0, entries, dense
+// above, as rows of (launch = 2 * source level + push, piece, conflict domain (0: tile cut; from kIntervalDomain on: cut in
+// intervals of the target's positions), row0, col0, entries, dense
 // entries, issued fragment-chunks, 16-wide k chunks, of which in dense entries).  Issued fragment-chunks: per 16-wide k chunk of an entry the 16 x 16
 // fragments that are multiplied -- a dense entry its whole 128 x 128 block (64) and 8 per strip that rides with it, a
 // ragged entry those its window touches.

@@ -6,6 +6,7 @@
 #include <map>
 #include <algorithm>
 #include <queue>
+#include <set>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -83,7 +84,10 @@ struct BuildKnobs {
     double dense_all_share;  // PARSY_DENSE_ALL_SHARE (percent; kDenseAllShare): ragged share up to which k_chol_dense takes it too
     int dense_fill_min;      // PARSY_DENSE_FILL (percent of 128 x 128; kDenseMinFill), in entries: windows this full count as dense
     bool dense_strips;       // PARSY_DENSE_STRIPS (1): 0 = no strips ride with the dense blocks
-    bool big_recut;          // PARSY_BIG_RECUT (1): 0 = every BIG update is cut on the target's tile grid (find_conflict_domains)
+    bool big_recut_set;      // PARSY_BIG_RECUT: 0 = every BIG update is cut on the target's tile grid; 1 = domains of one row set
+    int big_recut;           //   in their own row order; 2 = the other domains in intervals too; 3 = as 2 without the tail guard
+                             //   (tests, tools).  Set: whatever the size of the job; unset: 2 from kPieceAutoFlops update flops
+                             //   on where PARSY_BIG_SUPER is unset too, else 1 (find_conflict_domains)
 };
 
 BuildKnobs read_build_knobs() {
@@ -117,7 +121,8 @@ BuildKnobs read_build_knobs() {
     K.dense_all_share = percent("PARSY_DENSE_ALL_SHARE", kDenseAllShare) / 100.0;
     K.dense_fill_min = percent("PARSY_DENSE_FILL", kDenseMinFill) * kBigTile * kBigTile / 100;
     K.dense_strips = env_int("PARSY_DENSE_STRIPS", 1) != 0;
-    K.big_recut = env_int("PARSY_BIG_RECUT", 1) != 0;
+    K.big_recut_set = std::getenv("PARSY_BIG_RECUT") != nullptr;
+    K.big_recut = std::max(0, std::min(3, env_int("PARSY_BIG_RECUT", 2)));
     return K;
 }
 
@@ -136,8 +141,11 @@ struct BuildState {
     std::vector<int64_t> level_tiles;       // 64 x 64 tiles of the tiled pieces per level of the Cholesky view
     std::vector<int64_t> big_tile0;         // first 128 x 128 tile index of every tiled piece
     std::vector<int32_t> upd_domain;        // per update: 0 = cut on the target's tile grid; else the re-cut conflict domain it is a
-                                            //   member of = 1 + (the domain's first update - the target's first update)
-    std::vector<BigKeyed> bigk;             // the BIG entries as they are found, keyed by (launch, tile)
+                                            //   member of = 1 + (the domain's first update - the target's first update),
+                                            //   + kIntervalDomain where it is cut in intervals of the target's positions
+    std::vector<int64_t> upd_bounds;        // per update of an interval domain: where its domain's intervals start in `bounds`
+    std::vector<int32_t> bounds;            // per interval domain: the count, then the first position of every interval, ascending
+    std::vector<BigKeyed> bigk;            // the BIG entries as they are found, keyed by (launch, tile)
 };
 
 // A run of an update's rows that falls into one window of the target's rows.
@@ -697,8 +705,65 @@ int64_t issued_ns(const BuildKnobs& K, int mi, int nj, int k, bool rides) {
     return (int64_t)ceil_div(k, 16) * (kIssueRaggedNs + (int64_t)kIssueFragmentNs * ceil_div(mi, 16) * ceil_div(nj, 16));
 }
 
-// Reads the pieces, their updates and levels, B.launch_super, the knobs.  Fills B.upd_domain.
-// CONFLICT DOMAINS.  The tile grid exists to fix the order of sums: an entry (r, c) of L is written by source A only
+// The INTERVAL cut of a conflict domain whose members' rows differ (find_conflict_domains): where its intervals start.
+// The members' rows are swept by their position in T's panel, all members merged.  An interval starts at position 0, at
+// T.w -- so that the column intervals are exactly the intervals below T.w -- and at the first position where some member
+// would receive row kBigTile + 1 of the current interval.  Every member then has at most kBigTile rows in an interval,
+// consecutive in its own panel because positions ascend with its own row order: two faces of 64 rows each per 128 target
+// rows grow an interval to 256 target rows that holds one full block of each.
+void interval_bounds(const Schedule& S, const SnDesc& T, const std::vector<const UpdDesc*>& members,
+                     std::vector<std::pair<int32_t, int32_t>>& rows, std::vector<int32_t>& count, std::vector<int32_t>& bounds) {
+    rows.clear();
+    for (size_t q = 0; q < members.size(); ++q)
+        for (int k = 0; k < members[q]->m; ++k) rows.push_back({rel_at(S, T, *members[q], k), (int32_t)q});
+    std::sort(rows.begin(), rows.end());
+    count.assign(members.size(), 0);
+    bounds.assign(1, 0);
+    for (size_t a = 0, b; a < rows.size(); a = b) {
+        const int32_t pos = rows[a].first;
+        for (b = a; b < rows.size() && rows[b].first == pos; ++b) {}
+        int32_t start = 0;
+        if (pos >= T.w && bounds.back() < T.w) start = T.w;
+        for (size_t c = a; c < b && !start; ++c)
+            if (count[(size_t)rows[c].second] == kBigTile) start = pos;
+        if (start) {
+            bounds.push_back(start);
+            std::fill(count.begin(), count.end(), 0);
+        }
+        for (size_t c = a; c < b; ++c) ++count[(size_t)rows[c].second];
+    }
+}
+
+// The blocks of update U under the INTERVAL cut of its domain, whose nb intervals start at bounds[0 .. nb):
+// fn(row interval, column interval, ia, mi, ja, nj) -- the member's run of rows in the one times its run in the other,
+// both in its own row numbering.  A block strictly above the diagonal is dropped as tile_cut_blocks drops it, one that
+// straddles it is kept whole.
+template <class Fn>
+void interval_blocks(const Schedule& S, const SnDesc& T, const UpdDesc& U, const int32_t* bounds, int nb, std::vector<RowRun>& runs,
+                     Fn&& fn) {
+    runs.clear();
+    int w = 0;
+    for (int k = 0; k < U.m;) {
+        const int pos = rel_at(S, T, U, k);
+        while (w + 1 < nb && bounds[w + 1] <= pos) ++w;
+        int k1 = k + 1;
+        while (k1 < U.m && (w + 1 >= nb || rel_at(S, T, U, k1) < bounds[w + 1])) ++k1;
+        if (k1 - k > kBigTile) throw std::runtime_error("schedule: an interval holds more than a block of one update's rows");
+        runs.push_back(RowRun{w, k, k1 - k});
+        k = k1;
+    }
+    for (const RowRun& gc : runs) {
+        if (gc.first >= U.n1) break;
+        const int nj = std::min(gc.len, U.n1 - gc.first);
+        for (const RowRun& gr : runs) {
+            if (gr.win < gc.win || gr.first + gr.len - 1 < gc.first) continue;   // block strictly above the diagonal
+            fn(gr.win, gc.win, gr.first, gr.len, gc.first, nj);
+        }
+    }
+}
+
+// Reads the pieces, their updates and levels, B.launch_super, the knobs.  Fills B.upd_domain, B.upd_bounds, B.bounds.
+// CONFLICT DOMAINS. The tile grid exists to fix the order of sums: an entry (r, c) of L is written by source A only
 // if both r and c are rows of A, so two sources of one launch meet on a target piece only if they share a row that is
 // one of the piece's columns.  Per BIG launch and target piece -- over all sources, whatever is active, so that every
 // rank of a distributed run decides alike -- the sources that share a column (transitively) are one domain; different
@@ -707,16 +772,62 @@ int64_t issued_ns(const BuildKnobs& K, int mi, int nj, int k, bool rides) {
 // (recut_blocks): windows of 128 positions are full but for the last, where a 128-row window of the target held about 64
 // rows.  Taken only where it issues less work (issued_ns), a function of the pattern and the knobs alone; every other
 // domain keeps the tile cut.  PARSY_BIG_RECUT=0: the tile cut everywhere.
+// A domain whose members' rows DIFFER (the faces of neighbouring sub-boxes, chained through shared columns) is cut in
+// intervals of the target's positions (interval_bounds, interval_blocks) where that issues less than the tile cut AND the
+// TAIL GUARD holds: its longest interval task issues no more than the larger of its longest task under the tile cut and
+// the launch's work under the tile cut / kIssueSlots.  An interval task holds a block of every member, so it is longer
+// than a tile's; with tasks dealt heaviest first, one below the per-slot average cannot be what ends a launch, and one no
+// longer than the tile cut's longest ends it no later (forcing 4 x 4 super-tiles lost 19 ms of dense time to long last
+// tasks).  PARSY_BIG_RECUT=1: never; 3: without the guard.
 void find_conflict_domains(Schedule& S, BuildState& B) {
     const BuildKnobs& K = B.knobs;
     const int nc = (int)S.csn.size();
     B.upd_domain.assign(S.upd.size(), 0);
-    if (S.solve_only || !K.big_recut) return;
+    B.upd_bounds.assign(S.upd.size(), -1);
+    B.bounds.clear();
+    // The interval cut is the default from the size on at which it was measured (Flan-class: the multi-source launches
+    // of a job whose supernodes are cut into pieces run for milliseconds each); smaller jobs, and plans whose BIG launches
+    // exist only because a diagnostic knob forces them, keep the cut of domains of one row set unless the knob says otherwise;
+    // so does a plan with one super-tile shape forced on every launch (PARSY_BIG_SUPER: a diagnostic of the tile cut).
+    const int recut = K.big_recut_set || (S.update_flops >= kPieceAutoFlops && !K.super_r) ? K.big_recut : 1;
+    if (S.solve_only || !recut) return;
+    std::vector<RowRun> runs, cruns;
+    auto super_of = [&](int64_t launch) {
+        return std::pair<int, int>{K.super_r ? K.super_r : B.launch_super[(size_t)launch], K.super_r ? K.super_c : B.launch_super[(size_t)launch]};
+    };
+    // the tail guard's per-slot average: every launch's issued work under the tile cut, over all targets
+    std::vector<int64_t> launch_tile_ns(B.launch_super.size(), 0);
+    if (recut == 2)
+        for (int t = 0; t < nc; ++t) {
+            const SnDesc& T = S.csn[t];
+            if (is_small(T)) continue;
+            for (int64_t u = T.upd0; u < T.upd0 + T.nupd; ++u) {
+                const UpdDesc& U = S.upd[u];
+                if (!is_big(S, U, t)) continue;
+                const int64_t launch = big_launch_of(S.level_of[S.upd_src[u]], S.level_of[t]);
+                const auto [sr, sc] = super_of(launch);
+                int64_t ns = 0;
+                tile_cut_blocks(S, T, U, sr, sc, runs, cruns, [&](int, int, int, int mi, int, int nj) { ns += issued_ns(K, mi, nj, U.K, false); });
+                launch_tile_ns[(size_t)launch] += ns;
+            }
+        }
+    std::vector<const UpdDesc*> member_upd;
+    std::vector<std::pair<int32_t, int32_t>> sweep_rows;
+    std::vector<int32_t> sweep_count, ivals;
+    std::map<std::pair<int, int>, int64_t> tile_task, ival_task;   // issued ns of the domain's entries per task of either cut
+    std::set<std::array<int, 4>> full_blocks;                      // (row window, column window, ia, ja) of a member's full blocks
+    // (the strips count as riding wherever k_chol_dense is used, whatever PARSY_DENSE_STRIPS says: that knob changes the strips
+    // of a plan, not the cut of its interval domains)
+    const bool strips = K.dense_mode != 0;
+    auto longest = [](const std::map<std::pair<int, int>, int64_t>& m) {
+        int64_t v = 0;
+        for (const auto& kv : m) v = std::max(v, kv.second);
+        return v;
+    };
     std::vector<std::pair<int64_t, int64_t>> big;   // (launch, update) of one piece's BIG updates
     std::vector<int64_t> owner;                     // per column of the piece: launch << 32 | first member that names it
     std::vector<int32_t> root;                      // union-find over the members of one launch, the smallest index on top
     std::vector<std::pair<int32_t, int32_t>> members;   // (domain, member), sorted
-    std::vector<RowRun> runs, cruns;
     auto find = [&](int32_t x) {
         while (root[(size_t)x] != x) x = root[(size_t)x] = root[(size_t)root[(size_t)x]];
         return x;
@@ -751,8 +862,7 @@ void find_conflict_domains(Schedule& S, BuildState& B) {
                     else root[(size_t)a] = b;
                 }
             }
-            const int sr = K.super_r ? K.super_r : B.launch_super[(size_t)launch];
-            const int sc = K.super_r ? K.super_c : B.launch_super[(size_t)launch];
+            const auto [sr, sc] = super_of(launch);
             members.clear();
             for (int32_t q = 0; q < nm; ++q) members.push_back({find(q), q});
             std::sort(members.begin(), members.end());
@@ -767,7 +877,51 @@ void find_conflict_domains(Schedule& S, BuildState& B) {
                     same = U.m == U0.m && U.n1 == U0.n1;
                     for (int k = 0; k < U.m && same; ++k) same = rel_at(S, T, U, k) == rel_at(S, T, U0, k);
                 }
-                if (!same) continue;
+                const int64_t first = big[i + q].second - T.upd0;
+                if (first >= kIntervalDomain - 1) throw std::runtime_error("schedule: too many updates of one piece");
+                if (!same) {
+                    if (recut < 2) continue;
+                    // rows differ: intervals of the target's positions, or the tile cut
+                    member_upd.clear();
+                    for (size_t d = d0; d < d1; ++d) member_upd.push_back(&S.upd[big[i + members[d].second].second]);
+                    interval_bounds(S, T, member_upd, sweep_rows, sweep_count, ivals);
+                    if (ivals.size() >= 0xffff) throw std::runtime_error("schedule: too many intervals of one conflict domain");
+                    tile_task.clear();
+                    ival_task.clear();
+                    int64_t tile_ns = 0, ival_ns = 0;
+                    for (const UpdDesc* U : member_upd) {
+                        // (under the tile cut a remainder right behind or beside a full block of its task rides with it
+                        // as a strip -- build_big_tasks; the full block comes first in the task's runs)
+                        full_blocks.clear();
+                        tile_cut_blocks(S, T, *U, sr, sc, runs, cruns, [&](int wr, int wc, int ia, int mi, int ja, int nj) {
+                            const bool row_strip = mi <= kStripMax && nj == kBigTile, col_strip = nj <= kStripMax && mi == kBigTile;
+                            if (mi == kBigTile && nj == kBigTile) full_blocks.insert({wr, wc, ia, ja});
+                            const bool rides = strips && U->K >= kDenseChunk && (row_strip || col_strip) &&
+                                               full_blocks.count({wr, wc, ia - (row_strip ? kBigTile : 0), ja - (col_strip ? kBigTile : 0)}) != 0;
+                            const int64_t ns = issued_ns(K, mi, nj, U->K, rides);
+                            tile_ns += ns;
+                            tile_task[{wr, wc}] += ns;
+                        });
+                        interval_blocks(S, T, *U, ivals.data(), (int)ivals.size(), runs, [&](int wr, int wc, int, int mi, int, int nj) {
+                            const int64_t ns = issued_ns(K, mi, nj, U->K, false);
+                            ival_ns += ns;
+                            ival_task[{wr, wc}] += ns;
+                        });
+                    }
+                    if (ival_ns >= tile_ns) continue;
+                    if (recut == 2 &&
+                        longest(ival_task) > std::max(longest(tile_task), launch_tile_ns[(size_t)launch] / kIssueSlots))
+                        continue;
+                    const int64_t at = (int64_t)B.bounds.size();
+                    B.bounds.push_back((int32_t)ivals.size());
+                    B.bounds.insert(B.bounds.end(), ivals.begin(), ivals.end());
+                    for (size_t d = d0; d < d1; ++d) {
+                        const size_t u = (size_t)big[i + members[d].second].second;
+                        B.upd_domain[u] = kIntervalDomain + (int32_t)first + 1;
+                        B.upd_bounds[u] = at;
+                    }
+                    continue;
+                }
                 int64_t tile_ns = 0, recut_ns = 0;
                 for (size_t d = d0; d < d1; ++d) {
                     const UpdDesc& U = S.upd[big[i + members[d].second].second];
@@ -779,8 +933,6 @@ void find_conflict_domains(Schedule& S, BuildState& B) {
                     });
                 }
                 if (recut_ns >= tile_ns) continue;
-                const int64_t first = big[i + q].second - T.upd0;
-                if (first >= 0x7fffffff) throw std::runtime_error("schedule: too many updates of one piece");
                 for (size_t d = d0; d < d1; ++d) B.upd_domain[(size_t)big[i + members[d].second].second] = (int32_t)first + 1;
             }
             i = j;
@@ -820,6 +972,15 @@ void collect_big_entries(Schedule& S, BuildState& B) {
                 return WaveEntry{U.src, (int32_t)std::max<int64_t>(U.rel, 0), U.ld, U.K, ia, ja, mi | (nj << 8) | ((U.rel < 0) << 16)};
             };
             const int64_t domain = B.upd_domain[(size_t)u];
+            if (domain >= kIntervalDomain) {
+                // an interval domain: a task owns one (row interval, column interval) of the target's positions
+                const int32_t* iv = &B.bounds[(size_t)B.upd_bounds[(size_t)u]];
+                interval_blocks(S, T, U, iv + 1, iv[0], runs, [&](int wr, int wc, int ia, int mi, int ja, int nj) {
+                    B.bigk.push_back(BigKeyed{(launch << 40) | B.big_tile0[t], (domain << 32) | ((int64_t)wc << 16) | wr,
+                                              entry(ia, mi, ja, nj), 1, 1});
+                });
+                continue;
+            }
             if (domain) {
                 // a re-cut domain: a task owns one (row window, column window) of the members' own row order
                 if (U.m / kBigTile >= 0xffff) throw std::runtime_error("schedule: too many windows of one update");
@@ -906,7 +1067,8 @@ void build_big_tasks(Schedule& S, BuildState& B) {
         // (A task of a re-cut domain holds a remainder only beside its full block -- recut_blocks -- so there it rides
         // with the block also in a launch that hands k_chol_dense everything: as an entry of its own it would be
         // multiplied as a whole block and double the task's length.)
-        const bool strips_ride = bigk[i].window != 0 && lmode == 2 && B.knobs.dense_strips;
+        // (An interval domain's task holds one block per member: as a task of the tile cut.)
+        const bool strips_ride = bigk[i].window != 0 && (bigk[i].window >> 32) < kIntervalDomain && lmode == 2 && B.knobs.dense_strips;
         auto dense_here = [&](const WaveEntry& E) {
             if (!is_dense(E, lmode)) return false;
             const int mi = entry_rows(E), nj = entry_cols(E);
@@ -2609,12 +2771,24 @@ int64_t check_schedule(const Schedule& S, std::string& what) {
     // What fixes the order of sums within a launch: no two tasks write the same entry of L.  Tasks of the tile cut own
     // disjoint super-tiles.  Tasks of re-cut conflict domains: per launch and piece every column belongs to at most one
     // domain (the tile cut counts as one), a domain's members all have the same rows, its tasks have pairwise
-    // disjoint windows of that index, and every entry's rows lie in its task's window.
+    // disjoint windows of that index, and every entry's rows lie in its task's window.  Tasks of interval domains (members'
+    // rows differ): pairwise different (row interval, column interval), and over all entries of the domain every panel
+    // position named under interval index i lies below every position named under a larger index -- so the rectangles
+    // interval i x interval j of the piece's panel are disjoint, and an entry's positions lie in its task's.
     std::vector<int32_t> col_domain;                  // of the current (launch, piece): -1 = not named yet
     std::map<int32_t, int64_t> domain_upd;            // ... domain -> its first update seen: the rows every member must have
     std::vector<std::array<int32_t, 3>> domain_wins;  // ... (domain, row0, col0) of its tasks
+    std::map<std::pair<int32_t, int32_t>, std::pair<int32_t, int32_t>> ival_span;   // ... (interval domain, index) -> (lowest, highest) position named
     const Schedule::BigTask* group = nullptr;
     auto close_group = [&]() {
+        int32_t dom = 0, top = -1;
+        for (const auto& kv : ival_span) {
+            if (kv.first.first != dom) dom = kv.first.first, top = -1;
+            if (kv.second.first <= top)
+                fail("intervals " + std::to_string(kv.first.second) + " and below of a conflict domain of piece " + std::to_string(group->sn) + " overlap");
+            top = std::max(top, kv.second.second);
+        }
+        ival_span.clear();
         std::sort(domain_wins.begin(), domain_wins.end());
         if (std::adjacent_find(domain_wins.begin(), domain_wins.end()) != domain_wins.end())
             fail("two BIG tasks of piece " + std::to_string(group->sn) + " own the same window of a conflict domain");
@@ -2662,6 +2836,15 @@ int64_t check_schedule(const Schedule& S, std::string& what) {
                 if (rel_at(E.ia) / win_r != b.row0 / win_r || rel_at(E.ia + mi + ms - 1) / win_r != b.row0 / win_r ||
                     rel_at(E.ja) / win_c != b.col0 / win_c || rel_at(E.ja + nj + ns - 1) / win_c != b.col0 / win_c)
                     fail("BIG entry " + std::to_string(e) + " names rows outside its task's tile");
+            } else if (b.domain >= kIntervalDomain) {
+                // interval cut: the positions it names, filed under its task's row and column interval
+                auto name = [&](int32_t index, int k0, int k1) {
+                    auto& span = ival_span.emplace(std::make_pair(b.domain, index), std::make_pair(INT32_MAX, -1)).first->second;
+                    span.first = std::min(span.first, (int32_t)rel_at(k0));
+                    span.second = std::max(span.second, (int32_t)rel_at(k1 - 1));
+                };
+                name(b.row0 / kBigTile, E.ia, E.ia + mi + ms);
+                name(b.col0 / kBigTile, E.ja, E.ja + nj + ns);
             } else {
                 // re-cut: the rows it names lie in the task's window of the domain's index (a remainder of <= kStripMax
                 // positions at the end of the index may sit in the window before it: recut_blocks) ...

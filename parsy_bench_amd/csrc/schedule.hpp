@@ -101,6 +101,11 @@ constexpr int kStripMax = 16;
 // (schedule.cpp: issued_ns): a k_chol_dense chunk of 8 k, a strip riding with it, a k_chol_big chunk of 16 k = a fixed
 // part + a part per 16 x 16 fragment (1.0 + 2.1 * fragments / 35 us, fitted to one Flan-class launch).
 constexpr int kIssueDenseNs = 2090, kIssueStripNs = 260, kIssueRaggedNs = 1000, kIssueFragmentNs = 60;
+// Workgroup slots a BIG / DENSE launch's tasks are dealt to (2 per compute unit of the 256): a task that issues less than
+// the launch's work / kIssueSlots cannot be what ends the launch (the tail guard of the interval cut).
+constexpr int kIssueSlots = 512;
+// Conflict domains cut in intervals of the target's positions are numbered from here (Schedule::BigTask::domain).
+constexpr int32_t kIntervalDomain = 1 << 30;
 inline int entry_rows(const WaveEntry& E) { return E.mn & 255; }          // rows in the row window
 inline int entry_cols(const WaveEntry& E) { return (E.mn >> 8) & 255; }   // rows in the column window
 inline bool big_ident(const WaveEntry& E) { return (E.mn >> 16) & 1; }
@@ -327,6 +332,10 @@ struct Schedule {
                      // re-cut conflict domain of its piece and launch it belongs to (1 + the domain's first update, counted from
                      // the piece's first): its entries are blocks of the members' own row order, (row0, col0) = kBigTile x its
                      // (row window, column window) of that order -- the kernels read neither.
+                     // From kIntervalDomain on (kIntervalDomain + the same number): a domain whose members' rows differ, cut in
+                     // intervals of the target's panel positions (schedule.cpp: interval_bounds): (row0, col0) = kBigTile x
+                     // its (row interval, column interval), an entry per member that has rows in both, each at most
+                     // kBigTile consecutive rows of the member's own order.
                      int32_t domain; };
     std::vector<BigTask> big_all;         // every task, grouped by (src_level, next)
     std::vector<TileDesc> big_tasks;      // tasks of the launches (active targets): k_chol_big: wp, sp = the ragged part [em, e1) of a
