@@ -344,6 +344,8 @@ static void run_begin(parsy_plan* pl) {
     pl->run_early_seen.assign(pl->ev_early_done.size(), 0);
 }
 
+// (the solve cases of the switch below, run_solve, plan_solve and plan_backsolve choose launch functions by form, gates and
+// right-hand sides: mirrored by predict() of tests/solve_cases.py -- change both)
 static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0, size_t i1, double* L,
                       const double* Lc, double* x, int nrhs, int ldx, hipStream_t stream) {
     size_t& cursor = pl->run_cursor;
@@ -531,10 +533,12 @@ SolveGates read_solve_gates() {
     num("PARSY_BMRHS_MIN", g.bmrhs_min);
     const char* w = std::getenv("PARSY_BMRHS_WIDE_ONLY");
     g.bmrhs_wide_only = !(w && w[0] == '0');
+    num("PARSY_BMRHS_WIDE_BLOCKS", g.bmrhs_wide_blocks);
     num("PARSY_BCHAIN_MIN_BLOCKS", g.bchain_min_blocks);
     num("PARSY_SMALL_MRHS_HALVES_MIN", g.small_halves_min);
     num("PARSY_SUB_MRHS_MIN", g.sub_mrhs_min);
     g.xt_min_set = num("PARSY_XT_MIN", g.xt_min);
+    num("PARSY_CHAIN_FEW_CHUNKS", g.chain_few_chunks);
     const char* st = std::getenv("PARSY_DEBUG_SOLVE_STALL");
     g.wait_bias = (st && st[0] == '1') ? (1 << 20) : 0;
     num("PARSY_SUB_ABL", g.sub_abl);

@@ -15,16 +15,22 @@ constexpr int kPassLanes = 8;    // passes over the right-hand sides of a solve 
 // values; the variables (diagnostics, tests: every variant can be forced) are read ONCE at the start of every forward /
 // backward solve call (read_solve_gates, into the plan's DevicePattern, where the launch functions take them from) -- not
 // per process, so a test can change them between solves, and not per launch (a solve makes hundreds of launches).
+// tests/solve_cases.py (predict, GATE_DEFAULTS) mirrors these defaults and the choices the executor and the launch
+// functions make with them, to pin the solve catalogue to its kernels without a GPU: a change here, in run_range /
+// plan_solve / plan_backsolve (executor.hip) or in a launch function of the trsv sources is made there too.  The GPU
+// tier compares that copy with the kernel witness, cell by cell.
 struct SolveGates {
     int mrhs_min = 6;             // PARSY_MRHS_MIN=k (this: k, the next: min(k, 2)): narrow supernodes take k_solve_small_mrhs from here on
     int chain_mrhs_min = 2;       // ... the wide supernodes' chain k_solve_blocks_mrhs (armed hand-off buffer)
     int bmrhs_min = 16;           // PARSY_BMRHS_MIN: the backward solve's many-right-hand-side kernels
     bool bmrhs_wide_only = true;  // PARSY_BMRHS_WIDE_ONLY=0: k_bsolve_block_mrhs on launches of few blocks too
+    int bmrhs_wide_blocks = 128;  // PARSY_BMRHS_WIDE_BLOCKS: launches of at least this many blocks take k_bsolve_block_mrhs<4> (64 right-hand sides per pass)
     int bchain_min_blocks = 128;  // PARSY_BCHAIN_MIN_BLOCKS: chain launches take k_bsolve_chain_mrhs from this many block columns on
     int small_halves_min = 512;   // PARSY_SMALL_MRHS_HALVES_MIN: k_solve_small_mrhs<64> sweeps in halves from this many supernodes on
     int sub_mrhs_min = 6;         // PARSY_SUB_MRHS_MIN: the subtree launches take the many-right-hand-side form (0: never)
     int xt_min = 16;              // PARSY_XT_MIN: forward solves of this many right-hand sides work on X row-major (0: never)
     bool xt_min_set = false;      // ... set: whatever the factor's density
+    int chain_few_chunks = 384;   // PARSY_CHAIN_FEW_CHUNKS: one right-hand side, forward chain launches of more chunks take k_solve_chain_w<4>, the others <2>
     int wait_bias = 0;            // PARSY_DEBUG_SOLVE_STALL=1: 1 << 20, no hand-off wait of the solve is ever satisfied
     int sub_abl = 0;              // PARSY_SUB_ABL: ablation mask of the subtree kernels (diagnostic build, trsv_sub_kernels.hip)
 };

@@ -1486,10 +1486,11 @@ void launch_bsolve_chain_w(const DevicePattern& P, int first, int count, const d
         P.bsolve_pairs + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias, P.bpart);
 }
 
-static constexpr int kMrhsWideBlocks = 128;   // backward launches of at least this many blocks take 64 right-hand sides per pass
+// (backward launches of at least SolveGates::bmrhs_wide_blocks blocks, 128, take 64 right-hand sides per pass)
 // form: Launch::form -- kFormEach: one workgroup per block, kFormChain: chain launch (tickets), kFormSubtrees: subtree launch
 // (`first` counts (begin, end) pairs of bsolve_ranges, which index the whole block list); width_class: Launch::width_class
 // (0 | 1: kTinyWidth | 2: kTinyWidth2)
+// (the order of the choices below is mirrored by predict() of tests/solve_cases.py -- change both)
 void launch_bsolve_block(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
                          double* x, double* xscratch, int nrhs, int ldx, LaunchForm form, int width_class, int ticket,
                          int wait_bias, hipStream_t stream) {
@@ -1528,10 +1529,10 @@ void launch_bsolve_block(const DevicePattern& P, int first, int count, const dou
             pds, P.rows, L, x, xscratch, nrhs, ldx, P.sinfo, P.stickets + ticket, wait_bias, count, dinv);
         return;
     }
-    if (nrhs >= G.bmrhs_min && (!G.bmrhs_wide_only || count >= kMrhsWideBlocks)) {   // 64 right-hand sides per pass over L, products on the matrix cores
+    if (nrhs >= G.bmrhs_min && (!G.bmrhs_wide_only || count >= G.bmrhs_wide_blocks)) {   // 64 right-hand sides per pass over L, products on the matrix cores
         // launches of few blocks (the top of the tree, small inputs) take 16 right-hand sides per pass in up to 8
         // workgroups per block side by side; the others 64 per pass (L read once per 64)
-        const bool wide = count >= kMrhsWideBlocks && nrhs > 16;
+        const bool wide = count >= G.bmrhs_wide_blocks && nrhs > 16;
         const int per = wide ? kRhsM : 16;
         const int mlanes = std::min(kPassLanes, (nrhs + per - 1) / per);
         const dim3 mgrid = chain ? dim3(count * mlanes) : dim3(count, mlanes);

@@ -490,6 +490,7 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
   }
 }
 
+// (which kernel by width, right-hand sides and count: mirrored by predict() of tests/solve_cases.py -- change both)
 void launch_solve_small(const DevicePattern& P, int first, int count, int wmax, bool subtrees, const double* L,
                         double* x, int nrhs, int ldx, int ldq, hipStream_t stream) {
     if (count <= 0) return;
@@ -625,7 +626,7 @@ void launch_solve_panel(const DevicePattern& P, int first, int count, const doub
 // Arithmetic never produces the armed pattern (results of operations on NaNs are quiet NaNs); should the data
 // hold it, the wait times out and the solve's status word reports it, like any other abandoned hand-off.
 // Rows below the supernode's own columns are scattered at the end with atomics, as in the other kernels.
-static constexpr int kChainFewChunks = 384;                  // launches of at most this many chunks: top of the tree
+// (launches of at most SolveGates::chain_few_chunks chunks, 384: the top of the tree)
 
 // RB = 64-row blocks per workgroup (8 / RB waves share each of them): 4 where a launch has plenty of chunks, 2
 // where it is the top of the tree -- few, very wide supernodes: twice the workgroups (a CU sustains about
@@ -1317,6 +1318,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
 }
 #undef TSF
 
+// (narrow up to 16 right-hand sides: mirrored by predict() of tests/solve_cases.py -- change both)
 void launch_solve_blocks_mrhs(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
                               double* x, double* xscratch, int nrhs, int ldx, int ldq, int ticket, int wait_bias,
                               hipStream_t stream) {
@@ -1381,10 +1383,11 @@ void launch_solve_arm_wide(const DevicePattern& P, int npairs, double* xscratch,
 }
 
 // One right-hand side: xscratch was armed by the caller (solve_arm_handoff)
+// (<2> up to P.gates.chain_few_chunks chunks, else <4>: mirrored by predict() of tests/solve_cases.py -- change both)
 void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv, double* x,
                         double* xscratch, int ticket, int wait_bias, hipStream_t stream) {
     if (count <= 0) return;
-    if (count <= kChainFewChunks) {
+    if (count <= P.gates.chain_few_chunks) {
         launch_witnessed<k_solve_chain_w<2>, kWSolveChainW2>(dim3(2 * count), dim3(kChainThreads), 0, stream, P.sn,
             P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias);
     } else {

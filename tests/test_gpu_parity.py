@@ -1501,6 +1501,7 @@ def test_one_rhs_under_mrhs_min_1(api, oracle, monkeypatch, name):
 # cells launch every entry of the witness table but _NOT_COVERED.
 _COVERAGE = [
     ("lap30", {"PARSY_SOLVE_ONE": "0"}, 1, True, ["k_solve_tiny<16>", "k_solve_small", "k_solve_chain_w<2>", "k_diag_inverse"]),
+    ("lap30", {"PARSY_SOLVE_ONE": "0", "PARSY_CHAIN_FEW_CHUNKS": "0"}, 1, True, ["k_solve_chain_w<4>"]),
     ("lap30", {"PARSY_SOLVE_ONE": "0"}, 1, False, ["k_bsolve_chain_w", "k_bsolve_below", "k_bsolve_block<1>", "k_bsolve_tiny<16>"]),
     ("lap30", {"PARSY_SOLVE_ONE": "0"}, 8, True, ["k_solve_small_mrhs<16>", "k_solve_small_mrhs<64,true>",
                                                    "k_solve_blocks_mrhs<true>", "k_solve_arm_wide"]),
@@ -1524,7 +1525,6 @@ _COVERAGE = [
     ("nd24k", {"PARSY_SOLVE_ONE": "0", "PARSY_SUB_MRHS_MIN": "0"}, 19, False, ["k_bsolve_block_mrhs<4>"]),
 ]
 _NOT_COVERED = {
-    "k_solve_chain_w<4>": "one right-hand side through a forward chain launch of more than 384 chunks: Flan-class plans only",
     "k_copy_segments": "the multi-device exchange's copy, not a solve: bitwise in test_copy_segments_device_packs_and_unpacks",
 }
 _PLAN_VARIABLES = ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED")   # (read when the plan is made; the others per solve)
@@ -1539,7 +1539,8 @@ def test_coverage_matrix_reaches_every_solve_kernel(api, oracle, monkeypatch):
     plans = {}
     for name, env, nrhs, fwd, want in _COVERAGE:
         for k in ("PARSY_SOLVE_ONE", "PARSY_FORCE_UNFUSED", "PARSY_XT_MIN", "PARSY_BCHAIN_MIN_BLOCKS", "PARSY_BMRHS_WIDE_ONLY",
-                  "PARSY_SMALL_MRHS_HALVES_MIN", "PARSY_MRHS_MIN", "PARSY_SUB_MRHS_MIN"):
+                  "PARSY_SMALL_MRHS_HALVES_MIN", "PARSY_MRHS_MIN", "PARSY_SUB_MRHS_MIN", "PARSY_CHAIN_FEW_CHUNKS",
+                  "PARSY_BMRHS_WIDE_BLOCKS"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
