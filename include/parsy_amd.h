@@ -661,6 +661,100 @@ typedef struct parsy_rowmod_info {
 } parsy_rowmod_info;
 int parsy_rowmod_get_info(parsy_plan* plan, parsy_rowmod_info* info);          /* host-only plans too */
 
+/* ---- Normal matrices: N = F diag(w) F' + beta I + A0 on the plan's pattern, and least squares through its factor -----
+ * F is a sparse n x m matrix in compressed columns: Fp (m + 1 entries) and Fi (row indices, strictly ascending within a
+ * column, in the caller's ordering) on the host; the values fx (nnzF doubles, in that order; positions count from
+ * Fp[0]) and the weights w (m doubles, any finite values; NULL: all ones) on the device.  F's rows go through the
+ * plan's ordering (parsy_plan_set_perm) like every vector of the refinement calls.  A0 is optional: nnzA doubles in A2
+ * order, or NULL.
+ * THE PATTERN OF A DOES NOT CHANGE: every pair of rows that share a column of F, and every row of F on the diagonal,
+ * must be a stored entry of the plan's pattern of A (parsy_plan_pattern).  An F that breaks the rule is refused on the
+ * host, when the handle is made; the message names the column of F and the two rows in both orderings.  Entries of the
+ * pattern that F does not produce get 0 (+ beta on the diagonal) (+ A0).
+ *
+ * parsy_normal_pattern: the lower triangle of the pattern of F F' with a full diagonal as sorted CSC (Ap: n + 1 ints;
+ * Ai == NULL: only Ap and the count) -- what to hand to parsy_order_nd and parsy_analyze, with any values, for a plan
+ * that satisfies the rule.  Returns the entry count, or -1. */
+int64_t parsy_normal_pattern(int n, int m, const int* Fp, const int* Fi, int* Ap, int* Ai);
+/* A handle belongs to one plan and one pattern of F; several handles per plan are allowed, host-only plans (device < 0)
+ * too: only the device calls refuse those.  The handle copies the plan's ordering as it stands: a later
+ * parsy_plan_set_perm does not move it.  The plan is borrowed and must outlive the handle's calls.
+ * The inspector runs here, once: per A2 entry q = (i, j) the list of triples (a, b, k) -- column k of F holds both rows,
+ * a is the position in fx of the entry on row i, b the one on row j (i >= j in the factor's ordering, a == b on the
+ * diagonal) -- ascending in k, which is the summation order; lists of more than 512 triples are cut into chunks of 512
+ * (the last one shorter), the others binned by length into three classes (1, 8, 64 lanes per entry) whose borders are
+ * constants; and the transposed index of F (row -> its positions in fx and their columns, ascending).
+ * Refused, with parsy_last_error naming the reason and nothing allocated (NULL is returned): a NULL argument, m < 0, a
+ * row outside 0 .. n - 1, indices unsorted or repeated within a column, Fp decreasing, more than 2^31 - 1 chunks (nnzF
+ * is bounded by Fp's type), a plan built from L's pattern alone, the pattern rule. */
+typedef struct parsy_normal parsy_normal;
+parsy_normal* parsy_normal_create(parsy_plan* plan, int m, const int* Fp, const int* Fi);
+void parsy_normal_destroy(parsy_normal* nrm);
+typedef struct parsy_normal_info {
+    int32_t n, m, nnzF;
+    int32_t longest_list;        /* triples of the longest list */
+    int32_t chunked_entries;     /* entries whose list is cut into chunks */
+    int32_t chunks;              /* their chunks */
+    int32_t border[3];           /* longest list of the 1-, 8- and 64-lane class (constants: 8, 64, 512) */
+    int32_t launches;            /* kernels of one values call: one per non-empty class, two for the chunks */
+    int64_t class_entries[3];    /* entries of each class */
+    int64_t pairs;               /* triples in all = sum over the columns of F of c (c + 1) / 2 */
+    int64_t entries_untouched;   /* entries of A's pattern that F does not produce */
+    int64_t device_bytes;        /* index and workspace held by the handle (0 before its first device call); not part
+                                    of the plan's figure */
+} parsy_normal_info;
+int parsy_normal_get_info(const parsy_normal* nrm, parsy_normal_info* info);
+/* List q (0 <= q < nnzA): a, b, k (each may be NULL) hold up to longest_list entries.  Returns the length, or -1. */
+int64_t parsy_normal_pairs(const parsy_normal* nrm, int64_t q, int32_t* a, int32_t* b, int32_t* k);
+/* Violations of the index (0: sound): every pair of every column appears exactly once, every list ascends in k, the
+ * chunks tile their lists, every entry is in the class of its length, every position of the row index holds its row. */
+long long parsy_normal_check(const parsy_normal* nrm);
+
+/* d_values[q] = ((s_q + beta on the diagonal) + d_base[q]) for EVERY entry q of A's pattern (no zero-fill needed), with
+ * s_q = sum over list q of (fx[a] w[k]) fx[b] by fma in the fixed order above (w == NULL: fx[a] fx[b], the same bits as
+ * w = 1).  d_base may be NULL and may be d_values itself.  One launch per non-empty class and two for the chunks,
+ * ordered by the stream alone; no float atomics: two calls give the same bits, on any device.  The first device call of
+ * a handle uploads its index (12 bytes per triple and the rest). */
+int parsy_normal_values_device(parsy_normal* nrm, const double* d_fx, const double* d_w, double beta,
+                               const double* d_base, double* d_values, void* stream);
+/* Y = beta Y + alpha op(X):  PARSY_NORMAL_F   Y (n x nrhs) = beta Y + alpha F (diag(w) X),  X m x nrhs;
+ *                            PARSY_NORMAL_FT  Y (m x nrhs) = beta Y + alpha F' X,           X n x nrhs (d_w is not read).
+ * Column-major with leading dimensions, the n-side in the caller's ordering.  The right-hand sides go in blocks of 8;
+ * column q of a call with nrhs columns is bitwise what a call with that column alone gives.  beta == 0: Y is not read.
+ * Refused: a NULL argument (d_w may be NULL), another op, nrhs < 1, a leading dimension below the rows of its operand,
+ * d_x == d_y, a host-only plan. */
+#define PARSY_NORMAL_F 0
+#define PARSY_NORMAL_FT 1
+int parsy_normal_apply_device(parsy_normal* nrm, int op, const double* d_fx, const double* d_w, const double* d_x, int ldx,
+                              int nrhs, double alpha, double beta, double* d_y, int ldy, void* stream);
+/* Least squares: X (n x nrhs) minimises sum_k w_k (f_k' x - c_k)^2 + beta ||x||^2 for every column of C (m x nrhs), by
+ * the corrected normal equations.  S is the plan's forward + backward solve with d_lValues in the handle's ordering,
+ * exactly as parsy_solve_spd_device with max_steps = 0 runs it:
+ *     x = S F W c;   `steps` times (steps >= 0):  r = c - F' x,  g = F W r - beta x,  x += S g;
+ * and at the end r and g are formed once more from the returned x -- the residual (d_r, m x nrhs) and the gradient
+ * (d_g, n x nrhs) at the answer; each may be NULL, with both NULL the last pass is skipped.  Everything is enqueued with
+ * no host wait; read parsy_solve_status after synchronising (a solve of the call whose hand-off wait timed out shows
+ * there).  There is no convergence test.
+ * STALE FACTOR: the operator of every correction is (L L')^-1, the inverse of the matrix that was FACTORED; r and g come
+ * from fx, w and beta as given.  So d_lValues may be the factor of N at nearby weights or beta: the loop is then
+ * iterative refinement of the normal equations through it, and x converges to the minimiser of the problem as GIVEN as
+ * far as (L L')^-1 stands for N^-1; the factor only sets the number of steps.
+ * The workspace (n x nrhs + m x nrhs doubles) is the handle's, grown on demand, counted in its device_bytes.
+ * Refused, with the outputs untouched: what parsy_residual_device refuses; steps < 0, nrhs < 1; ldc < m, ldx < n,
+ * ldr < m, ldg < n; d_x == d_c. */
+int parsy_lsq_solve_device(parsy_normal* nrm, const double* d_fx, const double* d_w, double beta, const double* d_lValues,
+                           const double* d_c, int ldc, double* d_x, int ldx, int nrhs, int steps, double* d_r, int ldr,
+                           double* d_g, int ldg, void* stream);
+/* Host buffers: H2D, the call above, D2H; seconds (may be NULL) = device time.  Synchronous.  (lsq: x stays untouched
+ * when a solve's status is bad.) */
+int parsy_normal_values_host(parsy_normal* nrm, const double* fx, const double* w, double beta, const double* base,
+                             double* values, double* seconds);
+int parsy_normal_apply_host(parsy_normal* nrm, int op, const double* fx, const double* w, const double* x, int ldx, int nrhs,
+                            double alpha, double beta, double* y, int ldy, double* seconds);
+int parsy_lsq_solve_host(parsy_normal* nrm, const double* fx, const double* w, double beta, const double* lValues,
+                         const double* c, int ldc, double* x, int ldx, int nrhs, int steps, double* r, int ldr, double* g,
+                         int ldg, double* seconds);
+
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */
 int parsy_factor_host(parsy_plan* plan, const double* values, double* lValues, double* seconds);

@@ -98,7 +98,24 @@ EXPORTED_SYMBOLS = [
     "parsy_factor_rowdel_device", "parsy_factor_rowadd_device", "parsy_factor_rowdel_host", "parsy_factor_rowadd_host",
     "parsy_rowmod_status", "parsy_rowmod_reach", "parsy_rowmod_get_info",
     "parsy_eigs_get_info", "parsy_eigs_device", "parsy_eigs_host",
+    "parsy_normal_pattern", "parsy_normal_create", "parsy_normal_destroy", "parsy_normal_get_info", "parsy_normal_pairs",
+    "parsy_normal_check", "parsy_normal_values_device", "parsy_normal_apply_device", "parsy_lsq_solve_device",
+    "parsy_normal_values_host", "parsy_normal_apply_host", "parsy_lsq_solve_host",
 ]
+
+
+class NormalInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("nnzF", C.c_int32), ("longest_list", C.c_int32),
+        ("chunked_entries", C.c_int32), ("chunks", C.c_int32), ("border", C.c_int32 * 3), ("launches", C.c_int32),
+        ("class_entries", C.c_int64 * 3), ("pairs", C.c_int64), ("entries_untouched", C.c_int64),
+        ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["border"], d["class_entries"] = list(self.border), list(self.class_entries)
+        return d
 
 
 class ApplyInfo(C.Structure):
@@ -294,6 +311,25 @@ def _declare(lib):
     eigs = [vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     lib.parsy_eigs_device.argtypes = eigs
     lib.parsy_eigs_host.argtypes = eigs
+    lib.parsy_normal_pattern.restype = C.c_int64
+    lib.parsy_normal_pattern.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.parsy_normal_create.restype = vp
+    lib.parsy_normal_create.argtypes = [vp, C.c_int, vp, vp]
+    lib.parsy_normal_destroy.restype = None
+    lib.parsy_normal_destroy.argtypes = [vp]
+    lib.parsy_normal_get_info.argtypes = [vp, vp]
+    lib.parsy_normal_pairs.restype = C.c_int64
+    lib.parsy_normal_pairs.argtypes = [vp, C.c_int64, vp, vp, vp]
+    lib.parsy_normal_check.restype = C.c_longlong
+    lib.parsy_normal_check.argtypes = [vp]
+    lib.parsy_normal_values_device.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp]
+    lib.parsy_normal_values_host.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp]
+    nap = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp]
+    lib.parsy_normal_apply_device.argtypes = nap
+    lib.parsy_normal_apply_host.argtypes = nap
+    lsq = [vp, vp, vp, C.c_double, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]
+    lib.parsy_lsq_solve_device.argtypes = lsq
+    lib.parsy_lsq_solve_host.argtypes = lsq
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

@@ -811,6 +811,187 @@ class Plan:
 
 
 # ---------------------------------------------------------------------------
+# normal matrices on the plan's pattern: N = F diag(w) F' + beta I + A0, least squares through its factor
+# ---------------------------------------------------------------------------
+class NormalEquations:
+    """One plan and one pattern of F (parsy_normal).  F: a (Fp, Fi, Fx) triple or anything with .indptr / .indices /
+    .data in compressed columns (n x m, rows ascending within a column, in the caller's ordering).  The handle keeps
+    the plan's ordering as it stands; a plan whose ordering was never set takes sym.Perm first, as solve_refined
+    does.  Every pair of rows that share a column of F must be a stored entry of the plan's pattern of A: an F that
+    breaks the rule is refused here (RuntimeError).  Host-only plans (device < 0) too: info, pairs, check."""
+
+    OPS = {"F": 0, "FT": 1}
+
+    def __init__(self, plan: "Plan", F):
+        Fp, Fi, Fx = self._csc(F)
+        if not getattr(plan, "_perm_set", False):
+            plan.set_perm(plan.sym.Perm)
+            plan._perm_set = True
+        self.plan = plan
+        self.n = int(plan.sym.n)
+        self.m = int(Fp.size) - 1
+        self.Fp, self.Fi = Fp, Fi
+        self.fx = Fx
+        self._h = N.lib().parsy_normal_create(plan._h, self.m, N.ptr(Fp), N.ptr(Fi))
+        if not self._h:
+            raise RuntimeError("parsy_normal_create failed: " + N.last_error())
+
+    @staticmethod
+    def _csc(F):
+        if isinstance(F, tuple):
+            Fp, Fi, Fx = F
+        else:
+            Fp, Fi, Fx = F.indptr, F.indices, F.data
+        return _i32(Fp), _i32(Fi), (None if Fx is None else _f64(Fx))
+
+    @staticmethod
+    def pattern(n: int, F):
+        """(Ap, Ai): the lower triangle of the pattern of F F' with a full diagonal, sorted CSC -- what to order and
+        analyse (with any values) for a plan that satisfies the pattern rule."""
+        Fp, Fi, _ = NormalEquations._csc(F)
+        Ap = np.zeros(n + 1, dtype=np.int32)
+        nnz = N.lib().parsy_normal_pattern(n, Fp.size - 1, N.ptr(Fp), N.ptr(Fi), N.ptr(Ap), None)
+        if nnz < 0:
+            raise RuntimeError("parsy_normal_pattern failed: " + N.last_error())
+        Ai = np.zeros(max(int(nnz), 1), dtype=np.int32)
+        N.lib().parsy_normal_pattern(n, Fp.size - 1, N.ptr(Fp), N.ptr(Fi), N.ptr(Ap), N.ptr(Ai))
+        return Ap, Ai[:nnz]
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            N.lib().parsy_normal_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def info(self) -> dict:
+        """n, m, nnzF, pairs, longest_list, chunked_entries, chunks, border (longest list of the 1-, 8- and 64-lane
+        class), class_entries, entries_untouched, launches (per values call), device_bytes."""
+        ni = N.NormalInfo()
+        if N.lib().parsy_normal_get_info(self._h, C.byref(ni)) != 0:
+            raise RuntimeError("parsy_normal_get_info failed: " + N.last_error())
+        return ni.as_dict()
+
+    def pairs(self, q: int):
+        """(a, b, k) of A2 entry q: positions in fx of the entries on its row and its column (factor's ordering), and
+        their column of F, ascending in k: the summation order."""
+        cap = max(int(self.info["longest_list"]), 1)
+        a, b, k = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        cnt = N.lib().parsy_normal_pairs(self._h, int(q), N.ptr(a), N.ptr(b), N.ptr(k))
+        if cnt < 0:
+            raise RuntimeError("parsy_normal_pairs failed: " + N.last_error())
+        return a[:cnt].copy(), b[:cnt].copy(), k[:cnt].copy()
+
+    def check(self) -> int:
+        return int(N.lib().parsy_normal_check(self._h))
+
+    def _fx(self, fx):
+        fx = self.fx if fx is None else _f64(fx)
+        if fx is None or fx.size != self.Fi.size:
+            raise ValueError(f"fx must hold nnzF = {self.Fi.size} values")
+        return fx
+
+    def _w(self, w):
+        if w is None:
+            return None
+        w = _f64(w)
+        if w.size != self.m:
+            raise ValueError(f"w must hold m = {self.m} weights")
+        return w
+
+    def values_device(self, d_fx: int, d_values: int, d_w: int = 0, beta: float = 0.0, d_base: int = 0,
+                      stream: int = 0) -> None:
+        """d_values (nnzA doubles, A2 order) = F diag(w) F' + beta I + base on the plan's pattern; d_w / d_base: 0 for
+        none; d_base may be d_values."""
+        if N.lib().parsy_normal_values_device(self._h, d_fx or None, d_w or None, beta, d_base or None, d_values or None,
+                                              stream) != 0:
+            raise RuntimeError("parsy_normal_values_device failed: " + N.last_error())
+
+    def values(self, fx=None, w=None, beta: float = 0.0, base=None):
+        """Host arrays: (values in A2 order, device_seconds)."""
+        fx, w = self._fx(fx), self._w(w)
+        base = None if base is None else _f64(base)
+        nnz = int(self.plan.info["nnzA"])
+        if base is not None and base.size != nnz:
+            raise ValueError(f"base must hold nnzA = {nnz} values")
+        out = np.zeros(nnz, dtype=np.float64)
+        sec = C.c_double(0)
+        if N.lib().parsy_normal_values_host(self._h, N.ptr(fx), N.ptr(w), beta, N.ptr(base), N.ptr(out), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_normal_values_host failed: " + N.last_error())
+        return out, sec.value
+
+    def apply_device(self, op, d_fx: int, d_x: int, ldx: int, nrhs: int, d_y: int, ldy: int, d_w: int = 0,
+                     alpha: float = 1.0, beta: float = 0.0, stream: int = 0) -> None:
+        """Y = beta Y + alpha op(X): "F" (Y n x nrhs = F diag(w) X) or "FT" (Y m x nrhs = F' X); column-major device
+        arrays, the n-side in the caller's ordering."""
+        op = self.OPS[op] if isinstance(op, str) else int(op)
+        if N.lib().parsy_normal_apply_device(self._h, op, d_fx or None, d_w or None, d_x or None, ldx, nrhs, alpha, beta,
+                                             d_y or None, ldy, stream) != 0:
+            raise RuntimeError("parsy_normal_apply_device failed: " + N.last_error())
+
+    def apply(self, op, x, fx=None, w=None, alpha: float = 1.0, y=None, beta: float = 0.0):
+        """Host arrays (rows,) or (rows, nrhs) in: (beta y + alpha op(x), device_seconds); y is not changed."""
+        opi = self.OPS[op] if isinstance(op, str) else int(op)
+        nx, ny = (self.m, self.n) if opi == 0 else (self.n, self.m)
+        fx, w = self._fx(fx), self._w(w)
+        x = np.asarray(x, dtype=np.float64)
+        one = x.ndim == 1
+        X = np.asfortranarray(x.reshape(nx, -1))
+        nrhs = X.shape[1]
+        if y is None:
+            if beta != 0.0:
+                raise ValueError("apply: beta != 0 needs y")
+            Y = np.zeros((ny, nrhs), order="F")
+        else:
+            Y = np.array(np.asarray(y, dtype=np.float64).reshape(ny, -1), order="F", copy=True)
+            if Y.shape[1] != nrhs:
+                raise ValueError(f"apply: x has {nrhs} columns, y has {Y.shape[1]}")
+        sec = C.c_double(0)
+        if N.lib().parsy_normal_apply_host(self._h, opi, N.ptr(fx), N.ptr(w), X.ctypes.data_as(C.c_void_p), max(nx, 1), nrhs,
+                                           alpha, beta, Y.ctypes.data_as(C.c_void_p), max(ny, 1), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_normal_apply_host failed: " + N.last_error())
+        return (Y[:, 0].copy() if one else np.ascontiguousarray(Y)), sec.value
+
+    def lstsq_device(self, d_fx: int, d_lValues: int, d_c: int, ldc: int, d_x: int, ldx: int, nrhs: int, steps: int = 1,
+                     d_w: int = 0, beta: float = 0.0, d_r: int = 0, ldr: int = 0, d_g: int = 0, ldg: int = 0,
+                     stream: int = 0) -> None:
+        """x = S F W c and `steps` corrections x += S (F W (c - F' x) - beta x) through d_lValues (it may be a stale
+        factor); d_r / d_g (0: none) receive the residual and the gradient at the returned x.  Nothing waits: check
+        plan.solve_status() after synchronising."""
+        if N.lib().parsy_lsq_solve_device(self._h, d_fx or None, d_w or None, beta, d_lValues or None, d_c or None, ldc,
+                                          d_x or None, ldx, nrhs, steps, d_r or None, ldr, d_g or None, ldg, stream) != 0:
+            raise RuntimeError("parsy_lsq_solve_device failed: " + N.last_error())
+
+    def lstsq(self, lValues, c, w=None, beta: float = 0.0, steps: int = 1, fx=None):
+        """Host arrays: (x, r, g) minimising sum_k w_k (f_k' x - c_k)^2 + beta ||x||^2 for c (m,) or (m, nrhs); r = c - F' x
+        and g = F W r - beta x at the returned x."""
+        fx, w = self._fx(fx), self._w(w)
+        c = np.asarray(c, dtype=np.float64)
+        one = c.ndim == 1
+        Cm = np.asfortranarray(c.reshape(self.m, -1))
+        nrhs = Cm.shape[1]
+        X = np.zeros((self.n, nrhs), order="F")
+        R = np.zeros((self.m, nrhs), order="F")
+        G = np.zeros((self.n, nrhs), order="F")
+        lv = _f64(lValues)
+        sec = C.c_double(0)
+        vp = C.c_void_p
+        if N.lib().parsy_lsq_solve_host(self._h, N.ptr(fx), N.ptr(w), beta, N.ptr(lv), Cm.ctypes.data_as(vp), max(self.m, 1),
+                                        X.ctypes.data_as(vp), max(self.n, 1), nrhs, steps, R.ctypes.data_as(vp),
+                                        max(self.m, 1), G.ctypes.data_as(vp), max(self.n, 1), C.byref(sec)) != 0:
+            raise RuntimeError("parsy_lsq_solve_host failed: " + N.last_error())
+        self.last_seconds = sec.value
+        if one:
+            return X[:, 0].copy(), R[:, 0].copy(), G[:, 0].copy()
+        return np.ascontiguousarray(X), np.ascontiguousarray(R), np.ascontiguousarray(G)
+
+
+# ---------------------------------------------------------------------------
 # distribution of one factorization over the devices of a node
 # ---------------------------------------------------------------------------
 class Dist:

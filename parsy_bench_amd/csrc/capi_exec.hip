@@ -921,6 +921,95 @@ int parsy_rowmod_get_info(parsy_plan* pl, parsy_rowmod_info* info) {
     return 0;
 }
 
+parsy_normal* parsy_normal_create(parsy_plan* pl, int m, const int* Fp, const int* Fi) {
+    const char* who = "parsy_normal_create";
+    if (!pl || !Fp) {
+        set_last_error(std::string(who) + ": null argument");
+        return nullptr;
+    }
+    if (pl->solve_only) {
+        set_last_error(std::string(who) + ": plan was built from L's pattern only (no A pattern)");
+        return nullptr;
+    }
+    parsy::NormalIndex I;
+    if (parsy::normal_build(pl->S, pl->perm, m, Fp, Fi, I) != 0) return nullptr;
+    parsy_normal* h = new parsy_normal();
+    h->plan = pl;
+    h->device = pl->device;
+    h->I = std::move(I);
+    return h;
+}
+
+void parsy_normal_destroy(parsy_normal* h) {
+    if (!h) return;
+    if (h->dev.on_device || h->dev.ws.data()) {
+        (void)hipSetDevice(h->device);
+        (void)hipDeviceSynchronize();   // (a call may still read the index)
+    }
+    delete h;
+}
+
+int parsy_normal_get_info(const parsy_normal* h, parsy_normal_info* info) {
+    if (!h || !info) {
+        set_last_error("parsy_normal_get_info: null argument");
+        return -1;
+    }
+    const parsy::NormalIndex& I = h->I;
+    info->n = I.n, info->m = I.m, info->nnzF = I.nnzF();
+    info->longest_list = I.longest_list;
+    info->chunked_entries = (int32_t)I.fold_q.size();
+    info->chunks = (int32_t)I.chunks();
+    info->launches = I.chunks() > 0 ? 2 : 0;
+    for (int c = 0; c < parsy::kNormalClasses; ++c) {
+        info->border[c] = parsy::kNormalBorder[c];
+        info->class_entries[c] = (int64_t)I.cls[c].size();
+        info->launches += !I.cls[c].empty();
+    }
+    info->pairs = I.pairs;
+    info->entries_untouched = I.entries_untouched;
+    info->device_bytes = h->dev.meter.bytes;
+    return 0;
+}
+
+int64_t parsy_normal_pairs(const parsy_normal* h, int64_t q, int32_t* a, int32_t* b, int32_t* k) {
+    if (!h || q < 0 || q >= h->I.nnzA) {
+        set_last_error("parsy_normal_pairs: null handle or q outside 0 .. nnzA - 1");
+        return -1;
+    }
+    const parsy::NormalIndex& I = h->I;
+    const int64_t t0 = I.lptr[(size_t)q], len = I.lptr[(size_t)q + 1] - t0;
+    for (int64_t t = 0; t < len; ++t) {
+        if (a) a[t] = I.ta[(size_t)(t0 + t)];
+        if (b) b[t] = I.tb[(size_t)(t0 + t)];
+        if (k) k[t] = I.tk[(size_t)(t0 + t)];
+    }
+    return len;
+}
+
+long long parsy_normal_check(const parsy_normal* h) {
+    if (!h) {
+        set_last_error("parsy_normal_check: null handle");
+        return -1;
+    }
+    return parsy::normal_check(h->I);
+}
+
+int parsy_normal_values_device(parsy_normal* h, const double* d_fx, const double* d_w, double beta, const double* d_base,
+                               double* d_values, void* stream) {
+    return parsy::normal_values(h, d_fx, d_w, beta, d_base, d_values, stream);
+}
+
+int parsy_normal_apply_device(parsy_normal* h, int op, const double* d_fx, const double* d_w, const double* d_x, int ldx,
+                              int nrhs, double alpha, double beta, double* d_y, int ldy, void* stream) {
+    return parsy::normal_apply(h, op, d_fx, d_w, d_x, ldx, nrhs, alpha, beta, d_y, ldy, stream);
+}
+
+int parsy_lsq_solve_device(parsy_normal* h, const double* d_fx, const double* d_w, double beta, const double* d_lValues,
+                           const double* d_c, int ldc, double* d_x, int ldx, int nrhs, int steps, double* d_r, int ldr,
+                           double* d_g, int ldg, void* stream) {
+    return parsy::normal_lsq(h, d_fx, d_w, beta, d_lValues, d_c, ldc, d_x, ldx, nrhs, steps, d_r, ldr, d_g, ldg, stream);
+}
+
 void parsy_dropin_reset(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_plans) parsy::plan_free(kv.second);

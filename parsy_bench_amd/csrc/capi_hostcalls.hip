@@ -606,4 +606,92 @@ int parsy_factor_rowadd_host(parsy_plan* pl, double* lValues, int row, int nz, c
     return 0;
 }
 
+// The normal-matrix calls stage in buffers of their own, freed on return; operands go to the device with the leading
+// dimension of their row count.
+int parsy_normal_values_host(parsy_normal* h, const double* fx, const double* w, double beta, const double* base,
+                             double* values, double* seconds) {
+    const char* who = "parsy_normal_values_host";
+    if (parsy::normal_check_values_args(h, who, fx, values) != 0) return -1;
+    PARSY_HIP(hipSetDevice(h->plan->device));
+    Scratch sc;
+    const int64_t nnz = h->I.nnzA;
+    double* d_fx = sc.upload(fx, h->I.nnzF(), true);
+    double* d_w = w ? sc.upload(w, h->I.m, true) : nullptr;
+    double* d_v = sc.upload(base, nnz, base != nullptr);   // (in place: A0 and the result share the array)
+    if (!d_fx || (w && !d_w) || !d_v || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_normal_values_device(h, d_fx, d_w, beta, base ? d_v : nullptr, d_v, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds) || (nnz > 0 && hipMemcpy(values, d_v, (size_t)nnz * 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_last_error(std::string(who) + ": download failed");
+        return -1;
+    }
+    return 0;
+}
+
+int parsy_normal_apply_host(parsy_normal* h, int op, const double* fx, const double* w, const double* x, int ldx, int nrhs,
+                            double alpha, double beta, double* y, int ldy, double* seconds) {
+    const char* who = "parsy_normal_apply_host";
+    if (parsy::normal_check_apply_args(h, who, op, fx, x, ldx, nrhs, y, ldy) != 0) return -1;
+    PARSY_HIP(hipSetDevice(h->plan->device));
+    const int nx = op == PARSY_NORMAL_F ? h->I.m : h->I.n, ny = op == PARSY_NORMAL_F ? h->I.n : h->I.m;
+    Scratch sc;
+    double* d_fx = sc.upload(fx, h->I.nnzF(), true);
+    double* d_w = w ? sc.upload(w, h->I.m, true) : nullptr;
+    double* d_x = sc.upload(nullptr, (int64_t)nx * nrhs, false);
+    double* d_y = sc.upload(nullptr, (int64_t)ny * nrhs, false);
+    if (!d_fx || (w && !d_w) || !d_x || !d_y || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (nx > 0) PARSY_HIP(hipMemcpy2D(d_x, (size_t)nx * 8, x, (size_t)ldx * 8, (size_t)nx * 8, nrhs, hipMemcpyHostToDevice));
+    if (ny > 0 && beta != 0.0)
+        PARSY_HIP(hipMemcpy2D(d_y, (size_t)ny * 8, y, (size_t)ldy * 8, (size_t)ny * 8, nrhs, hipMemcpyHostToDevice));
+    if (parsy_normal_apply_device(h, op, d_fx, d_w, d_x, std::max(nx, 1), nrhs, alpha, beta, d_y, std::max(ny, 1), nullptr) != 0)
+        return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    if (ny > 0) PARSY_HIP(hipMemcpy2D(y, (size_t)ldy * 8, d_y, (size_t)ny * 8, (size_t)ny * 8, nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int parsy_lsq_solve_host(parsy_normal* h, const double* fx, const double* w, double beta, const double* lValues,
+                         const double* c, int ldc, double* x, int ldx, int nrhs, int steps, double* r, int ldr, double* g,
+                         int ldg, double* seconds) {
+    const char* who = "parsy_lsq_solve_host";
+    if (parsy::normal_check_lsq_args(h, who, fx, lValues, c, ldc, x, ldx, nrhs, steps, r, ldr, g, ldg) != 0) return -1;
+    parsy_plan* pl = h->plan;
+    const int n = h->I.n, m = h->I.m;
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)pl->S.xsize * 8, hipMemcpyHostToDevice));
+    Scratch sc;
+    double* d_fx = sc.upload(fx, h->I.nnzF(), true);
+    double* d_w = w ? sc.upload(w, m, true) : nullptr;
+    double* d_c = sc.upload(nullptr, (int64_t)m * nrhs, false);
+    double* d_x = sc.upload(nullptr, (int64_t)n * nrhs, false);
+    double* d_r = r ? sc.upload(nullptr, (int64_t)m * nrhs, false) : nullptr;
+    double* d_g = g ? sc.upload(nullptr, (int64_t)n * nrhs, false) : nullptr;
+    if (!d_fx || (w && !d_w) || !d_c || !d_x || (r && !d_r) || (g && !d_g) || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (m > 0) PARSY_HIP(hipMemcpy2D(d_c, (size_t)m * 8, c, (size_t)ldc * 8, (size_t)m * 8, nrhs, hipMemcpyHostToDevice));
+    if (parsy_lsq_solve_device(h, d_fx, d_w, beta, pl->h_L_dev.data(), d_c, std::max(m, 1), d_x, std::max(n, 1), nrhs, steps,
+                               d_r, std::max(m, 1), d_g, std::max(n, 1), nullptr) != 0)
+        return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    if (parsy_solve_status(pl) != 0) return -1;
+    if (n > 0) PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, d_x, (size_t)n * 8, (size_t)n * 8, nrhs, hipMemcpyDeviceToHost));
+    if (r && m > 0) PARSY_HIP(hipMemcpy2D(r, (size_t)ldr * 8, d_r, (size_t)m * 8, (size_t)m * 8, nrhs, hipMemcpyDeviceToHost));
+    if (g && n > 0) PARSY_HIP(hipMemcpy2D(g, (size_t)ldg * 8, d_g, (size_t)n * 8, (size_t)n * 8, nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

@@ -1,10 +1,11 @@
 // The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp,
-// rowmod.hpp, eigs.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
+// rowmod.hpp, eigs.hpp, normal.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
 // each only once one of the feature's device calls has run.
 #pragma once
 #include "apply.hpp"
 #include "device_buffer.hpp"
 #include "grad.hpp"
+#include "normal.hpp"
 #include "rowmod.hpp"
 #include "selinv.hpp"
 #include "updown.hpp"
@@ -132,4 +133,30 @@ struct EigsState {
     std::vector<double> h_g, h_s, h_st, h_theta, h_c1, h_c2, h_eta;
 };
 
+// Device state of a normal-matrix handle (normal.hpp, normal_kernels.hip): made by the handle's first device call.
+struct NormalState {
+    ByteMeter meter;                  // parsy_normal_info.device_bytes: everything here (a handle's memory is its own: not in
+                                      // the plan's figure, the plan may be destroyed first)
+    bool on_device = false;           // set when the whole index is on the device
+    DevicePool index{&meter};
+    int64_t *d_lptr = nullptr, *d_chunk_off = nullptr, *d_rptr = nullptr;
+    int32_t *d_ta = nullptr, *d_tb = nullptr, *d_tk = nullptr, *d_chunk_len = nullptr, *d_fold_q = nullptr,
+            *d_fold_ptr = nullptr, *d_fp = nullptr, *d_fi = nullptr, *d_rpos = nullptr, *d_rcol = nullptr;
+    int32_t* d_cls[kNormalClasses] = {nullptr, nullptr, nullptr};
+    uint8_t* d_diag = nullptr;
+    double* d_part = nullptr;         // one partial per chunk
+    int* d_perm = nullptr;            // the handle's ordering and its inverse (null: identity)
+    int* d_inv = nullptr;
+    int* d_ctl = nullptr;             // the folded status of the solves of a least-squares call
+    DeviceBuf<double> ws{&meter};     // n x nrhs + m x nrhs of parsy_lsq_solve_device
+};
+
 }  // namespace parsy
+
+// A handle: one plan, one pattern of F.  The plan is borrowed and must outlive every device call of the handle.
+struct parsy_normal {
+    parsy_plan* plan = nullptr;
+    int device = -1;                  // the plan's (kept: parsy_normal_destroy may run after the plan is gone)
+    parsy::NormalIndex I;
+    parsy::NormalState dev;
+};

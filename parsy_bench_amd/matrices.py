@@ -85,6 +85,55 @@ def grid_spd(nx: int, ny: int, nz: int = 1, stencil: int = 5, shift: float = 0.1
     return LowerCSC(n, Ap, Ai, Ax)
 
 
+@dataclass
+class ColumnsCSC:
+    """A sparse n x m matrix in compressed columns, rows ascending within a column (the F of api.NormalEquations)."""
+    n: int
+    m: int
+    indptr: np.ndarray   # int32 m+1
+    indices: np.ndarray  # int32 nnz
+    data: np.ndarray     # float64 nnz
+
+    def to_dense(self) -> np.ndarray:
+        F = np.zeros((self.n, self.m))
+        cols = np.repeat(np.arange(self.m), np.diff(self.indptr))
+        F[self.indices, cols] = self.data
+        return F
+
+
+def _columns(n: int, rows: np.ndarray, vals: np.ndarray) -> ColumnsCSC:
+    """rows / vals: (m, c) arrays, one column of F per line; the rows of a line are sorted here."""
+    m, c = rows.shape
+    order = np.argsort(rows, axis=1, kind="stable")
+    rows = np.take_along_axis(rows, order, axis=1)
+    vals = np.take_along_axis(vals, order, axis=1)
+    return ColumnsCSC(n, m, (np.arange(m + 1, dtype=np.int64) * c).astype(np.int32), rows.reshape(-1).astype(np.int32),
+                      np.ascontiguousarray(vals.reshape(-1), dtype=np.float64))
+
+
+def grid_edges(nx: int, ny: int, nz: int = 1) -> ColumnsCSC:
+    """The edge-node incidence of the 5- / 7-point grid: one column per edge, +1 at its lower node and -1 at the
+    higher.  F F' + shift I is grid_spd(nx, ny, nz, 5 or 7, shift) exactly."""
+    ids = np.arange(nx * ny * nz).reshape(nz, ny, nx)
+    pairs = [np.stack([ids[:, :, :-1].ravel(), ids[:, :, 1:].ravel()], axis=1),
+             np.stack([ids[:, :-1, :].ravel(), ids[:, 1:, :].ravel()], axis=1),
+             np.stack([ids[:-1, :, :].ravel(), ids[1:, :, :].ravel()], axis=1)]
+    rows = np.concatenate(pairs, axis=0)
+    vals = np.tile(np.array([1.0, -1.0]), (rows.shape[0], 1))
+    return _columns(nx * ny * nz, rows, vals)
+
+
+def grid_cells(nx: int, ny: int, nz: int = 1) -> ColumnsCSC:
+    """One column per cell of the grid with a one at each of its 4 (2-D, nz == 1) or 8 corners: F F' has exactly the
+    9- / 27-point pattern."""
+    ids = np.arange(nx * ny * nz).reshape(nz, ny, nx)
+    zs = (0,) if nz == 1 else (0, 1)
+    corners = [ids[dz:nz - (1 if nz > 1 else 0) + dz, dy:ny - 1 + dy, dx:nx - 1 + dx].ravel()
+               for dz in zs for dy in (0, 1) for dx in (0, 1)]
+    rows = np.stack(corners, axis=1)
+    return _columns(nx * ny * nz, rows, np.ones(rows.shape))
+
+
 def grid_nd(nx: int, ny: int, nz: int = 1, leaf: int | None = None) -> np.ndarray:
     if leaf is None:
         leaf = 8 if nz == 1 else 27
