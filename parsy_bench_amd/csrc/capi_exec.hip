@@ -560,6 +560,27 @@ int64_t parsy_debug_launches(const parsy_plan* pl, int which, int32_t* out, int6
     return (int64_t)seq.size();
 }
 
+// Diagnostics: the route of a solve (solve_route.hpp) with the gates the environment sets at this call, as the witness
+// indices (parsy_debug_kernel_name) of the launches it enqueues, in order; plans without a device too (device < 0: every
+// subtree tier counts as usable).  Returns the number of launches and fills at most cap entries (kernels may be null);
+// -1: nrhs < 1 or ldx < n.
+int64_t parsy_debug_solve_route(const parsy_plan* pl, int nrhs, int ldx, int backward, int32_t* kernels, int64_t cap) {
+    if (!pl || nrhs < 1 || ldx < pl->S.n) return -1;
+    parsy::SolveRoute R;
+    parsy::solve_route(pl->S, parsy::read_solve_gates(), parsy::plan_route_runtime(pl), nrhs, ldx, backward != 0, R);
+    return parsy::route_kernels(R, kernels, cap);
+}
+
+// ... and of one step of a solve in steps of levels (parsy_solve_levels_device: level_begin, level_end, flags)
+int64_t parsy_debug_solve_route_levels(const parsy_plan* pl, int nrhs, int ldx, int level_begin, int level_end, int flags,
+                                       int32_t* kernels, int64_t cap) {
+    if (!pl || nrhs < 1 || ldx < pl->S.n || level_begin > level_end) return -1;
+    parsy::SolveRoute R;
+    parsy::solve_route_levels(pl->S, parsy::read_solve_gates(), parsy::plan_route_runtime(pl), nrhs, ldx, (flags & 4) != 0,
+                              level_begin, level_end, (flags & 1) != 0, (flags & 2) != 0, R);
+    return parsy::route_kernels(R, kernels, cap);
+}
+
 // Diagnostics (tools/schedule_digests.py): the digest of the plan's whole schedule (schedule_digest.hpp) -- one 64-bit hash
 // per data member of parsy::Schedule, in declaration order.  Returns the number of fields; out / name (either may be
 // null) receive the hash and the member's name of field `field`, where that is one.

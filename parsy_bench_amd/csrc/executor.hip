@@ -177,7 +177,7 @@ int plan_upload_launches(parsy_plan* pl) {
         upload(pl, S.sub_slots, pl->dp.sub_slots, true) || upload(pl, S.sub_out_rows, pl->dp.sub_out_rows, true))
         return -1;
     // (trees whose workgroup would not get its LDS: the subtree launches keep the level kernels' form)
-    pl->dp.sub_ntiers = (!S.sub_tiers.empty() && solve_sub_prepare(S.sub_max_slots) == 0) ? (int)S.sub_tiers.size() : 0;
+    pl->route_rt.sub_ntiers = (!S.sub_tiers.empty() && solve_sub_prepare(S.sub_max_slots) == 0) ? (int)S.sub_tiers.size() : 0;
     {
         auto up = [&](const Schedule::OneLists& O, DevicePattern::OneDev& D) {
             D = DevicePattern::OneDev();
@@ -326,30 +326,18 @@ static void profile_mark(parsy_plan* pl, int kind, hipStream_t stream, size_t& c
     ++cursor;
 }
 
-// The subtree launches of a solve with this many right-hand sides take the form of one wave per subtree and 16 right-
-// hand sides (trsv_sub_kernels.hip; PARSY_SUB_MRHS_MIN, 0: never)
-// (the kernels address x by a 32-bit byte offset from a wave-uniform base: 16 rows or right-hand sides of either stride)
-static bool sub_tiers_usable(const parsy_plan* pl, int nrhs, int ldx) {
-    const int m = pl->dp.gates.sub_mrhs_min;
-    return pl->dp.sub_ntiers > 0 && m > 0 && nrhs >= m && ldx < (1 << 24) && nrhs < (1 << 20);
-}
-
-// Enqueue the launches seq[i0, i1).  The state that orders the two streams (which level-completion events have been
-// recorded, which side launches are in flight, the profiling cursor) lives in the plan, so that a factorization can
-// be enqueued level by level (parsy_factor_level) with the caller's own work -- the exchange step of a
-// multi-device run -- in between: run_begin() resets it, run_end() closes the profiling record.
+// Enqueue the factorization's launches seq[i0, i1) (a solve's: run_route).  The state that orders the two streams (which
+// level-completion events have been recorded, which side launches are in flight, the profiling cursor) lives in the plan,
+// so that a factorization can be enqueued level by level (parsy_factor_level) with the caller's own work -- the exchange
+// step of a multi-device run -- in between: run_begin() resets it, run_end() closes the profiling record.
 static void run_begin(parsy_plan* pl) {
     pl->run_cursor = 0;
     pl->run_next_level_event = 0;
     pl->run_early_seen.assign(pl->ev_early_done.size(), 0);
 }
 
-// (the solve cases of the switch below, run_solve, plan_solve and plan_backsolve choose launch functions by form, gates and
-// right-hand sides: mirrored by predict() of tests/solve_cases.py -- change both)
-static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0, size_t i1, double* L,
-                      const double* Lc, double* x, int nrhs, int ldx, hipStream_t stream) {
+static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0, size_t i1, double* L, hipStream_t stream) {
     size_t& cursor = pl->run_cursor;
-    double *const dinv = pl->dinv.data(), *const xscratch = pl->xscratch.data();
     // TILES_EARLY launches go to the side stream (unless profiling / disabled): they wait for the
     // completion event of the level two below their targets and run beside the main stream's
     // block-column chain; the matching TILES (late) launch waits for them.
@@ -397,42 +385,7 @@ static void run_range(parsy_plan* pl, const std::vector<Launch>& seq, size_t i0,
                 break;
             }
             case kLaunchChain: launch_chol_chain(pl->dp, l.first, l.count, l.ticket, pl->epoch, l.rows_only != 0, L, stream); break;
-            case kLaunchSolveSmall:
-                // (the subtree launch with many right-hand sides: a wave per subtree and 16 right-hand sides, traffic in LDS)
-                if (l.form == kFormSubtrees && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count)
-                    launch_solve_sub_mrhs(pl->dp, pl->S.sub_tiers[0], Lc, x, nrhs, ldx, pl->solve_ldq, stream);
-                else
-                    launch_solve_small(pl->dp, l.first, l.count, l.width, l.form == kFormSubtrees, Lc, x, nrhs, ldx, pl->solve_ldq, stream);
-                break;
-            case kLaunchSolvePanel:
-                if (l.form == kFormChain && nrhs >= pl->dp.gates.chain_mrhs_min)
-                    launch_solve_blocks_mrhs(pl->dp, l.task_first, l.task_count, Lc, dinv, x, xscratch, nrhs, ldx,
-                                             pl->solve_ldq, l.ticket, pl->dp.gates.wait_bias, stream);
-                else if (l.form == kFormChain)   // (one right-hand side: chain_mrhs_min is at most 2)
-                    launch_solve_chain(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, l.ticket, pl->dp.gates.wait_bias,
-                                       stream);
-                else
-                    launch_solve_panel(pl->dp, l.first, l.count, Lc, x, xscratch, nrhs, ldx, stream);
-                break;
-            case kLaunchSolveFixup:
-                launch_solve_fixup(pl->dp, l.first, l.count, x, xscratch, nrhs, ldx, stream);
-                break;
-            case kLaunchBackBelow:
-                if (nrhs == 1) launch_bsolve_below(pl->dp, l.first, l.count, Lc, x, stream);
-                break;
-            case kLaunchBackBlock:
-                if (l.form == kFormChain && nrhs == 1) {   // one right-hand side: the wave dataflow over block-column pairs
-                    launch_bsolve_chain_w(pl->dp, l.task_first, l.task_count, Lc, dinv, x, xscratch, l.ticket,
-                                          pl->dp.gates.wait_bias, stream);
-                    break;
-                }
-                if (l.form == kFormSubtrees && sub_tiers_usable(pl, nrhs, ldx) && pl->S.sub_tiers[0].ntrees == l.count) {
-                    launch_bsolve_sub_mrhs(pl->dp, pl->S.sub_tiers[0], Lc, x, nrhs, ldx, stream);
-                    break;
-                }
-                launch_bsolve_block(pl->dp, l.first, l.count, Lc, dinv, x, xscratch, nrhs, ldx, (LaunchForm)l.form,
-                                    l.width_class, l.ticket, pl->dp.gates.wait_bias, stream);
-                break;
+            default: break;   // (the solves' kinds: enqueued from a route, run_route)
         }
     }
 }
@@ -442,47 +395,21 @@ static void run_end(parsy_plan* pl, hipStream_t stream) {
     if (pl->profile) pl->pev_kind.resize(pl->run_cursor);
 }
 
-static void run_launches(parsy_plan* pl, const std::vector<Launch>& seq, double* L, const double* Lc,
-                         double* x, int nrhs, int ldx, hipStream_t stream) {
-    run_begin(pl);
-    run_range(pl, seq, 0, seq.size(), L, Lc, x, nrhs, ldx, stream);
-    run_end(pl, stream);
-}
-
-// Whether a solve is ONE launch (its counters follow the status word in the hand-off buffers; no chain tickets)
-// (how many right-hand sides: 8 where the launch has at most kOneSmallBlocks blocks -- ex15-class, 8: 0.130 -> 0.087 ms --, else
-// 4 -- from 6 on the level launches use the matrix cores: nd24k-class, 8: 0.75 vs 1.24 ms this way; 4: 0.81 -> 0.60 --, and 1 for
-// the backward solve beside a subtree launch -- parabolic_fem-class, 4: 0.79 vs 0.86 ms -- and for the much larger plans)
-static bool solve_takes_one_launch(const parsy_plan* pl, int nrhs, bool backward) {
-    if (!(backward ? pl->S.solve_one_back : pl->S.solve_one)) return false;
-    if (backward ? pl->one_off_back : pl->one_off) return false;   // (its buffers could not be allocated)
-    const size_t nblocks = backward ? pl->S.one_back().sn.size() : pl->S.one_f.sn.size();
-    // (round 5, tools/gate_sweep.py: forward blocks of 5-8 right-hand sides through the ONE launch on factors of fewer than
-    // 400 entries per row -- 2-D grids of 3 400 .. 14 000 supernodes 0.26 -> 0.18, 0.33 -> 0.24, 0.35 -> 0.31 ms; 3-D grids of
-    // 580-670 entries per row lose 5 %, the backward solve loses wherever the plan is not small)
-    // -- and up to 4 096 blocks: the parabolic_fem-class plan, 6 546 blocks, takes 8 right-hand sides through its subtree and
-    // band launches in 0.51 ms against 0.60; likewise the backward solve beside a subtree launch: 4 right-hand sides per
-    // ONE launch up to that size (grids of 2 000 .. 4 000 blocks: 0.44 -> 0.34, 1.11 -> 0.93, 0.81 -> 0.68, 0.40 -> 0.26 ms), one
-    // beyond it (parabolic_fem-class, 4: 0.79 vs 0.86 ms)
-    const bool mid = nblocks <= (size_t)kOneMidBlocks && !pl->S.one_big;
-    const bool f8 = !backward && mid && pl->S.xsize < (int64_t)kOneRhs8Density * pl->S.n;
-    const int max_rhs = (pl->S.one_forced || nblocks <= (size_t)kOneSmallBlocks || f8)         ? kOneMaxRhs
-                        : (pl->S.one_big || (backward && pl->S.one_subtrees && !mid))          ? 1
-                                                                                               : 4;
-    return nrhs <= max_rhs;
-}
+struct OneBuffers {   // what one ONE-launch solve works through
+    double *y = nullptr, *y_next = nullptr;
+    int *st = nullptr, *st_next = nullptr;
+};
 
 // The buffers of the ONE-launch solves, made by the first of them: per direction two hand-off buffers (forward: one
 // slot per entry of the row-id array, backward: one per unknown; kOneMaxRhs right-hand sides), all armed, and two
 // {status, ticket} pairs, zero.  Every such solve then works through buffer / pair (its direction's count & 1) and
 // leaves the other one armed and zeroed for the next solve of its kind (k_solve_one, k_bsolve_one) -- one
 // enqueue per solve, no memset.
-static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream, double*& y, double*& y_next, int*& st,
-                     int*& st_next) {
-    // (a direction's buffers hold 1, 4 or 8 right-hand sides -- nd24k-class: 12.5 MB per right-hand side for the forward
-    // slots -- and are made again, larger, when a wider block comes: earlier solves on the stream are complete by then)
+static int one_begin(parsy_plan* pl, bool backward, int want, hipStream_t stream, OneBuffers& one) {
+    // (a direction's buffers hold `want` = 1, 4 or 8 right-hand sides, the route's capacity class -- nd24k-class: 12.5 MB per
+    // right-hand side for the forward slots -- and are made again, larger, when a wider block comes: earlier solves on the
+    // stream are complete by then)
     const int d = backward ? 1 : 0;
-    const int want = nrhs == 1 ? 1 : nrhs <= 4 ? 4 : kOneMaxRhs;
     DeviceBuf<double>& buf = pl->one_y[d];
     if (want > pl->one_cap[d] && buf.data()) {
         PARSY_HIP(hipStreamSynchronize(stream));
@@ -498,7 +425,7 @@ static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream
             // no room for the hand-off buffers: this plan's solves of that direction go by the level launches from now on
             (void)hipGetLastError();
             pl->one_cap[d] = 0;
-            (backward ? pl->one_off_back : pl->one_off) = true;
+            pl->route_rt.one_off[d] = true;
             return 1;
         }
         PARSY_HIP(solve_arm_handoff(buf.data(), (int64_t)(2 * len), stream));
@@ -508,41 +435,12 @@ static int one_begin(parsy_plan* pl, bool backward, int nrhs, hipStream_t stream
     const size_t len = (size_t)(backward ? pl->S.n : pl->dp.one_f.nslots) * pl->one_cap[d];
     int* state = reinterpret_cast<int*>(buf.data() + 2 * len);
     const unsigned k = pl->one_calls[d]++ & 1u;
-    y = buf.data() + k * len;
-    y_next = buf.data() + (k ^ 1u) * len;
-    st = state + 2 * k;
-    st_next = state + 2 * (k ^ 1u);
-    pl->solve_status_word = st;
+    one.y = buf.data() + k * len;
+    one.y_next = buf.data() + (k ^ 1u) * len;
+    one.st = state + 2 * k;
+    one.st_next = state + 2 * (k ^ 1u);
+    pl->solve_status_word = one.st;
     return 0;
-}
-
-// The gates of the solves' kernel variants (SolveGates, kernels.hpp), from the environment.
-SolveGates read_solve_gates() {
-    SolveGates g;
-    auto num = [](const char* name, int& v) {
-        const char* e = std::getenv(name);
-        if (e && *e) v = std::atoi(e);
-        return e && *e;
-    };
-    int m = 0;
-    num("PARSY_MRHS_MIN", m);
-    if (m > 0) {
-        g.mrhs_min = m;
-        g.chain_mrhs_min = std::min(m, g.chain_mrhs_min);
-    }
-    num("PARSY_BMRHS_MIN", g.bmrhs_min);
-    const char* w = std::getenv("PARSY_BMRHS_WIDE_ONLY");
-    g.bmrhs_wide_only = !(w && w[0] == '0');
-    num("PARSY_BMRHS_WIDE_BLOCKS", g.bmrhs_wide_blocks);
-    num("PARSY_BCHAIN_MIN_BLOCKS", g.bchain_min_blocks);
-    num("PARSY_SMALL_MRHS_HALVES_MIN", g.small_halves_min);
-    num("PARSY_SUB_MRHS_MIN", g.sub_mrhs_min);
-    g.xt_min_set = num("PARSY_XT_MIN", g.xt_min);
-    num("PARSY_CHAIN_FEW_CHUNKS", g.chain_few_chunks);
-    const char* st = std::getenv("PARSY_DEBUG_SOLVE_STALL");
-    g.wait_bias = (st && st[0] == '1') ? (1 << 20) : 0;
-    num("PARSY_SUB_ABL", g.sub_abl);
-    return g;
 }
 
 // Argument checks of a device solve (`who`: the C ABI call the messages name).  A solve that starts here abandons one in
@@ -558,66 +456,92 @@ static int solve_start(parsy_plan* pl, const char* who, bool args_ok, const char
     }
     if (starts) {
         pl->levels_open = false;
-        pl->dp.gates = read_solve_gates();
+        pl->gates = read_solve_gates();
     }
     return 0;
 }
 
-// The prologue of a solve by level launches: its own status word and the chain launches' ticket counters zeroed
-// (arm_wide: by the k_solve_arm_wide launch below instead), xscratch grown to `scratch` entries, the inverse diagonal
-// blocks and (bpart, one right-hand side) the backward partial sums allocated by the first solve that needs them; then
-// ev_s0, the hand-off buffer armed -- its first `armed` entries, or with arm_wide the wide supernodes' columns -- and
-// k_diag_inverse.  The chain launches hand x over through xscratch itself (solve_arm_handoff) and finish a block
-// column with a product with its inverse diagonal block.
-static int solve_prologue(parsy_plan* pl, const double* d_L, int nrhs, int ldx, int ldq, int64_t scratch, bool bpart,
-                          bool arm_wide, int64_t armed, hipStream_t stream) {
+// The prologue of a solve by level launches, from its route's facts: its own status word and the chain launches' ticket
+// counters zeroed (arm_wide: by the route's k_solve_arm_wide launch instead), xscratch grown to `scratch` entries, xt to X
+// row-major, the inverse diagonal blocks and the backward partial sums allocated by the first solve that needs them;
+// then ev_s0 and, without arm_wide, the first `armed` entries of the hand-off buffer armed.  The chain launches hand x
+// over through xscratch itself (solve_arm_handoff) and finish a block column with a product with its inverse diagonal
+// block (k_diag_inverse, the route's next launch).
+static int solve_prologue(parsy_plan* pl, const SolveRoute& R, hipStream_t stream) {
     const Schedule& S = pl->S;
-    const int nwide = (int)S.solve_wide_list.size() / 2, ntickets = std::max(S.n_solve_chain_launches, 1);
     pl->solve_status_word = nullptr;
-    if (!arm_wide) {
+    if (!R.arm_wide) {
         PARSY_HIP(hipMemsetAsync(pl->dp.sinfo, 0, sizeof(int), stream));
-        PARSY_HIP(hipMemsetAsync(pl->dp.stickets, 0, (size_t)ntickets * sizeof(int), stream));
+        PARSY_HIP(hipMemsetAsync(pl->dp.stickets, 0, (size_t)std::max(S.n_solve_chain_launches, 1) * sizeof(int), stream));
     }
-    if (scratch > 0) PARSY_HIP(pl->xscratch.grow(scratch));
-    if (nwide > 0 && !pl->dinv.data()) PARSY_HIP(pl->dinv.grow(std::max<int64_t>(S.n_dslots, 1) * kTile * kTile));
-    if (bpart && nrhs == 1 && S.n_bpart_slots > 0 && !pl->dp.bpart) {
+    if (R.use_xt) PARSY_HIP(pl->xt.grow((int64_t)S.n * R.ldq));
+    if (R.scratch > 0) PARSY_HIP(pl->xscratch.grow(R.scratch));
+    if (R.dinv && !pl->dinv.data()) PARSY_HIP(pl->dinv.grow(std::max<int64_t>(S.n_dslots, 1) * kTile * kTile));
+    if (R.bpart && !pl->dp.bpart) {
         PARSY_HIP(pl->bpart.grow((int64_t)S.n_bpart_slots * kTile));
         pl->dp.bpart = pl->bpart.data();
     }
     PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-    if (arm_wide) launch_solve_arm_wide(pl->dp, nwide, pl->xscratch.data(), nrhs, ldx, ldq, ntickets, stream);
-    else if (armed > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch.data(), armed, stream));
-    launch_diag_inverse(pl->dp, nwide, d_L, pl->dinv.data(), stream);
+    if (!R.arm_wide && R.armed > 0) PARSY_HIP(solve_arm_handoff(pl->xscratch.data(), R.armed, stream));
     return 0;
 }
 
-// The level launches of a whole forward / backward solve.  Where the subtree tiers serve it (sub_tiers_usable), the bands
-// of levels that are one launch each take the place of the level launches they cover: first in the forward solve, last
-// in the backward one.
-static void run_solve(parsy_plan* pl, bool backward, const double* d_L, double* x, int nrhs, int ldx, hipStream_t stream) {
+// Walk a route: every step's mark in the profiling record (run_begin has opened it; `end`: closed behind the last marked
+// step), then the launch function its kernel belongs to, with the launch record or the tier the step runs on.
+static void run_route(parsy_plan* pl, const SolveRoute& R, bool backward, const OneBuffers& one, const double* L, double* d_x,
+                      int nrhs, int ldx, hipStream_t stream, bool end = true) {
     const Schedule& S = pl->S;
+    const DevicePattern& P = pl->dp;
     const std::vector<Launch>& seq = backward ? S.bsolve : S.solve;
-    if (!sub_tiers_usable(pl, nrhs, ldx) || S.sub_cover_level < 0) {
-        run_launches(pl, seq, nullptr, d_L, x, nrhs, ldx, stream);
-        return;
-    }
-    run_begin(pl);
-    if (!backward) {
-        for (const SubTier& T : S.sub_tiers) {
-            profile_mark(pl, kLaunchSolveSmall, stream, pl->run_cursor, 0, 0, T.ntrees);
-            launch_solve_sub_mrhs(pl->dp, T, d_L, x, nrhs, ldx, pl->solve_ldq, stream);
+    double* const x = R.use_xt ? pl->xt.data() : d_x;
+    double *const dinv = pl->dinv.data(), *const xs = pl->xscratch.data();
+    const int wait_bias = pl->gates.wait_bias, sub_abl = pl->gates.sub_abl, cap = pl->one_cap[backward ? 1 : 0];
+    const int nwide = (int)S.solve_wide_list.size() / 2;
+    static const Launch none{};
+    for (size_t i = 0; i < R.steps.size(); ++i) {
+        const SolveStep& s = R.steps[i];
+        if (i == R.tail && end) run_end(pl, stream);
+        if (s.kind >= 0) profile_mark(pl, s.kind, stream, pl->run_cursor, s.level, s.side, s.count);
+        const Launch& l = s.launch >= 0 ? seq[(size_t)s.launch] : none;
+        switch (s.kernel) {
+            case kWSolveTiny: case kWSolveSmall: case kWSolveSmallMrhs16: case kWSolveSmallMrhs32: case kWSolveSmallMrhs64:
+            case kWSolveSmallMrhs64Halves:
+                launch_solve_small(P, s.kernel, l.first, l.count, l.form == kFormSubtrees, L, x, nrhs, ldx, R.ldq, stream);
+                break;
+            case kWSolveSubMrhs: launch_solve_sub_mrhs(P, S.sub_tiers[(size_t)s.tier], L, x, nrhs, ldx, R.ldq, sub_abl, stream); break;
+            case kWBsolveSubMrhs: launch_bsolve_sub_mrhs(P, S.sub_tiers[(size_t)s.tier], L, x, nrhs, ldx, sub_abl, stream); break;
+            case kWSolveBlocksMrhsNarrow: case kWSolveBlocksMrhs:
+                launch_solve_blocks_mrhs(P, s.kernel, l.task_first, l.task_count, L, dinv, x, xs, nrhs, ldx, R.ldq, l.ticket,
+                                         wait_bias, stream);
+                break;
+            case kWSolveChainW2: case kWSolveChainW4:
+                launch_solve_chain(P, s.kernel, l.first, l.count, L, dinv, x, xs, l.ticket, wait_bias, stream);
+                break;
+            case kWSolvePanel: launch_solve_panel(P, l.first, l.count, L, x, xs, nrhs, ldx, stream); break;
+            case kWSolveFixup: launch_solve_fixup(P, l.first, l.count, x, xs, nrhs, ldx, stream); break;
+            case kWBsolveBelow: launch_bsolve_below(P, l.first, l.count, L, x, stream); break;
+            case kWBsolveChainW: launch_bsolve_chain_w(P, l.task_first, l.task_count, L, dinv, x, xs, l.ticket, wait_bias, stream); break;
+            case kWBsolveBlock1: case kWBsolveBlock4: case kWBsolveBlockMrhs1: case kWBsolveBlockMrhs4: case kWBsolveChainMrhs:
+            case kWBsolveTiny16: case kWBsolveTiny32: case kWBsolveTinyMrhs:
+                launch_bsolve_block(P, s.kernel, l.first, l.count, L, dinv, x, xs, nrhs, ldx, (LaunchForm)l.form, l.ticket, wait_bias,
+                                    stream);
+                break;
+            case kWSolveOne1: case kWSolveOne4: case kWSolveOne8:
+                launch_solve_one(P, s.kernel, L, x, nrhs, ldx, one.y, one.y_next, one.st, one.st_next, wait_bias, cap, stream);
+                break;
+            case kWBsolveOne1: case kWBsolveOne4: case kWBsolveOne8:
+                launch_bsolve_one(P, s.kernel, S.n, L, x, nrhs, ldx, one.y, one.y_next, one.st, one.st_next, wait_bias, cap, stream);
+                break;
+            // (in before the marked steps, out behind them)
+            case kWTransposeX: launch_transpose_x(d_x, ldx, pl->xt.data(), R.ldq, S.n, nrhs, i < R.body, stream); break;
+            case kWSolveArmWide:
+                launch_solve_arm_wide(P, nwide, xs, nrhs, ldx, R.ldq, std::max(S.n_solve_chain_launches, 1), stream);
+                break;
+            case kWDiagInverse: launch_diag_inverse(P, nwide, L, dinv, stream); break;
+            default: break;   // (kWitnessCount: a launch record that enqueues nothing)
         }
     }
-    for (size_t li = 0; li < seq.size(); ++li)
-        if (seq[li].form != kFormSubtrees && seq[li].level > S.sub_cover_level)
-            run_range(pl, seq, li, li + 1, nullptr, d_L, x, nrhs, ldx, stream);
-    if (backward) {
-        for (size_t k = S.sub_tiers.size(); k-- > 0;) {
-            profile_mark(pl, kLaunchBackBlock, stream, pl->run_cursor, 0, 0, S.sub_tiers[k].ntrees);
-            launch_bsolve_sub_mrhs(pl->dp, S.sub_tiers[k], d_L, x, nrhs, ldx, stream);
-        }
-    }
-    run_end(pl, stream);
+    if (R.tail >= R.steps.size() && end) run_end(pl, stream);
 }
 
 static int solve_end(parsy_plan* pl, hipStream_t stream) {
@@ -627,40 +551,38 @@ static int solve_end(parsy_plan* pl, hipStream_t stream) {
     return 0;
 }
 
-int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
-    if (solve_start(pl, "parsy_backsolve", nrhs >= 1 && ldx >= pl->S.n, "nrhs >= 1 and ldx >= n") != 0) return -1;
-    const Schedule& S = pl->S;
-    double *y = nullptr, *y_next = nullptr;
-    int *st = nullptr, *st_next = nullptr;
-    int one_rc = solve_takes_one_launch(pl, nrhs, true) ? one_begin(pl, true, nrhs, stream, y, y_next, st, st_next) : 1;
-    if (one_rc < 0) return -1;
-    if (one_rc == 0) {
-        // the whole solve -- or everything above the subtree launch, which follows -- is ONE launch (k_bsolve_one)
-        PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-        run_begin(pl);
-        profile_mark(pl, kLaunchBackBlock, stream, pl->run_cursor, 0, 0, pl->dp.one_b.nblocks);
-        launch_bsolve_one(pl->dp, S.n, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, pl->dp.gates.wait_bias, pl->one_cap[1],
-                          stream);
-        if (S.one_subtrees && S.n_bsolve_subtrees > 0)
-            run_range(pl, S.bsolve, S.bsolve.size() - 1, S.bsolve.size(), nullptr, d_L, d_x, nrhs, ldx, stream);
-        run_end(pl, stream);
-        return solve_end(pl, stream);
+// A whole forward / backward solve: the arguments, the gates, the route, one prologue from the route's facts, the steps.
+static int solve_whole(parsy_plan* pl, const char* who, bool backward, const double* d_L, double* d_x, int nrhs, int ldx,
+                       hipStream_t stream) {
+    if (solve_start(pl, who, nrhs >= 1 && ldx >= pl->S.n, "nrhs >= 1 and ldx >= n") != 0) return -1;
+    SolveRoute& R = pl->route[backward ? 1 : 0];
+    solve_route(pl->S, pl->gates, pl->route_rt, nrhs, ldx, backward, R);
+    OneBuffers one;
+    if (R.one) {
+        const int rc = one_begin(pl, backward, R.one_cap, stream, one);
+        if (rc < 0) return -1;
+        if (rc > 0) solve_route(pl->S, pl->gates, pl->route_rt, nrhs, ldx, backward, R);   // (no room: by level launches)
     }
-    // (several right-hand sides and wide supernodes: one prologue launch instead of memsets + a fill of n x nrhs entries)
-    const int64_t need = (int64_t)ldx * nrhs;
-    const bool wide = !S.solve_wide_list.empty();
-    if (solve_prologue(pl, d_L, nrhs, ldx, 0, S.max_width > kTile ? need : 0, true, nrhs > 1 && wide, wide ? need : 0,
-                       stream) != 0)
-        return -1;
-    run_solve(pl, true, d_L, d_x, nrhs, ldx, stream);
+    if (R.one) PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
+    else if (solve_prologue(pl, R, stream) != 0) return -1;
+    run_begin(pl);
+    run_route(pl, R, backward, one, d_L, d_x, nrhs, ldx, stream);
     return solve_end(pl, stream);
+}
+
+int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
+    return solve_whole(pl, "parsy_solve", false, d_L, d_x, nrhs, ldx, stream);
+}
+
+int plan_backsolve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
+    return solve_whole(pl, "parsy_backsolve", true, d_L, d_x, nrhs, ldx, stream);
 }
 
 // A solve in steps of etree levels (the exchange steps of a solve that is distributed above the cut go in between,
 // as parsy_factor_level's do for the factorization): the level launches of the plan's active supernodes whose level lies
 // in [lev0, lev1).  flags: bit 0 = the first step of a solve (status word, tickets, hand-off buffer, inverse diagonal
 // blocks), bit 1 = the last one, bit 2 = backward (levels then go DOWN from step to step).  Level launches only: the
-// caller's layout of X, no ONE launch, no bands (a rank's share of the supernodes has neither).
+// caller's layout of X, no ONE launch, no bands (a rank's share of the supernodes has neither) -- solve_route_levels.
 int plan_solve_levels(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream, int lev0,
                       int lev1, int flags) {
     const bool first = flags & 1, last = flags & 2, backward = flags & 4;
@@ -671,26 +593,17 @@ int plan_solve_levels(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, 
         set_last_error("parsy_solve_levels: a step without PARSY_SOLVE_FIRST needs an open solve of the same direction and width");
         return -1;
     }
-    const Schedule& S = pl->S;
+    SolveRoute& R = pl->route[backward ? 1 : 0];
+    solve_route_levels(pl->S, pl->gates, pl->route_rt, nrhs, ldx, backward, lev0, lev1, first, last, R);
     if (first) {
-        // (the wide supernodes' chains: one right-hand side forward hands over through the first ldx entries)
-        const int64_t need = (int64_t)ldx * nrhs;
-        const int64_t armed = S.n_solve_wide == 0 ? 0 : (!backward && nrhs == 1) ? (int64_t)ldx : need;
-        if (solve_prologue(pl, d_L, nrhs, ldx, 0, (S.n_solve_wide > 0 || S.max_width > kTile) ? need : 0, backward, false,
-                           armed, stream) != 0)
-            return -1;
-        pl->solve_ldq = 0;
+        if (solve_prologue(pl, R, stream) != 0) return -1;
         run_begin(pl);
         pl->levels_open = true;
         pl->levels_backward = backward;
         pl->levels_nrhs = nrhs;
     }
-    const std::vector<Launch>& seq = backward ? S.bsolve : S.solve;
-    for (size_t li = 0; li < seq.size(); ++li)
-        if ((seq[li].level >= lev0 && seq[li].level < lev1) || (last && seq[li].kind == kLaunchSolveFixup))
-            run_range(pl, seq, li, li + 1, nullptr, d_L, d_x, nrhs, ldx, stream);
+    run_route(pl, R, backward, OneBuffers(), d_L, d_x, nrhs, ldx, stream, last);
     if (!last) return 0;
-    run_end(pl, stream);
     pl->levels_open = false;
     return solve_end(pl, stream);
 }
@@ -762,8 +675,7 @@ int plan_factor_levels(parsy_plan* pl, int level0, int level1, double* d_L, hipS
         return -1;
     }
     if (level1 > level0)
-        run_range(pl, S.chol, S.chol_level_begin[(size_t)level0], S.chol_level_begin[(size_t)level1], d_L, d_L, nullptr,
-                  0, 0, stream);
+        run_range(pl, S.chol, S.chol_level_begin[(size_t)level0], S.chol_level_begin[(size_t)level1], d_L, stream);
     // (profiling: what the caller does between two steps is not a launch's time)
     profile_mark(pl, -1, stream, pl->run_cursor);
     pl->factor_next_level = level1;
@@ -813,51 +725,6 @@ int plan_factor(parsy_plan* pl, const double* d_values, double* d_L, hipStream_t
     if (plan_factor_begin(pl, d_values, d_L, stream, init) != 0) return -1;
     if (plan_factor_levels(pl, 0, pl->S.cnlevels, d_L, stream) != 0) return -1;
     return plan_factor_end(pl, stream);
-}
-
-int plan_solve(parsy_plan* pl, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream) {
-    if (solve_start(pl, "parsy_solve", nrhs >= 1 && ldx >= pl->S.n, "nrhs >= 1 and ldx >= n") != 0) return -1;
-    const Schedule& S = pl->S;
-    const SolveGates& G = pl->dp.gates;
-    double *y = nullptr, *y_next = nullptr;
-    int *st = nullptr, *st_next = nullptr;
-    int one_rc = solve_takes_one_launch(pl, nrhs, false) ? one_begin(pl, false, nrhs, stream, y, y_next, st, st_next) : 1;
-    if (one_rc < 0) return -1;
-    if (one_rc == 0) {
-        // the whole solve -- or everything above the subtree launch, which comes first -- is ONE launch (k_solve_one)
-        PARSY_HIP(hipEventRecord(pl->ev_s0, stream));
-        run_begin(pl);
-        pl->solve_ldq = 0;
-        if (S.one_subtrees && S.n_solve_subtrees > 0) run_range(pl, S.solve, 0, 1, nullptr, d_L, d_x, nrhs, ldx, stream);
-        profile_mark(pl, kLaunchSolveSmall, stream, pl->run_cursor, 0, 0, pl->dp.one_f.nblocks);
-        launch_solve_one(pl->dp, d_L, d_x, nrhs, ldx, y, y_next, st, st_next, G.wait_bias, pl->one_cap[0], stream);
-        run_end(pl, stream);
-        return solve_end(pl, stream);
-    }
-    // From 16 right-hand sides on the solve works on X with the right-hand sides of a row contiguous (transposed in
-    // and out: both kernels a solve of that many takes -- k_solve_small_mrhs, k_solve_blocks_mrhs -- read and write
-    // whole rows then; a supernode's x block was 64 eight-byte pieces per column).  PARSY_XT_MIN=k (0: never).
-    // (measured, 64 right-hand sides: Flan-class 23.1 -> 20.4 ms, nd24k-class 1.31 -> 1.19 ms; parabolic_fem-class 1.72 ->
-    // 1.75 ms -- its factor has 67 entries per row and the two transposes, 0.3 ms, cost what the kernels gain: the layout
-    // is taken from 200 entries of L per row on)
-    const bool use_xt = G.xt_min > 0 && nrhs >= G.xt_min && nrhs >= G.mrhs_min && S.solve_fix_list.empty() &&
-                        (S.xsize >= (int64_t)150 * S.n || G.xt_min_set);
-    const int ldq = use_xt ? (nrhs + 15) & ~15 : 0;
-    const int64_t need = use_xt ? (int64_t)S.n * ldq : (int64_t)ldx * nrhs;
-    if (use_xt) PARSY_HIP(pl->xt.grow(need));
-    // The chain launches of the wide supernodes take the whole buffer armed -- k_solve_chain_w (one right-hand side),
-    // k_solve_blocks_mrhs (from G.chain_mrhs_min on) --, or where it can (no fixup list) the latter's prologue launch,
-    // k_solve_arm_wide, arms their columns and zeroes the status word and the tickets.
-    const bool arm_wide = nrhs >= G.chain_mrhs_min && S.n_solve_wide > 0 && !S.solve_wide_list.empty() &&
-                          S.solve_fix_list.empty();
-    const int64_t scratch = S.n_solve_wide > 0 ? need : 0;
-    if (solve_prologue(pl, d_L, nrhs, ldx, ldq, scratch, false, arm_wide, scratch, stream) != 0) return -1;
-    pl->solve_ldq = ldq;
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt.data(), ldq, S.n, nrhs, true, stream);
-    run_solve(pl, false, d_L, use_xt ? pl->xt.data() : d_x, nrhs, ldx, stream);
-    if (use_xt) launch_transpose_x(d_x, ldx, pl->xt.data(), ldq, S.n, nrhs, false, stream);
-    pl->solve_ldq = 0;
-    return solve_end(pl, stream);
 }
 
 }  // namespace parsy

@@ -49,7 +49,12 @@ struct parsy_plan {
     parsy::DeviceBuf<double> one_y[2] = {parsy::DeviceBuf<double>(&meter), parsy::DeviceBuf<double>(&meter)};
     unsigned one_calls[2] = {0, 0};
     int one_cap[2] = {0, 0};                 // right-hand sides the buffers are made for (1, 4 or 8: grown on demand)
-    bool one_off = false, one_off_back = false;   // a direction whose buffers could not be allocated: level launches from then on
+    // The dispatch of the solves (solve_route.hpp): the gates of the running solve, what its route depends on beyond them
+    // and the schedule -- a direction whose ONE-launch buffers could not be allocated: level launches from then on; the
+    // subtree tiers whose workgroups get their LDS --, and the route itself, forward and backward, made again by every solve
+    parsy::SolveGates gates;
+    parsy::RouteRuntime route_rt;
+    parsy::SolveRoute route[2];
     const int* solve_status_word = nullptr;   // where the last solve left its status (null: dp.sinfo)
 
     // buffers of the host-buffer calls (capi_hostcalls.hip): A's values, the factor, the right-hand sides; they live as
@@ -86,7 +91,6 @@ struct parsy_plan {
     bool profile = false;
     parsy::DeviceBuf<double> xt;    // X with the right-hand sides of a row contiguous (forward solves with many of them;
                                     // not counted)
-    int solve_ldq = 0;              // > 0: the running solve works on xt with this row stride
     std::vector<hipEvent_t> pev;
     std::vector<int> pev_kind;
     std::vector<int> pev_level;     // per mark: level << 1 | side of a factorization launch (-1: other)
@@ -134,5 +138,11 @@ int plan_backsolve(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, i
 int plan_solve_levels(parsy_plan* plan, const double* d_L, double* d_x, int nrhs, int ldx, hipStream_t stream, int lev0,
                       int lev1, int flags);
 int plan_collect_profile(parsy_plan* plan);
+// What a route of the plan depends on at run time; without a device every subtree tier of the schedule counts as usable.
+inline RouteRuntime plan_route_runtime(const parsy_plan* plan) {
+    RouteRuntime rt = plan->route_rt;
+    if (plan->device < 0) rt.sub_ntiers = (int)plan->S.sub_tiers.size();
+    return rt;
+}
 
 }  // namespace parsy

@@ -1488,71 +1488,74 @@ void launch_bsolve_chain_w(const DevicePattern& P, int first, int count, const d
 
 // (backward launches of at least SolveGates::bmrhs_wide_blocks blocks, 128, take 64 right-hand sides per pass)
 // form: Launch::form -- kFormEach: one workgroup per block, kFormChain: chain launch (tickets), kFormSubtrees: subtree launch
-// (`first` counts (begin, end) pairs of bsolve_ranges, which index the whole block list); width_class: Launch::width_class
-// (0 | 1: kTinyWidth | 2: kTinyWidth2)
-// (the order of the choices below is mirrored by predict() of tests/solve_cases.py -- change both)
-void launch_bsolve_block(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
-                         double* x, double* xscratch, int nrhs, int ldx, LaunchForm form, int width_class, int ticket,
-                         int wait_bias, hipStream_t stream) {
+// (`first` counts (begin, end) pairs of bsolve_ranges, which index the whole block list)
+// (k: by width class, right-hand sides, form and count -- back_block_kernel, solve_route.cpp)
+void launch_bsolve_block(const DevicePattern& P, WitnessKernel k, int first, int count, const double* L, const double* dinv,
+                         double* x, double* xscratch, int nrhs, int ldx, LaunchForm form, int ticket, int wait_bias,
+                         hipStream_t stream) {
     if (count <= 0) return;
     const int chain = form == kFormChain;
     const PanelDesc* pds = form == kFormSubtrees ? P.bsolve_blocks : P.bsolve_blocks + first;
     const int32_t* ranges = form == kFormSubtrees ? P.bsolve_ranges + 2 * first : nullptr;
-    const SolveGates& G = P.gates;
-    if (width_class == 1 && nrhs >= G.bmrhs_min) {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
-        const dim3 grid(count, std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM));
-        launch_witnessed<k_bsolve_tiny_mrhs, kWBsolveTinyMrhs>(grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L,
-            x, nrhs, ldx);
-        return;
-    }
-    if (width_class && nrhs < G.bmrhs_min) {   // width class kTinyWidth (1) or kTinyWidth2 (2), a subtree launch or a level's launch: one wave each
-        const dim3 grid(count, std::min(kPassLanes, nrhs));
-        static_assert(kTinyWidth == 16 && kTinyWidth2 == 32, "witness entries k_bsolve_tiny<16>, <32>");
-        if (width_class == 1) {
-            launch_witnessed<k_bsolve_tiny<kTinyWidth>, kWBsolveTiny16>(grid, dim3(64), 0, stream, P.sn, pds, ranges,
-                P.rows, L, x, nrhs, ldx);
-        } else {
-            launch_witnessed<k_bsolve_tiny<kTinyWidth2>, kWBsolveTiny32>(grid, dim3(64), 0, stream, P.sn, pds, ranges,
-                P.rows, L, x, nrhs, ldx);
+    static_assert(kTinyWidth == 16 && kTinyWidth2 == 32, "witness entries k_bsolve_tiny<16>, <32>");
+    switch (k) {
+        case kWBsolveTinyMrhs: {   // many right-hand sides: 64 per pass, matrix cores, one wave per supernode
+            const dim3 grid(count, std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM));
+            launch_witnessed<k_bsolve_tiny_mrhs, kWBsolveTinyMrhs>(grid, dim3(64), 0, stream, P.sn, pds, ranges, P.rows, L,
+                x, nrhs, ldx);
+            break;
         }
-        return;
-    }
-    // launches of few blocks (the top of the tree, small inputs: a chain of hand-offs, not a stream of L) keep the
-    // light kernel -- 4 right-hand sides per workgroup, up to 8 workgroups per block side by side (nd24k-class, 16
-    // right-hand sides: 1.02 ms against 2.06 with the kernel below everywhere)
-    // (G.bmrhs_wide_only; PARSY_BMRHS_WIDE_ONLY=0: the kernel below everywhere)
-    // (round 5) chain launches of more than 16 right-hand sides: k_bsolve_chain_mrhs from G.bchain_min_blocks (128) block
-    // columns on (PARSY_BCHAIN_MIN_BLOCKS), 64 right-hand sides per pass
-    if (chain && nrhs > 16 && nrhs >= G.bmrhs_min && count >= G.bchain_min_blocks) {
-        const int mlanes = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
-        launch_witnessed<k_bsolve_chain_mrhs, kWBsolveChainMrhs>(dim3(count * mlanes), dim3(kThreads), 0, stream, P.sn,
-            pds, P.rows, L, x, xscratch, nrhs, ldx, P.sinfo, P.stickets + ticket, wait_bias, count, dinv);
-        return;
-    }
-    if (nrhs >= G.bmrhs_min && (!G.bmrhs_wide_only || count >= G.bmrhs_wide_blocks)) {   // 64 right-hand sides per pass over L, products on the matrix cores
-        // launches of few blocks (the top of the tree, small inputs) take 16 right-hand sides per pass in up to 8
-        // workgroups per block side by side; the others 64 per pass (L read once per 64)
-        const bool wide = count >= G.bmrhs_wide_blocks && nrhs > 16;
-        const int per = wide ? kRhsM : 16;
-        const int mlanes = std::min(kPassLanes, (nrhs + per - 1) / per);
-        const dim3 mgrid = chain ? dim3(count * mlanes) : dim3(count, mlanes);
-        if (wide) {
-            launch_witnessed<k_bsolve_block_mrhs<4>, kWBsolveBlockMrhs4>(mgrid, dim3(kThreads), 0, stream, P.sn, pds,
-                P.rows, L, x, xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
-        } else {
-            launch_witnessed<k_bsolve_block_mrhs<1>, kWBsolveBlockMrhs1>(mgrid, dim3(kThreads), 0, stream, P.sn, pds,
-                P.rows, L, x, xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+        // width class kTinyWidth or kTinyWidth2, a subtree launch or a level's launch: one wave each
+        case kWBsolveTiny16:
+        case kWBsolveTiny32: {
+            const dim3 grid(count, std::min(kPassLanes, nrhs));
+            if (k == kWBsolveTiny16) {
+                launch_witnessed<k_bsolve_tiny<kTinyWidth>, kWBsolveTiny16>(grid, dim3(64), 0, stream, P.sn, pds, ranges,
+                    P.rows, L, x, nrhs, ldx);
+            } else {
+                launch_witnessed<k_bsolve_tiny<kTinyWidth2>, kWBsolveTiny32>(grid, dim3(64), 0, stream, P.sn, pds, ranges,
+                    P.rows, L, x, nrhs, ldx);
+            }
+            break;
         }
-        return;
-    }
-    const int lanes = nrhs == 1 ? 1 : std::min(kPassLanes, (nrhs + 3) / 4);
-    const dim3 grid = chain ? dim3(count * lanes) : dim3(count, lanes);
-    if (nrhs == 1) {
-        launch_witnessed<k_bsolve_block<1>, kWBsolveBlock1>(grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x,
-            xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
-    } else {
-        launch_witnessed<k_bsolve_block<4>, kWBsolveBlock4>(grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x,
-            xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+        case kWBsolveChainMrhs: {   // 64 right-hand sides per pass
+            const int mlanes = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
+            launch_witnessed<k_bsolve_chain_mrhs, kWBsolveChainMrhs>(dim3(count * mlanes), dim3(kThreads), 0, stream, P.sn,
+                pds, P.rows, L, x, xscratch, nrhs, ldx, P.sinfo, P.stickets + ticket, wait_bias, count, dinv);
+            break;
+        }
+        // products on the matrix cores: <1> 16 right-hand sides per pass in up to 8 workgroups per block side by side (launches
+        // of few blocks: the top of the tree, small inputs), <4> 64 per pass (L read once per 64)
+        case kWBsolveBlockMrhs4:
+        case kWBsolveBlockMrhs1: {
+            const bool wide = k == kWBsolveBlockMrhs4;
+            const int per = wide ? kRhsM : 16;
+            const int mlanes = std::min(kPassLanes, (nrhs + per - 1) / per);
+            const dim3 mgrid = chain ? dim3(count * mlanes) : dim3(count, mlanes);
+            if (wide) {
+                launch_witnessed<k_bsolve_block_mrhs<4>, kWBsolveBlockMrhs4>(mgrid, dim3(kThreads), 0, stream, P.sn, pds,
+                    P.rows, L, x, xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+            } else {
+                launch_witnessed<k_bsolve_block_mrhs<1>, kWBsolveBlockMrhs1>(mgrid, dim3(kThreads), 0, stream, P.sn, pds,
+                    P.rows, L, x, xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+            }
+            break;
+        }
+        // the light kernel: 4 right-hand sides per workgroup, up to 8 workgroups per block side by side
+        case kWBsolveBlock1:
+        case kWBsolveBlock4: {
+            const int lanes = nrhs == 1 ? 1 : std::min(kPassLanes, (nrhs + 3) / 4);
+            const dim3 grid = chain ? dim3(count * lanes) : dim3(count, lanes);
+            if (k == kWBsolveBlock1) {
+                launch_witnessed<k_bsolve_block<1>, kWBsolveBlock1>(grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x,
+                    xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+            } else {
+                launch_witnessed<k_bsolve_block<4>, kWBsolveBlock4>(grid, dim3(kThreads), 0, stream, P.sn, pds, P.rows, L, x,
+                    xscratch, nrhs, ldx, chain, P.sinfo, P.stickets + ticket, wait_bias, count, ranges, dinv);
+            }
+            break;
+        }
+        default: launch_refused("launch_bsolve_block", k);
     }
 }
 

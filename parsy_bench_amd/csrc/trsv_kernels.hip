@@ -312,7 +312,7 @@ __global__ __launch_bounds__(64) void k_solve_tiny(const SnDesc* __restrict__ sn
 //   * for the wide supernodes' chain (k_solve_blocks_mrhs) from 2 on
 // (parabolic_fem-class input, MI355X, forward solve: 4 right-hand sides 1.02 -> 0.85 ms, 8: 1.41 -> 0.89 ms; Flan-class,
 // 8: 18.2 -> 11.6 ms).  PARSY_MRHS_MIN=k sets both thresholds to k (diagnostics, tests).  These and the other gates of the
-// solves' variants: SolveGates (kernels.hpp), read at the start of every solve.
+// solves' variants: SolveGates (solve_route.hpp), read at the start of every solve; what is chosen with them: solve_route.cpp.
 static constexpr int kLdXs = kRhsM + 4; // row stride of xs in LDS
 
 template <int WMAX, bool HALVES = false>  // WMAX: widest supernode of the launch, rounded up to 16 / 32 / 64: sizes LDS and loops
@@ -490,36 +490,39 @@ __global__ __launch_bounds__(kThreads) void k_solve_small_mrhs(const SnDesc* __r
   }
 }
 
-// (which kernel by width, right-hand sides and count: mirrored by predict() of tests/solve_cases.py -- change both)
-void launch_solve_small(const DevicePattern& P, int first, int count, int wmax, bool subtrees, const double* L,
+// (k: by width, right-hand sides and count -- small_kernel, solve_route.cpp)
+void launch_solve_small(const DevicePattern& P, WitnessKernel k, int first, int count, bool subtrees, const double* L,
                         double* x, int nrhs, int ldx, int ldq, hipStream_t stream) {
     if (count <= 0) return;
     // subtree launch: `first` counts (begin, end) pairs of solve_small_ranges, which index the whole list
     const int32_t* list = subtrees ? P.solve_small_list : P.solve_small_list + first;
     const int32_t* ranges = subtrees ? P.solve_small_ranges + 2 * first : nullptr;
-    const int mrhs_min = P.gates.mrhs_min;
-    if (nrhs < mrhs_min && wmax <= kTinyWidth) {   // one wave per supernode (or per subtree of them)
-        launch_witnessed<k_solve_tiny<kTinyWidth>, kWSolveTiny>(dim3(count, std::min(kPassLanes, nrhs)), dim3(64), 0,
-            stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx);
-        return;
-    }
-    if (nrhs >= mrhs_min) {
-        if (wmax <= 16) {
+    switch (k) {
+        case kWSolveTiny:   // one wave per supernode (or per subtree of them)
+            launch_witnessed<k_solve_tiny<kTinyWidth>, kWSolveTiny>(dim3(count, std::min(kPassLanes, nrhs)), dim3(64), 0,
+                stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx);
+            break;
+        case kWSolveSmallMrhs16:
             launch_witnessed<k_solve_small_mrhs<16>, kWSolveSmallMrhs16>(dim3(count), dim3(kThreads), 0, stream, P.sn,
                 list, ranges, P.rows, L, x, nrhs, ldx, ldq);
-        } else if (wmax <= 32) {
+            break;
+        case kWSolveSmallMrhs32:
             launch_witnessed<k_solve_small_mrhs<32>, kWSolveSmallMrhs32>(dim3(count), dim3(kThreads), 0, stream, P.sn,
                 list, ranges, P.rows, L, x, nrhs, ldx, ldq);
-        } else if (count >= P.gates.small_halves_min || nrhs <= 32) {   // (at most 32 right-hand sides: one sweep either way, fewer registers)
+            break;
+        case kWSolveSmallMrhs64Halves:
             launch_witnessed<k_solve_small_mrhs<64, true>, kWSolveSmallMrhs64Halves>(dim3(count), dim3(kThreads), 0,
                 stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx, ldq);
-        } else {
+            break;
+        case kWSolveSmallMrhs64:
             launch_witnessed<k_solve_small_mrhs<64>, kWSolveSmallMrhs64>(dim3(count), dim3(kThreads), 0, stream, P.sn,
                 list, ranges, P.rows, L, x, nrhs, ldx, ldq);
-        }
-    } else {
-        launch_witnessed<k_solve_small, kWSolveSmall>(dim3(count, std::min(kPassLanes, (nrhs + kRhs - 1) / kRhs)),
-            dim3(kThreads), 0, stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx);
+            break;
+        case kWSolveSmall:
+            launch_witnessed<k_solve_small, kWSolveSmall>(dim3(count, std::min(kPassLanes, (nrhs + kRhs - 1) / kRhs)),
+                dim3(kThreads), 0, stream, P.sn, list, ranges, P.rows, L, x, nrhs, ldx);
+            break;
+        default: launch_refused("launch_solve_small", k);
     }
 }
 
@@ -1318,20 +1321,22 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
 }
 #undef TSF
 
-// (narrow up to 16 right-hand sides: mirrored by predict() of tests/solve_cases.py -- change both)
-void launch_solve_blocks_mrhs(const DevicePattern& P, int first, int count, const double* L, const double* dinv,
+// (k: narrow up to 16 right-hand sides -- route_launch, solve_route.cpp)
+void launch_solve_blocks_mrhs(const DevicePattern& P, WitnessKernel k, int first, int count, const double* L, const double* dinv,
                               double* x, double* xscratch, int nrhs, int ldx, int ldq, int ticket, int wait_bias,
                               hipStream_t stream) {
     if (count <= 0) return;
     const int lanes_m = std::min(kPassLanes, (nrhs + kRhsM - 1) / kRhsM);
-    if (nrhs <= 16) {
+    if (k == kWSolveBlocksMrhsNarrow) {
         launch_witnessed<k_solve_blocks_mrhs<true>, kWSolveBlocksMrhsNarrow>(dim3(count * lanes_m), dim3(kThreads), 0,
             stream, P.sn, P.solve_mtasks + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, ldq, P.sinfo,
             P.stickets + ticket, wait_bias, count);
-    } else {
+    } else if (k == kWSolveBlocksMrhs) {
         launch_witnessed<k_solve_blocks_mrhs<false>, kWSolveBlocksMrhs>(dim3(count * lanes_m), dim3(kThreads), 0,
             stream, P.sn, P.solve_mtasks + first, P.rows, L, dinv, x, xscratch, nrhs, ldx, ldq, P.sinfo,
             P.stickets + ticket, wait_bias, count);
+    } else {
+        launch_refused("launch_solve_blocks_mrhs", k);
     }
 }
 
@@ -1383,16 +1388,18 @@ void launch_solve_arm_wide(const DevicePattern& P, int npairs, double* xscratch,
 }
 
 // One right-hand side: xscratch was armed by the caller (solve_arm_handoff)
-// (<2> up to P.gates.chain_few_chunks chunks, else <4>: mirrored by predict() of tests/solve_cases.py -- change both)
-void launch_solve_chain(const DevicePattern& P, int first, int count, const double* L, const double* dinv, double* x,
+// (k: <2> up to SolveGates::chain_few_chunks chunks, else <4> -- route_launch, solve_route.cpp)
+void launch_solve_chain(const DevicePattern& P, WitnessKernel k, int first, int count, const double* L, const double* dinv, double* x,
                         double* xscratch, int ticket, int wait_bias, hipStream_t stream) {
     if (count <= 0) return;
-    if (count <= P.gates.chain_few_chunks) {
+    if (k == kWSolveChainW2) {
         launch_witnessed<k_solve_chain_w<2>, kWSolveChainW2>(dim3(2 * count), dim3(kChainThreads), 0, stream, P.sn,
             P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias);
-    } else {
+    } else if (k == kWSolveChainW4) {
         launch_witnessed<k_solve_chain_w<4>, kWSolveChainW4>(dim3(count), dim3(kChainThreads), 0, stream, P.sn,
             P.solve_panels + first, P.rows, L, dinv, x, xscratch, P.sinfo, P.stickets + ticket, wait_bias);
+    } else {
+        launch_refused("launch_solve_chain", k);
     }
 }
 
@@ -1984,16 +1991,17 @@ __global__ __launch_bounds__(kThreads) void k_bsolve_one(const SnDesc* __restric
     }
 }
 
-void launch_solve_one(const DevicePattern& P, const double* L, double* x, int nrhs, int ldx, double* y, double* y_next,
+void launch_solve_one(const DevicePattern& P, WitnessKernel k, const double* L, double* x, int nrhs, int ldx, double* y, double* y_next,
                       int* state, int* state_next, int wait_bias, int cap, hipStream_t stream) {
     const DevicePattern::OneDev& O = P.one_f;
     if (O.nblocks <= 0) return;
 #define PARSY_ONE_ARGS                                                                                                  \
     dim3(O.nblocks), dim3(kThreads), 0, stream, O.sn, O.slot0, O.pull_ptr, O.pull_slot, O.pull_pos, L, x, nrhs, ldx, O.nslots, \
         y, y_next, state, state_next, wait_bias, cap
-    if (nrhs == 1) launch_witnessed<k_solve_one<1>, kWSolveOne1>(PARSY_ONE_ARGS);
-    else if (nrhs <= 4) launch_witnessed<k_solve_one<4>, kWSolveOne4>(PARSY_ONE_ARGS);
-    else launch_witnessed<k_solve_one<8>, kWSolveOne8>(PARSY_ONE_ARGS);
+    if (k == kWSolveOne1) launch_witnessed<k_solve_one<1>, kWSolveOne1>(PARSY_ONE_ARGS);
+    else if (k == kWSolveOne4) launch_witnessed<k_solve_one<4>, kWSolveOne4>(PARSY_ONE_ARGS);
+    else if (k == kWSolveOne8) launch_witnessed<k_solve_one<8>, kWSolveOne8>(PARSY_ONE_ARGS);
+    else launch_refused("launch_solve_one", k);
 #undef PARSY_ONE_ARGS
 }
 
@@ -2003,16 +2011,17 @@ extern "C" void parsy_debug_onestamps(unsigned long long* out) {
 }
 #endif
 
-void launch_bsolve_one(const DevicePattern& P, int n, const double* L, double* x, int nrhs, int ldx, double* y, double* y_next,
+void launch_bsolve_one(const DevicePattern& P, WitnessKernel k, int n, const double* L, double* x, int nrhs, int ldx, double* y, double* y_next,
                        int* state, int* state_next, int wait_bias, int cap, hipStream_t stream) {
     const DevicePattern::OneDev& O = P.one_b;
     if (O.nblocks <= 0) return;
 #define PARSY_ONE_ARGS                                                                                                  \
     dim3(O.nblocks), dim3(kThreads), 0, stream, O.sn, P.rows, O.wleft, L, x, nrhs, ldx, n, O.nblocks, y, y_next, state,        \
         state_next, wait_bias, cap
-    if (nrhs == 1) launch_witnessed<k_bsolve_one<1>, kWBsolveOne1>(PARSY_ONE_ARGS);
-    else if (nrhs <= 4) launch_witnessed<k_bsolve_one<4>, kWBsolveOne4>(PARSY_ONE_ARGS);
-    else launch_witnessed<k_bsolve_one<8>, kWBsolveOne8>(PARSY_ONE_ARGS);
+    if (k == kWBsolveOne1) launch_witnessed<k_bsolve_one<1>, kWBsolveOne1>(PARSY_ONE_ARGS);
+    else if (k == kWBsolveOne4) launch_witnessed<k_bsolve_one<4>, kWBsolveOne4>(PARSY_ONE_ARGS);
+    else if (k == kWBsolveOne8) launch_witnessed<k_bsolve_one<8>, kWBsolveOne8>(PARSY_ONE_ARGS);
+    else launch_refused("launch_bsolve_one", k);
 #undef PARSY_ONE_ARGS
 }
 

@@ -489,7 +489,7 @@ static void sub_grid(const SubTier& T, int nrhs, int& ngroups, dim3& grid, dim3&
 }
 
 void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const double* L, double* x, int nrhs, int ldx, int ldq,
-                           hipStream_t stream) {
+                           int sub_abl, hipStream_t stream) {
     if (T.ntrees <= 0) return;
     int ngroups, per_wave;
     dim3 grid, block;
@@ -498,11 +498,11 @@ void launch_solve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doubl
     const bool tr = ldq > 0;
     launch_witnessed<k_solve_sub_mrhs, kWSolveSubMrhs>(grid, block, lds, stream, P.sub_members, P.sub_trees,
         reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs,
-        (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, P.gates.sub_abl);
+        (unsigned)(tr ? ldq : 1), (int64_t)(tr ? 1 : ldx), tr ? 1 : 0, sub_abl);
 }
 
 void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const double* L, double* x, int nrhs, int ldx,
-                            hipStream_t stream) {
+                            int sub_abl, hipStream_t stream) {
     if (T.ntrees <= 0) return;
     int ngroups, per_wave;
     dim3 grid, block;
@@ -510,7 +510,7 @@ void launch_bsolve_sub_mrhs(const DevicePattern& P, const SubTier& T, const doub
     sub_grid(T, nrhs, ngroups, grid, block, per_wave, lds);
     launch_witnessed<k_bsolve_sub_mrhs, kWBsolveSubMrhs>(grid, block, lds, stream, P.sub_members, P.sub_trees,
         reinterpret_cast<const uint2*>(P.sub_slots), P.sub_out_rows, T.tree0, per_wave, ngroups, L, x, nrhs, 1u,
-        (int64_t)ldx, P.gates.sub_abl);
+        (int64_t)ldx, sub_abl);
 }
 
 // Once per plan: a workgroup of four waves on the largest trees may need more than 64 KB of LDS -- ask for it (up to

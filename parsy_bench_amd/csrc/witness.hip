@@ -1,8 +1,11 @@
-// Kernel witness (kernels.hpp; include/parsy_amd.h, diagnostics): host-side launch counters of the factor and the solve
+// Kernel witness (solve_route.hpp; include/parsy_amd.h, diagnostics): host-side launch counters of the factor and the solve
 // kernels.
 #include <atomic>
 
-#include "kernels.hpp"
+#include <string>
+
+#include "errors.hpp"
+#include "launch.hpp"
 
 namespace parsy {
 
@@ -13,6 +16,10 @@ static const char* const kWitnessNames[kWitnessCount] = {
 #undef PARSY_WITNESS_NAME
 };
 void witness_launch(WitnessKernel k) { g_witness[k].fetch_add(1, std::memory_order_relaxed); }
+void launch_refused(const char* function, WitnessKernel k) {
+    set_last_error(std::string(function) + ": not a kernel of this launch function: " +
+                   (k >= 0 && k < kWitnessCount ? kWitnessNames[k] : "(none)"));
+}
 
 }  // namespace parsy
 

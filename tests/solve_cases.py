@@ -7,8 +7,9 @@ A plain helper module of the suite in the style of shape_cases.py (no fixtures, 
   limits of the ONE-launch kernels, the 512-row chunks of k_bsolve_below, levels of one width class only).  All have
   n <= 1000 and are analysed with shape_cases.ZRELAX.
 * `predict`: the kernels a solve launches, from the launch tables of a host-only plan (parsy_debug_launches), the plan's
-  counters and the gates of executor.hip / the launch functions -- so that test_solve_cases_host.py pins every cell to its
-  path without a GPU.  test_solve_shapes_gpu.py holds the prediction to the kernel witness, cell by cell.
+  counters and the gates -- the tests' independent copy of the library's dispatch (csrc/solve_route.cpp) -- so that
+  test_solve_cases_host.py pins every cell to its path without a GPU.  test_solve_route_host.py compares it with the
+  library's own route (`route`), test_solve_shapes_gpu.py holds both to the kernel witness, cell by cell.
 * `CELLS`: name, shape, the variables read when the plan is built and those read per solve, the number of right-hand
   sides, the direction, the witness entries the cell must launch and those it must not, and the border it exists for.
 
@@ -110,16 +111,16 @@ def set_env(monkeypatch, env):
 # ---------------------------------------------------------------------------
 # the prediction
 # ---------------------------------------------------------------------------
-# predict() is a second copy of the dispatch in executor.hip (plan_solve, plan_backsolve, run_solve, run_range) and in the
-# launch functions launch_solve_small, launch_solve_chain, launch_solve_blocks_mrhs, launch_bsolve_block, launch_solve_one
-# and launch_bsolve_one: a change to a gate or to one of them is made here too (comments there say so).  It cannot drift
-# unnoticed: test_solve_shapes_gpu.py holds it to the witness exactly, and test_solve_cases_host.py reads the field order
-# of parsy::Launch and the defaults of SolveGates from the headers.
+# predict() is the tests' independent copy of the dispatch, which the library holds in one place, csrc/solve_route.cpp: a
+# change to a gate or to a choice there is made here too (a comment there says so).  It cannot drift unnoticed:
+# test_solve_route_host.py compares it with the library's route on every point of a grid without a GPU,
+# test_solve_shapes_gpu.py holds it to the witness exactly, and test_solve_cases_host.py reads the field order of
+# parsy::Launch and the defaults of SolveGates from the headers.
 # parsy::Launch in declaration order (schedule.hpp)
 LAUNCH_FIELDS = ("kind", "first", "count", "level", "side", "wait_level", "form", "rows_only", "ticket", "lds_bytes", "stage",
                  "width", "width_class", "task_first", "task_count")
 KIND, FIRST, COUNT, LEVEL, SIDE, WAIT_LEVEL, FORM, ROWS_ONLY, TICKET, LDS_BYTES, STAGE, WIDTH, WIDTH_CLASS, TASK_FIRST, TASK_COUNT = range(len(LAUNCH_FIELDS))
-# the defaults of SolveGates (kernels.hpp) that _gates mirrors, by the struct's member names
+# the defaults of SolveGates (solve_route.hpp) that _gates mirrors, by the struct's member names
 GATE_DEFAULTS = {"mrhs_min": 6, "chain_mrhs_min": 2, "bmrhs_min": 16, "bmrhs_wide_blocks": 128, "bchain_min_blocks": 128,
                  "small_halves_min": 512, "sub_mrhs_min": 6, "xt_min": 16, "chain_few_chunks": 384}
 BACK_BELOW, SOLVE_SMALL, SOLVE_PANEL, SOLVE_FIXUP, BACK_BLOCK = 4, 5, 6, 7, 8
@@ -141,6 +142,35 @@ def launch_tables(plan):
     return out
 
 
+def _names(call):
+    """The witness names a route export returns: call(kernels, cap) -> number of launches."""
+    from parsy_bench_amd import _native as N
+    lib = N.lib()
+    n = call(None, 0)
+    assert n >= 0, N.last_error()
+    k = np.zeros(max(n, 1), dtype=np.int32)
+    assert call(k.ctypes.data, n) == n
+    return [lib.parsy_debug_kernel_name(int(i)).decode() for i in k[:n]]
+
+
+def route(plan, nrhs, ldx, forward):
+    """The library's own route of a solve (parsy_debug_solve_route, a diagnostic outside the public header): the witness names
+    of its launches in enqueue order, with the gates the environment sets now.  Plans without a device too."""
+    from parsy_bench_amd import _native as N
+    f = N.lib().parsy_debug_solve_route
+    f.restype, f.argtypes = C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    return _names(lambda out, cap: f(plan._h, nrhs, ldx, 0 if forward else 1, out, cap))
+
+
+def route_levels(plan, nrhs, ldx, forward, lev0, lev1, first, last):
+    """... of one step of a solve in steps of levels (parsy_debug_solve_route_levels; the flags of parsy_solve_levels_device)."""
+    from parsy_bench_amd import _native as N
+    f = N.lib().parsy_debug_solve_route_levels
+    f.restype, f.argtypes = C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    flags = (1 if first else 0) | (2 if last else 0) | (0 if forward else 4)
+    return _names(lambda out, cap: f(plan._h, nrhs, ldx, lev0, lev1, flags, out, cap))
+
+
 def _gates(env):
     d = GATE_DEFAULTS
     g = {"mrhs_min": d["mrhs_min"], "chain_mrhs_min": d["chain_mrhs_min"], "bmrhs_min": d["bmrhs_min"], "wide_only": True,
@@ -160,8 +190,7 @@ def _gates(env):
 
 
 def predict(info, tables, plan_env, solve_env, nrhs, forward):
-    """The witness entries a solve launches (a set): executor.hip's plan_solve / plan_backsolve / run_range and the launch
-    functions of the trsv sources, on the launch tables and counters of a plan built under plan_env."""
+    """The witness entries a solve launches (a set), on the launch tables and counters of a plan built under plan_env."""
     g = _gates(solve_env)
     fwd_t, bwd_t = tables
     one = plan_env.get("PARSY_SOLVE_ONE")

@@ -10,7 +10,7 @@ CSRC = ROOT / "parsy_bench_amd" / "csrc"
 SOLVE_SOURCES = "trsv*.hip"
 FACTOR_SOURCES = "chol_kernels.hip"
 
-# the table in its order (kernels.hpp, PARSY_WITNESS_KERNELS): the solve kernel instantiations, then the factor kernels
+# the table in its order (solve_route.hpp, PARSY_WITNESS_KERNELS): the solve kernel instantiations, then the factor kernels
 SOLVE_ENTRIES = [
     "k_solve_tiny<16>", "k_solve_small", "k_solve_small_mrhs<16>", "k_solve_small_mrhs<32>", "k_solve_small_mrhs<64>",
     "k_solve_small_mrhs<64,true>", "k_solve_panel", "k_diag_inverse", "k_solve_chain_w<2>", "k_solve_chain_w<4>",
@@ -43,8 +43,8 @@ def kernel_names(*patterns):
 
 
 def witness_idents():
-    """entry name -> its identifier (kernels.hpp)"""
-    table = re.sub(r"//[^\n]*", "", (CSRC / "kernels.hpp").read_text())
+    """entry name -> its identifier (solve_route.hpp)"""
+    table = re.sub(r"//[^\n]*", "", (CSRC / "solve_route.hpp").read_text())
     return {name: "kW" + ident for ident, name in re.findall(r'X\((\w+),\s*"([^"]+)"\)', table)}
 
 
@@ -90,7 +90,7 @@ def test_every_solve_kernel_has_a_witness_entry():
     bases = {name.split("<")[0] for name in table}
     names = kernel_names()
     missing = sorted(names - bases)
-    assert not missing, f"kernels without a witness entry (kernels.hpp, PARSY_WITNESS_KERNELS): {missing}"
+    assert not missing, f"kernels without a witness entry (solve_route.hpp, PARSY_WITNESS_KERNELS): {missing}"
     stale = sorted(bases - names)
     assert not stale, f"witness entries of no kernel in the sources: {stale}"
 
@@ -126,7 +126,7 @@ def test_no_bare_launch_of_a_witnessed_kernel():
         bare = set(re.findall(BARE, text)) & witnessed
         assert not bare, f"{src.name}: hipLaunchKernelGGL of {sorted(bare)} (use launch_witnessed)"
         assert "<<<" not in text, src.name
-        if src.name not in ("launch.hpp", "witness.hip", "kernels.hpp"):
+        if src.name not in ("launch.hpp", "witness.hip", "solve_route.hpp"):
             assert "witness_launch" not in text, f"{src.name}: witness_launch outside launch_witnessed"
     # (the helper itself: the bump, then the launch of its template argument)
     assert re.search(r"witness_launch\(W\);\s*hipLaunchKernelGGL\(Kernel,", source_text(CSRC / "launch.hpp"))

@@ -38,7 +38,7 @@ def test_names_and_variables_are_real():
 
 def test_prediction_reads_the_headers_right():
     """What solve_cases.predict mirrors of the headers, read from them: the fields of parsy::Launch in declaration order
-    (schedule.hpp: a row of the launch table) and the defaults of SolveGates (kernels.hpp)."""
+    (schedule.hpp: a row of the launch table) and the defaults of SolveGates (solve_route.hpp)."""
     import re
     from test_kernel_witness import CSRC, source_text
     body = re.search(r"struct Launch \{(.*?)\};", source_text(CSRC / "schedule.hpp"), flags=re.S).group(1)
@@ -50,7 +50,7 @@ def test_prediction_reads_the_headers_right():
         [V.BACK_BELOW, V.SOLVE_SMALL, V.SOLVE_PANEL, V.SOLVE_FIXUP, V.BACK_BLOCK]
     forms = dict(re.findall(r"(kForm\w+) = (\d+)", source_text(CSRC / "schedule.hpp")))
     assert [int(forms[k]) for k in ("kFormEach", "kFormChain", "kFormSubtrees")] == [V.EACH, V.CHAIN, V.SUBTREES]
-    gates = re.search(r"struct SolveGates \{(.*?)\};", source_text(CSRC / "kernels.hpp"), flags=re.S).group(1)
+    gates = re.search(r"struct SolveGates \{(.*?)\};", source_text(CSRC / "solve_route.hpp"), flags=re.S).group(1)
     defaults = {k: int(v) for k, v in re.findall(r"int (\w+) = (\d+);", gates)}
     assert {k: defaults.get(k) for k in V.GATE_DEFAULTS} == V.GATE_DEFAULTS, defaults
     assert set(defaults) - set(V.GATE_DEFAULTS) <= {"wait_bias", "sub_abl"}, "a gate of SolveGates that the prediction does not know"

@@ -7,7 +7,8 @@ all the catalogue's variables are cleared, and is held to
 
 * solve_status() == 0, the padding rows and the tail keep their bits;
 * rho_solve <= n + 1 units of u = 2^-53 for every column (shape_cases.py: the measure and the limit);
-* the kernel witness: every entry of cell.kernels launched, none of cell.absent;
+* the kernel witness: every entry of cell.kernels launched, none of cell.absent, and the counts of all entries are
+  exactly those of the library's own route of that solve (solve_cases.route: parsy_debug_solve_route);
 * for the k_solve_chain_w<4> / <2> pairs: the two X agree normwise to SOLVE_TOL.
 
 Between them the cells launch every solve entry of the witness table but k_copy_segments (the last test).
@@ -15,6 +16,8 @@ test_solve_cases_host.py pins every cell to its path without a GPU and proves th
 
 Every measured value is printed (pytest -rP shows it for passing tests) and stands in the assertion messages.
 """
+from collections import Counter
+
 import numpy as np
 import pytest
 
@@ -57,7 +60,8 @@ def _bits(a):
 
 
 def _solve(api, run, cell, scaled, B):
-    """X of one device solve of the cell (the caller has set its variables), the witness of that solve alone."""
+    """X of one device solve of the cell (the caller has set its variables), the witness of that solve alone and the
+    library's route of it (a Counter of witness names)."""
     import torch
     plan, n, nrhs = run["plan"], run["sym"].n, cell.nrhs
     ldx = n + _PAD
@@ -75,7 +79,7 @@ def _solve(api, run, cell, scaled, B):
     body = out[:ldx * nrhs].reshape(nrhs, ldx)
     assert np.array_equal(_bits(body[:, n:]), _bits(np.full((nrhs, _PAD), _SENTINEL))), f"{what}: the padding rows of X were written"
     assert np.array_equal(_bits(out[ldx * nrhs:]), _bits(np.full(_TAIL, _SENTINEL))), f"{what}: written past the last column"
-    return np.ascontiguousarray(body[:, :n].T), seen
+    return np.ascontiguousarray(body[:, :n].T), seen, Counter(V.route(plan, nrhs, ldx, cell.forward))
 
 
 def _check_witness(cell, seen, what):
@@ -117,9 +121,9 @@ def _result(api, monkeypatch, name):
             _RESULTS[name] = _rhs_ones(api, run, cell)
         else:
             B = V.rhs(run["shape"], cell.nrhs)
-            out = {"rho": {}, "seen": {}, "X": {}}
+            out = {"rho": {}, "seen": {}, "X": {}, "route": {}}
             for scaled in (False, True):
-                out["X"][scaled], out["seen"][scaled] = _solve(api, run, cell, scaled, B)
+                out["X"][scaled], out["seen"][scaled], out["route"][scaled] = _solve(api, run, cell, scaled, B)
                 Ld = run[scaled]["Ld"]
                 out["rho"][scaled] = SC.rho_solve(Ld if cell.forward else Ld.T, out["X"][scaled], B)
             _RESULTS[name] = out
@@ -138,6 +142,9 @@ def test_solve_cell(api, monkeypatch, name):
     for scaled in (False, True):
         what = f"{name} ({cell.shape}, nrhs={cell.nrhs}, {cell.direction}) scaled={scaled}"
         _check_witness(cell, got["seen"][scaled], what)
+        if name != "rhs_ones":
+            counts = Counter({k: v for k, v in got["seen"][scaled].items() if v})
+            assert counts == got["route"][scaled], f"{what}: launched {dict(counts)}, the route says {dict(got['route'][scaled])}"
         rho = got["rho"][scaled]
         assert rho.max() <= limit, f"{what}: rho = {rho.max():.4g} (column / row {int(rho.argmax())}) > {limit}; {cell.intent}"
     if cell.pair:
@@ -147,6 +154,54 @@ def test_solve_cell(api, monkeypatch, name):
             err = np.abs(X - Y).max() / max(1.0, np.abs(Y).max())
             print(f"PAIR {name} / {cell.pair} scaled={int(scaled)} err={err:.3e}")
             assert err <= SOLVE_TOL, f"{name} against {cell.pair} scaled={scaled}: {err:.3e}"
+
+
+@pytest.mark.parametrize("nrhs", [1, 3])
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+def test_solve_in_steps_of_levels(api, monkeypatch, direction, nrhs):
+    """tiles_257 through parsy_solve_levels_device in steps of one level: the witness counts summed over the steps are those
+    of the steps' routes (solve_cases.route_levels), and X is the one-call solve's -- bitwise backward, where every sum
+    has one order, and to SOLVE_TOL forward, where the chain's updates arrive by atomics."""
+    import torch
+    cell = V.CELL_BY_NAME["w2_tiles_257"]
+    assert cell.plan_env == V.L0
+    run = _plan(api, monkeypatch, cell)
+    V.set_env(monkeypatch, cell.plan_env)
+    plan, n, forward = run["plan"], run["sym"].n, direction == "forward"
+    ldx = n + _PAD
+    B = V.rhs(run["shape"], nrhs)
+    buf = np.full(ldx * nrhs + _TAIL, _SENTINEL)
+    buf[:ldx * nrhs].reshape(nrhs, ldx)[:, :n] = B.T
+    dev = torch.device("cuda", 0)
+    Ld, Xd, Yd = run[False]["dev"], torch.from_numpy(buf).to(dev), torch.from_numpy(buf).to(dev)
+    (plan.solve_device if forward else plan.backsolve_device)(Ld.data_ptr(), Yd.data_ptr(), nrhs, ldx)
+    torch.cuda.synchronize()
+    assert plan.solve_status() == 0
+    nl = int(plan.solve_levels().max()) + 1
+    assert nl >= 3
+    seen, routed = Counter(), Counter()
+    for k, lev in enumerate(range(nl) if forward else range(nl - 1, -1, -1)):
+        first, last = k == 0, k == nl - 1
+        api.reset_kernel_launches()
+        plan.solve_levels_device(Ld.data_ptr(), Xd.data_ptr(), nrhs, ldx, 0, lev, lev + 1, first, last, backward=not forward)
+        torch.cuda.synchronize()
+        step = Counter({name: v for name, v in api.kernel_launches().items() if v})
+        route = Counter(V.route_levels(plan, nrhs, ldx, forward, lev, lev + 1, first, last))
+        assert step == route, f"level {lev}: launched {dict(step)}, the route says {dict(route)}"
+        seen += step
+        routed += route
+    assert plan.solve_status() == 0
+    print(f"LEVELS {direction} nrhs={nrhs} levels={nl} launched={dict(seen)}")
+    assert seen == routed and sum(seen.values()) > nl
+    X, Y = Xd.cpu().numpy(), Yd.cpu().numpy()
+    if forward:
+        err = np.abs(X - Y).max() / max(1.0, np.abs(Y).max())
+        print(f"LEVELS forward nrhs={nrhs} err={err:.3e}")
+        assert err <= SOLVE_TOL, err
+        body = X[:ldx * nrhs].reshape(nrhs, ldx)
+        assert np.array_equal(_bits(body[:, n:]), _bits(np.full((nrhs, _PAD), _SENTINEL))) and np.array_equal(_bits(X[ldx * nrhs:]), _bits(np.full(_TAIL, _SENTINEL)))
+    else:
+        assert np.array_equal(_bits(X), _bits(Y)), "the backward solve in steps of levels differs from the one-call solve"
 
 
 def test_prediction_is_the_witness(api, monkeypatch):
