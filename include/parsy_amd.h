@@ -105,6 +105,16 @@ int H2LeveledBlockedLsolve_Peeled(int n, size_t* Lp, int* Li, double* Lx, int NN
                                   int parts, int* parPtr, int* partition, int chunk,
                                   int threads);
 
+/* Replace the pruned BCSC forward solve, reference triangularSolve/Triangular_BCSC.h:55: L x = b for the supernodes of
+ * BPSet alone (PBSetSize of them, in any order), numbered as the reference's loop reads them -- supernode i has the
+ * columns sup2col[i - 1] .. sup2col[i] - 1, i = 1 .. supNo.  x is read and written only in the columns of the listed
+ * supernodes.  The list must be closed towards the root of the supernodal etree, as the reach of a right-hand side
+ * (common/Reach.h:31) is: the reference has no defined result for any other list, and such a list is refused.  Returns
+ * 1, or 0 when Lp, Li or x is NULL (as the reference) or, loudly, when the list is refused or the device path could not
+ * run.  NNZ is unused.  Runs PARSY_SPARSE_GINV (below) on a handle whose B and selected rows are those columns. */
+int blockedPrunedLSolve(int n, size_t* Lp, int* Li, double* Lx, int NNZ, size_t* Li_ptr, int* BPSet, int PBSetSize,
+                        int* sup2col, int supNo, double* x);
+
 /* Drop the plans cached by the drop-in operators (frees device memory). */
 void parsy_dropin_reset(void);
 
@@ -754,6 +764,76 @@ int parsy_normal_apply_host(parsy_normal* nrm, int op, const double* fx, const d
 int parsy_lsq_solve_host(parsy_normal* nrm, const double* fx, const double* w, double beta, const double* lValues,
                          const double* c, int ldc, double* x, int ldx, int nrhs, int steps, double* r, int ldr, double* g,
                          int ldg, double* seconds);
+
+/* ---- Solves with sparse right-hand sides for selected rows of the result ------------------------------------------------
+ * CHOLMOD's solve2 with Bset / Xset, and the reference's blockedPrunedLSolve / reach_sn on blocks of right-hand sides.
+ * B is n x nrhs in compressed columns: bp (nrhs + 1 entries from 0, non-decreasing) and bi (rows strictly ascending
+ * within a column) on the host, in the caller's ordering (parsy_plan_set_perm); an empty column is allowed, its column
+ * of X is exactly zero.  xi lists nx distinct rows of the result in the caller's ordering, in any order; NULL: all n rows
+ * (nx is then ignored).  With P the plan's ordering:
+ *   F = the supernodes of the rows of P B and all their ancestors in the supernodal etree: L^-1 P B is zero elsewhere;
+ *   K = the supernodes of the rows of P xi and all their ancestors: those rows of L^-T y need nothing else.
+ * A call reads only the panels of F (forward) and of K (backward): parsy_reach_info.fwd_entries / bwd_entries stored
+ * entries of L, against xsize for the plan's full solves.  Every reach ends at the root: where the top separators hold
+ * most of L the full solve of the plan may well be faster.  The call never falls back by itself; the counts let a caller
+ * choose.
+ * A handle belongs to one plan, one pattern of B and one xi, and is built once: supernodes wider than 256 columns are cut
+ * into pieces of 256 (the last one shorter), a step is a set of pieces with no dependency among them (a supernode's first
+ * piece one step after the last pieces of its children in the set, piece k + 1 one step after piece k; the backward pass
+ * takes the steps of K in reverse), and every vector of a call lives in one compact numbering of the columns of F u K:
+ * nothing a handle holds, on the host or on the device, is of size n, ssize or xsize.  The handle copies the plan's
+ * ordering as it stands: a later parsy_plan_set_perm does not reach it.  The plan is borrowed and must outlive the
+ * handle's calls; the handle's memory is its own and is not in the plan's device_bytes.  Host-only plans (device < 0)
+ * too: only the device call refuses those.
+ * Refused, with parsy_last_error naming the reason (NULL is returned, nothing is allocated): a NULL argument (bi may be
+ * NULL when B has no entry), nrhs < 1, bp not non-decreasing from 0, a row outside 0 .. n - 1, rows of a column not
+ * strictly ascending, a repeated row in xi, nx < 1 with xi given, a plan restricted by parsy_plan_set_active /
+ * _set_active_pieces. */
+typedef struct parsy_reach parsy_reach;
+parsy_reach* parsy_reach_create(parsy_plan* plan, int nrhs, const int* bp, const int* bi, int nx, const int* xi);
+void parsy_reach_destroy(parsy_reach* reach);
+typedef struct parsy_reach_info {
+    int32_t nrhs, nx;
+    int32_t fwd_supernodes, fwd_pieces;   /* of F */
+    int32_t bwd_supernodes, bwd_pieces;   /* of K */
+    int32_t fwd_steps, bwd_steps;
+    int32_t last_op;             /* of the last device call (-1: none yet) */
+    int32_t last_kernels;        /* kernels it enqueued: the load, per step of each pass the triangles and -- where a piece
+                                    of the step has rows below it -- the panels, the gather, the clearing */
+    int64_t fwd_entries;         /* stored entries of L a forward pass over F reads */
+    int64_t bwd_entries;         /* ... a backward pass over K */
+    int64_t xsize;               /* ... the factor holds: what each of the plan's full solves reads */
+    int64_t device_bytes;        /* index and workspaces held by the handle (0 before its first device call) */
+} parsy_reach_info;
+int parsy_reach_get_info(const parsy_reach* reach, parsy_reach_info* info);   /* host-only plans too */
+/* F into fwd (fwd_supernodes entries) and K into bwd (bwd_supernodes entries), ascending; each may be NULL. */
+int parsy_reach_get(const parsy_reach* reach, int32_t* fwd, int32_t* bwd);
+/* Violations of the handle's index (0: sound): both sets closed towards the root, the steps in the order above, every
+ * piece and every panel row in exactly one launch of its pass, the gather lists ascending. */
+long long parsy_reach_check(const parsy_reach* reach);
+#define PARSY_SPARSE_A 0      /* X = (A^-1 B)[xi, :]: forward over F, backward over K */
+#define PARSY_SPARSE_GINV 1   /* X = (L^-1 P B) rows P xi: forward only, over F */
+#define PARSY_SPARSE_GINVT 2  /* X = (P' L^-T P B) rows xi: backward only, over K; entries of B outside K's columns are
+                                 not read */
+/* d_bx: the bp[nrhs] values of B in the order of bi, never written; d_x: nx x nrhs column-major, ldx >= nx, row k the
+ * row xi[k]; d_lValues: the factor in the handle's ordering.  The right-hand sides go in blocks of 8 that share nothing
+ * but the read of L: column q of a call is bitwise what a handle of that column alone gives, a row of a call what a
+ * handle with fewer selected rows gives for it, and entries of B that carry 0.0 change nothing.  Every sum has one order,
+ * fixed by the pattern (occurrences of a row in ascending position of lR, columns of a panel ascending, segments of 1024
+ * rows ascending); kernels are ordered by the stream alone, without flags, tickets or float atomics: two calls give the
+ * same bits.  The plan's own solve schedule is not used and nothing of the plan is written.
+ * The handle's first device call uploads its index and makes its workspaces (all zero between calls: a call ends by
+ * clearing exactly what it wrote); after it a call allocates nothing and waits for nothing, it only enqueues.  One call
+ * per handle at a time.
+ * Refused, with nothing written: a NULL argument (d_bx may be NULL when B has no entry), ldx < nx, an unknown op, a plan
+ * restricted by parsy_plan_set_active / _set_active_pieces, a handle of a host-only plan. */
+int parsy_solve_sparse_device(parsy_reach* reach, const double* d_lValues, const double* d_bx, int op, double* d_x, int ldx,
+                              void* stream);
+/* Host buffers, through the staging layer of the other host calls: the whole factor goes up into the plan's staging
+ * buffer (xsize doubles, as parsy_solve_host does it -- the upload reads all of L even where the solve does not), bx up,
+ * the call above, x back; seconds (may be NULL) = device time.  Synchronous. */
+int parsy_solve_sparse_host(parsy_reach* reach, const double* lValues, const double* bx, int op, double* x, int ldx,
+                            double* seconds);
 
 /* Host-buffer conveniences (H2D + kernels + D2H, synchronous). `seconds`, if
  * non-NULL, receives the device time of the numeric kernels alone. */

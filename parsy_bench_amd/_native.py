@@ -101,7 +101,21 @@ EXPORTED_SYMBOLS = [
     "parsy_normal_pattern", "parsy_normal_create", "parsy_normal_destroy", "parsy_normal_get_info", "parsy_normal_pairs",
     "parsy_normal_check", "parsy_normal_values_device", "parsy_normal_apply_device", "parsy_lsq_solve_device",
     "parsy_normal_values_host", "parsy_normal_apply_host", "parsy_lsq_solve_host",
+    "blockedPrunedLSolve", "parsy_reach_create", "parsy_reach_destroy", "parsy_reach_get_info", "parsy_reach_get",
+    "parsy_reach_check", "parsy_solve_sparse_device", "parsy_solve_sparse_host",
 ]
+
+
+class ReachInfo(C.Structure):
+    _fields_ = [
+        ("nrhs", C.c_int32), ("nx", C.c_int32), ("fwd_supernodes", C.c_int32), ("fwd_pieces", C.c_int32),
+        ("bwd_supernodes", C.c_int32), ("bwd_pieces", C.c_int32), ("fwd_steps", C.c_int32), ("bwd_steps", C.c_int32),
+        ("last_op", C.c_int32), ("last_kernels", C.c_int32), ("fwd_entries", C.c_int64), ("bwd_entries", C.c_int64),
+        ("xsize", C.c_int64), ("device_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class NormalInfo(C.Structure):
@@ -330,6 +344,18 @@ def _declare(lib):
     lsq = [vp, vp, vp, C.c_double, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     lib.parsy_lsq_solve_device.argtypes = lsq
     lib.parsy_lsq_solve_host.argtypes = lsq
+    lib.parsy_reach_create.restype = vp
+    lib.parsy_reach_create.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    lib.parsy_reach_destroy.restype = None
+    lib.parsy_reach_destroy.argtypes = [vp]
+    lib.parsy_reach_get_info.argtypes = [vp, vp]
+    lib.parsy_reach_get.argtypes = [vp, vp, vp]
+    lib.parsy_reach_check.restype = C.c_longlong
+    lib.parsy_reach_check.argtypes = [vp]
+    lib.parsy_solve_sparse_device.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
+    lib.parsy_solve_sparse_host.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
+    lib.blockedPrunedLSolve.restype = C.c_int
+    lib.blockedPrunedLSolve.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]
     lib.parsy_factor_host.argtypes = [vp, vp, vp, vp]
     lib.parsy_solve_host.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.parsy_last_factor_ms.restype = C.c_double

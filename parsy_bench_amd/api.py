@@ -132,6 +132,17 @@ def H2LeveledBlockedLsolve_Peeled(n, Lp, Li, Lx, NNZ, Li_ptr, col2sup, sup2col, 
                                                      N.ptr(pp), N.ptr(pt), chunk, threads))
 
 
+def blockedPrunedLSolve(n, Lp, Li, Lx, NNZ, Li_ptr, BPSet, PBSetSize, sup2col, supNo, x) -> int:
+    """The reference's pruned forward solve (Triangular_BCSC.h:55): L x = b on the supernodes of BPSet alone, numbered
+    1 .. supNo as the reference's loop reads sup2col; x changes only in their columns.  0 (loudly) for a list that is
+    not closed towards the root."""
+    assert x is None or (x.dtype == np.float64 and x.flags["C_CONTIGUOUS"])
+    keep = [None if Lp is None else _sz(Lp), None if Li is None else _i32(Li), _f64(Lx), _sz(Li_ptr), _i32(BPSet),
+            _i32(sup2col)]
+    return int(N.lib().blockedPrunedLSolve(n, N.ptr(keep[0]), N.ptr(keep[1]), N.ptr(keep[2]), int(NNZ), N.ptr(keep[3]),
+                                           N.ptr(keep[4]), int(PBSetSize), N.ptr(keep[5]), supNo, N.ptr(x)))
+
+
 def dropin_reset() -> None:
     N.lib().parsy_dropin_reset()
 
@@ -726,6 +737,18 @@ class Plan:
             raise RuntimeError("parsy_rowmod_get_info failed: " + N.last_error())
         return ri.as_dict()
 
+    def inverse_entries(self, lValues, rows, cols) -> np.ndarray:
+        """The dense len(rows) x len(cols) block A^-1[rows, cols] (caller's ordering) from the factor, through a sparse
+        solve whose right-hand sides are the unit vectors of `cols` and whose selected rows are `rows` (SparseSolve): only
+        the panels those reach are read.  On first use the plan takes sym.Perm as its ordering, as rowdel does."""
+        self._take_perm()
+        cols = _i32(cols).reshape(-1)
+        S = SparseSolve(self, (np.arange(cols.size + 1, dtype=np.int32), cols), rows)
+        try:
+            return S.solve(lValues, np.ones(cols.size), op="A")[0]
+        finally:
+            S.close()
+
     def backsolve_device(self, d_lValues: int, d_x: int, nrhs: int, ldx: int, stream: int = 0) -> None:
         if N.lib().parsy_backsolve_device(self._h, d_lValues, d_x, nrhs, ldx, stream) != 0:
             raise RuntimeError("parsy_backsolve_device failed: " + N.last_error())
@@ -808,6 +831,87 @@ class Plan:
         N.lib().parsy_plan_profile_get(self._h, N.ptr(ms), N.ptr(cnt), C.byref(runs))
         return {"runs": runs.value, "ms": dict(zip(KIND_NAMES, ms.tolist())),
                 "launches": dict(zip(KIND_NAMES, cnt.tolist()))}
+
+
+# ---------------------------------------------------------------------------
+# solves with sparse right-hand sides for selected rows of the result
+# ---------------------------------------------------------------------------
+class SparseSolve:
+    """One plan, one pattern of B and one list of selected rows (parsy_reach).  B_pattern: a (bp, bi) pair or anything
+    with .indptr / .indices in compressed columns (n x nrhs, rows strictly ascending within a column); rows: distinct rows
+    of the result in any order, None for all.  Both in the plan's ordering as it is set (Plan.set_perm; the handle keeps
+    a copy).  A call reads only the panels of the supernodes B reaches (forward) and the rows need (backward); it never
+    falls back to the plan's full solve: info["fwd_entries"] / ["bwd_entries"] against ["xsize"] let a caller choose.
+    Host-only plans (device < 0) too: info, reach, check."""
+
+    OPS = {"A": 0, "GINV": 1, "GINVT": 2}
+
+    def __init__(self, plan: "Plan", B_pattern, rows=None):
+        if isinstance(B_pattern, tuple):
+            bp, bi = B_pattern
+        else:
+            bp, bi = B_pattern.indptr, B_pattern.indices
+        self.bp, self.bi = _i32(bp).reshape(-1), _i32(bi).reshape(-1)
+        self.rows = None if rows is None else _i32(rows).reshape(-1)
+        self.plan = plan
+        self.n = int(plan.sym.n)
+        self.nrhs = int(self.bp.size) - 1
+        self.nx = self.n if self.rows is None else int(self.rows.size)
+        self._h = N.lib().parsy_reach_create(plan._h, self.nrhs, N.ptr(self.bp), N.ptr(self.bi), self.nx, N.ptr(self.rows))
+        if not self._h:
+            raise RuntimeError("parsy_reach_create failed: " + N.last_error())
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            N.lib().parsy_reach_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        """nrhs, nx; fwd_ / bwd_supernodes, _pieces, _steps, _entries; xsize; last_op and last_kernels of the last device
+        call (-1, 0: none yet); device_bytes (0 before the first device call)."""
+        ri = N.ReachInfo()
+        if N.lib().parsy_reach_get_info(self._h, C.byref(ri)) != 0:
+            raise RuntimeError("parsy_reach_get_info failed: " + N.last_error())
+        return ri.as_dict()
+
+    def reach(self):
+        """(F, K): the supernodes of the forward and of the backward reach, ascending."""
+        i = self.info()
+        fwd = np.zeros(max(i["fwd_supernodes"], 1), dtype=np.int32)
+        bwd = np.zeros(max(i["bwd_supernodes"], 1), dtype=np.int32)
+        if N.lib().parsy_reach_get(self._h, N.ptr(fwd), N.ptr(bwd)) != 0:
+            raise RuntimeError("parsy_reach_get failed: " + N.last_error())
+        return fwd[:i["fwd_supernodes"]].copy(), bwd[:i["bwd_supernodes"]].copy()
+
+    def check(self) -> int:
+        return int(N.lib().parsy_reach_check(self._h))
+
+    def solve_device(self, d_lValues: int, d_bx: int, d_x: int, ldx: int, op="A", stream: int = 0) -> None:
+        """d_x (nx x nrhs column-major, ldx >= nx) = the selected rows of A^-1 B ("A"), L^-1 P B ("GINV") or
+        P' L^-T P B ("GINVT"); d_bx: B's values in the order of bi.  Only enqueues (after the handle's first call)."""
+        op = self.OPS[op] if isinstance(op, str) else int(op)
+        if N.lib().parsy_solve_sparse_device(self._h, d_lValues or None, d_bx or None, op, d_x or None, ldx, stream) != 0:
+            raise RuntimeError("parsy_solve_sparse_device failed: " + N.last_error())
+
+    def solve(self, lValues, bx, op="A"):
+        """Host arrays: (X of shape (nx, nrhs), device_seconds); bx holds B's values in the order of bi."""
+        op = self.OPS[op] if isinstance(op, str) else int(op)
+        bx = _f64(bx).reshape(-1)
+        if bx.size != self.bi.size:
+            raise ValueError(f"bx must hold {self.bi.size} values, one per entry of the pattern of B")
+        lv = _f64(lValues)
+        X = np.zeros((self.nx, self.nrhs), order="F")
+        sec = C.c_double(0)
+        if N.lib().parsy_solve_sparse_host(self._h, N.ptr(lv), N.ptr(bx), op, X.ctypes.data_as(C.c_void_p), max(self.nx, 1),
+                                           C.byref(sec)) != 0:
+            raise RuntimeError("parsy_solve_sparse_host failed: " + N.last_error())
+        return np.ascontiguousarray(X), sec.value
 
 
 # ---------------------------------------------------------------------------

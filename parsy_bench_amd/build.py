@@ -18,8 +18,8 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libparsy_amd.so"
 OBJ = PKG / "build"
 
-HOST_SOURCES = ["inspector.cpp", "gen.cpp", "ordering.cpp", "capi_host.cpp", "schedule.cpp", "solve_route.cpp", "dist.cpp", "capi_dist.cpp", "selinv.cpp", "grad.cpp", "apply.cpp", "updown.cpp", "rowmod.cpp", "normal.cpp"]
-HIP_SOURCES = ["executor.hip", "chol_kernels.hip", "trsv_kernels.hip", "trsv_bwd_kernels.hip", "trsv_aux_kernels.hip", "trsv_sub_kernels.hip", "witness.hip", "capi_exec.hip", "capi_hostcalls.hip", "mg.hip", "refine_kernels.hip", "selinv_kernels.hip", "grad_kernels.hip", "cond_kernels.hip", "apply_kernels.hip", "updown_kernels.hip", "rowmod_kernels.hip", "eigs_kernels.hip", "normal_kernels.hip"]
+HOST_SOURCES = ["inspector.cpp", "gen.cpp", "ordering.cpp", "capi_host.cpp", "schedule.cpp", "solve_route.cpp", "dist.cpp", "capi_dist.cpp", "selinv.cpp", "grad.cpp", "apply.cpp", "updown.cpp", "rowmod.cpp", "normal.cpp", "reach.cpp"]
+HIP_SOURCES = ["executor.hip", "chol_kernels.hip", "trsv_kernels.hip", "trsv_bwd_kernels.hip", "trsv_aux_kernels.hip", "trsv_sub_kernels.hip", "witness.hip", "capi_exec.hip", "capi_hostcalls.hip", "mg.hip", "refine_kernels.hip", "selinv_kernels.hip", "grad_kernels.hip", "cond_kernels.hip", "apply_kernels.hip", "updown_kernels.hip", "rowmod_kernels.hip", "eigs_kernels.hip", "normal_kernels.hip", "sparse_solve_kernels.hip"]
 ARCH = "gfx950"
 
 

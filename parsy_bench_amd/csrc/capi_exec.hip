@@ -1031,6 +1031,73 @@ int parsy_lsq_solve_device(parsy_normal* h, const double* d_fx, const double* d_
     return parsy::normal_lsq(h, d_fx, d_w, beta, d_lValues, d_c, ldc, d_x, ldx, nrhs, steps, d_r, ldr, d_g, ldg, stream);
 }
 
+parsy_reach* parsy_reach_create(parsy_plan* pl, int nrhs, const int* bp, const int* bi, int nx, const int* xi) {
+    const char* who = "parsy_reach_create";
+    if (!pl || !bp) {
+        set_last_error(std::string(who) + ": null argument");
+        return nullptr;
+    }
+    if (pl->sn_mask_set || pl->piece_mask_set) {
+        set_last_error(std::string(who) + ": plan is restricted by parsy_plan_set_active / _set_active_pieces");
+        return nullptr;
+    }
+    parsy::ReachIndex I;
+    if (parsy::reach_build(pl->S, parsy::plan_perm_inverse(pl), who, nrhs, bp, bi, nx, xi, I) != 0) return nullptr;
+    parsy_reach* h = new parsy_reach();
+    h->plan = pl;
+    h->device = pl->device;
+    h->I = std::move(I);
+    return h;
+}
+
+void parsy_reach_destroy(parsy_reach* h) {
+    if (!h) return;
+    if (h->dev.on_device) {
+        (void)hipSetDevice(h->device);
+        (void)hipDeviceSynchronize();   // (a call may still read the index)
+    }
+    delete h;
+}
+
+int parsy_reach_get_info(const parsy_reach* h, parsy_reach_info* info) {
+    if (!h || !info) {
+        set_last_error("parsy_reach_get_info: null argument");
+        return -1;
+    }
+    const parsy::ReachIndex& I = h->I;
+    info->nrhs = I.nrhs, info->nx = I.nx;
+    info->fwd_supernodes = (int32_t)I.fwd.sn.size(), info->fwd_pieces = (int32_t)I.fwd.pieces.size();
+    info->bwd_supernodes = (int32_t)I.bwd.sn.size(), info->bwd_pieces = (int32_t)I.bwd.pieces.size();
+    info->fwd_steps = I.fwd.steps(), info->bwd_steps = I.bwd.steps();
+    info->last_op = h->dev.last_op, info->last_kernels = h->dev.last_kernels;
+    info->fwd_entries = I.fwd.entries, info->bwd_entries = I.bwd.entries, info->xsize = I.xsize;
+    info->device_bytes = h->dev.meter.bytes;
+    return 0;
+}
+
+int parsy_reach_get(const parsy_reach* h, int32_t* fwd, int32_t* bwd) {
+    if (!h) {
+        set_last_error("parsy_reach_get: null handle");
+        return -1;
+    }
+    if (fwd) std::copy(h->I.fwd.sn.begin(), h->I.fwd.sn.end(), fwd);
+    if (bwd) std::copy(h->I.bwd.sn.begin(), h->I.bwd.sn.end(), bwd);
+    return 0;
+}
+
+long long parsy_reach_check(const parsy_reach* h) {
+    if (!h) {
+        set_last_error("parsy_reach_check: null handle");
+        return -1;
+    }
+    return parsy::reach_check(h->plan->S, h->I);
+}
+
+int parsy_solve_sparse_device(parsy_reach* h, const double* d_lValues, const double* d_bx, int op, double* d_x, int ldx,
+                              void* stream) {
+    return parsy::reach_solve(h, d_lValues, d_bx, op, d_x, ldx, stream);
+}
+
 void parsy_dropin_reset(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (auto& kv : g_plans) parsy::plan_free(kv.second);
@@ -1104,6 +1171,57 @@ int blockedLsolve(int n, size_t* Lp, int* Li, double* Lx, int NNZ, size_t* Li_pt
                   int* sup2col, int supNo, double* x) {
     (void)NNZ; (void)col2sup;
     return dropin_solve("blockedLsolve", n, Lp, Li, Lx, Li_ptr, sup2col, supNo, x);
+}
+
+int blockedPrunedLSolve(int n, size_t* Lp, int* Li, double* Lx, int NNZ, size_t* Li_ptr, int* BPSet, int PBSetSize,
+                        int* sup2col, int supNo, double* x) {
+    (void)NNZ;
+    const char* who = "blockedPrunedLSolve";
+    if (!Lp || !Li || !x) return 0;  // reference: Triangular_BCSC.h:66
+    auto fail = [&](const std::string& what) {
+        if (!what.empty()) set_last_error(std::string(who) + ": " + what);
+        loud(who);
+        return 0;
+    };
+    if (!Lx || !Li_ptr || !sup2col || PBSetSize < 0 || (PBSetSize > 0 && !BPSet)) return fail("null or negative argument");
+    // the list, 0-based and ascending
+    std::vector<int> list;
+    for (int k = 0; k < PBSetSize; ++k) {
+        if (BPSet[k] < 1 || BPSet[k] > supNo)
+            return fail("supernode " + std::to_string(BPSet[k]) + " of the list is outside 1 .. supNo");
+        list.push_back(BPSet[k] - 1);
+    }
+    std::sort(list.begin(), list.end());
+    if (std::adjacent_find(list.begin(), list.end()) != list.end()) return fail("a supernode is listed twice");
+    if (list.empty()) return 1;
+    // closed towards the root: the parent of a supernode is the supernode of its first row below the diagonal block
+    // (tree_from_pattern), read here for the listed ones alone
+    for (int s : list) {
+        const size_t w = (size_t)(sup2col[s + 1] - sup2col[s]), b0 = Li_ptr[sup2col[s]], b1 = Li_ptr[sup2col[s + 1]];
+        if (b1 - b0 <= w) continue;
+        const int par = (int)(std::upper_bound(sup2col, sup2col + supNo + 1, Li[b0 + w]) - sup2col) - 1;
+        if (!std::binary_search(list.begin(), list.end(), par))
+            return fail("the list is not closed towards the root: supernode " + std::to_string(s + 1) + " is listed, its parent " +
+                        std::to_string(par + 1) + " is not");
+    }
+    parsy_plan* pl = cached_solve_plan(n, supNo, Lp, Li, Li_ptr, sup2col);
+    if (!pl) return fail("");
+    std::unique_lock<std::mutex> use(pl->use_mu);
+    // B and the selected rows: every column of the listed supernodes
+    std::vector<int> rows;
+    for (int s : list)
+        for (int j = sup2col[s]; j < sup2col[s + 1]; ++j) rows.push_back(j);
+    const int nr = (int)rows.size();
+    const int bp[2] = {0, nr};
+    std::vector<double> b((size_t)nr), out((size_t)nr);
+    for (int k = 0; k < nr; ++k) b[(size_t)k] = x[rows[(size_t)k]];
+    parsy_reach* h = parsy_reach_create(pl, 1, bp, rows.data(), nr, rows.data());
+    if (!h) return fail("");
+    const int rc = parsy_solve_sparse_host(h, Lx, b.data(), PARSY_SPARSE_GINV, out.data(), nr, nullptr);
+    parsy_reach_destroy(h);
+    if (rc != 0) return fail("");
+    for (int k = 0; k < nr; ++k) x[rows[(size_t)k]] = out[(size_t)k];
+    return 1;
 }
 
 int leveledBlockedLsolve(int n, size_t* Lp, int* Li, double* Lx, int NNZ, size_t* Li_ptr,

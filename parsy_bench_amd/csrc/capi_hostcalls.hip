@@ -694,4 +694,33 @@ int parsy_lsq_solve_host(parsy_normal* h, const double* fx, const double* w, dou
     return 0;
 }
 
+// The factor goes through the plan's staging buffer like every solve's; B's values and the selected rows stage in
+// buffers of their own, freed on return.
+int parsy_solve_sparse_host(parsy_reach* h, const double* lValues, const double* bx, int op, double* x, int ldx,
+                            double* seconds) {
+    const char* who = "parsy_solve_sparse_host";
+    if (parsy::reach_check_args(h, who, lValues, bx, op, x, ldx) != 0) return -1;
+    parsy_plan* pl = h->plan;
+    if (parsy::check_plan(pl, who, parsy::kNeedsDevice) != 0) return -1;
+    const int nx = h->I.nx, nrhs = h->I.nrhs;
+    const int64_t nnz = (int64_t)h->I.bcol.size();
+    PARSY_HIP(hipSetDevice(pl->device));
+    PARSY_HIP(stage(pl, false, 0));
+    PARSY_HIP(hipMemcpy(pl->h_L_dev.data(), lValues, (size_t)pl->S.xsize * 8, hipMemcpyHostToDevice));
+    Scratch sc;
+    double* d_bx = sc.upload(bx, nnz, true);
+    double* d_x = sc.upload(nullptr, (int64_t)nx * nrhs, false);
+    if (!d_bx || !d_x || !sc.timer.start()) {
+        set_last_error(std::string(who) + ": device buffers could not be made");
+        return -1;
+    }
+    if (parsy_solve_sparse_device(h, pl->h_L_dev.data(), d_bx, op, d_x, nx, nullptr) != 0) return -1;
+    if (!sc.timer.stop(seconds)) {
+        set_last_error(std::string(who) + ": timing the call failed");
+        return -1;
+    }
+    PARSY_HIP(hipMemcpy2D(x, (size_t)ldx * 8, d_x, (size_t)nx * 8, (size_t)nx * 8, nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

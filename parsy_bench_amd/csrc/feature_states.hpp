@@ -1,11 +1,12 @@
 // The device states of the features whose host schedules are plain C++ (selinv.hpp, grad.hpp, apply.hpp, updown.hpp,
-// rowmod.hpp, eigs.hpp, normal.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
+// rowmod.hpp, eigs.hpp, normal.hpp, reach.hpp: those headers are read by host-only translation units too, these structs own device memory).  A plan holds
 // each only once one of the feature's device calls has run.
 #pragma once
 #include "apply.hpp"
 #include "device_buffer.hpp"
 #include "grad.hpp"
 #include "normal.hpp"
+#include "reach.hpp"
 #include "rowmod.hpp"
 #include "selinv.hpp"
 #include "updown.hpp"
@@ -151,7 +152,34 @@ struct NormalState {
     DeviceBuf<double> ws{&meter};     // n x nrhs + m x nrhs of parsy_lsq_solve_device
 };
 
+// Device state of a sparse-solve handle (reach.hpp, sparse_solve_kernels.hip): made by the handle's first device call.
+struct ReachState {
+    ByteMeter meter;                  // parsy_reach_info.device_bytes: everything here (a handle's memory is its own: not in
+                                      // the plan's figure)
+    bool on_device = false;           // set when the index and the three workspaces exist
+    DevicePool fixed{&meter};
+    SparsePiece *d_fpieces = nullptr, *d_bpieces = nullptr;
+    int32_t *d_fwork = nullptr, *d_bwork = nullptr, *d_cmap = nullptr, *d_bcol = nullptr, *d_bcomp = nullptr,
+            *d_xcomp = nullptr;
+    int64_t *d_gptr = nullptr, *d_gpos = nullptr;
+    uint8_t *d_colmask = nullptr, *d_entmask = nullptr;
+    // per block of kSparseBlock right-hand sides, the columns of a row contiguous; all zero between calls
+    double* d_y = nullptr;            // ncomp rows: b, then y, then x in the compact numbering
+    double* d_t = nullptr;            // nent rows: what the panels of F subtract from the rows below them
+    double* d_p = nullptr;            // npart rows: the partials of the backward panels
+    int last_op = -1, last_kernels = 0;   // of the last device call (-1: none yet)
+};
+
 }  // namespace parsy
+
+// A handle: one plan, one pattern of B, one list of selected rows.  The plan is borrowed and must outlive every call of
+// the handle.
+struct parsy_reach {
+    parsy_plan* plan = nullptr;
+    int device = -1;                  // the plan's (kept: parsy_reach_destroy may run after the plan is gone)
+    parsy::ReachIndex I;
+    parsy::ReachState dev;
+};
 
 // A handle: one plan, one pattern of F.  The plan is borrowed and must outlive every device call of the handle.
 struct parsy_normal {
