@@ -675,7 +675,6 @@ __device__ __noinline__ void invert_and_trsm(lds_f64* __restrict__ tile, lds_f64
 static constexpr int kKC = 16;        // k extent of one chunk of an update stream
 static constexpr int kInFlightChain = 4;  // chunks in flight per wave (operands prefetched into registers)
 static constexpr int kInFlightTiles = 3;  // ... in the TILES launch: fewer registers, three workgroups per CU
-static constexpr unsigned long long kSpinTicks = 200000000ull;  // 2 s of the 100 MHz wall clock
 
 // One workgroup per 64x64 tile of a panel, one wave per 32x32 sub-tile, and the four waves run
 // their update streams independently (no workgroup barrier until the stream is finished).  A
@@ -1043,13 +1042,11 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
     };
     auto wait_flags = [&](int f0, int f1) -> bool {  // workgroup-wide bounded wait for two flags
         if (tid == 0) {
-            const unsigned long long t0 = wall_clock64();
-            int ok = 1, spins = 0;
+            BoundedWait wait;
+            int ok = 1;
             while (__hip_atomic_load(&tflags[f0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch ||
                    __hip_atomic_load(&tflags[f1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-                if ((++spins & 15) == 0 &&
-                    (wall_clock64() - t0 > kSpinTicks ||
-                     __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                if (wait.expired(info)) {
                     ok = 0;
                     break;
                 }
@@ -1058,7 +1055,7 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
             s_ok = ok;
         }
         __syncthreads();
-        if (!s_ok && tid == 0) atomicMin(info, -1);  // status < 0: a wait timed out / was abandoned
+        if (!s_ok && tid == 0) wait_failed(info);
         return s_ok != 0;
     };
     double* __restrict__ invd = s_invd;
@@ -1147,14 +1144,12 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             };
             auto ensure_ready = [&](int k) {  // block (bounded) until block column k can be read
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                const BoundedWait wait;
+                int spins = 0;   // (counted here, at the loop's end: the sleep policy reads it before the increment)
                 while (kready <= k) {
                     extend_ready();
                     if (kready > k) break;
-                    if ((spins & 15) == 15 &&
-                        (wall_clock64() - t0 > kSpinTicks ||
-                         __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                    if ((spins & 15) == 15 && wait.expired_now(info)) {
                         gave_up = true;     // status < 0 below; go on with whatever is there so that no barrier is missed
                         kready = n_int;
                         break;
@@ -1257,7 +1252,7 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
             }
         }
 #endif
-        if (gave_up) atomicMin(info, -1);
+        if (gave_up) wait_failed(info);
         if (prep_b || prep_c) {
             // prepared for the walker: every update except the walker's own is in; it goes to the panel
             // and is announced with the tile's PREP flag
@@ -1420,14 +1415,11 @@ __device__ __forceinline__ void tile_task(LdsT& S, const int task, const SnDesc*
             {
                 // every wave waits for the two prepared tiles itself (bounded) and then loads its
                 // quadrants: no workgroup barrier between the poll and the loads
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;
                 while (__hip_atomic_load(&tflags[nflags + f_b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch ||
                        __hip_atomic_load(&tflags[nflags + f_c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-                    if ((++spins & 15) == 0 &&
-                        (wall_clock64() - t0 > kSpinTicks ||
-                         __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
-                        atomicMin(info, -1);  // status < 0; go on (with whatever is there) so that nobody hangs
+                    if (wait.expired(info)) {
+                        wait_failed(info);  // go on (with whatever is there) so that nobody hangs
                         break;
                     }
                     __builtin_amdgcn_s_sleep(2);

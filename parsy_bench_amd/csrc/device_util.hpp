@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "device_wait.hpp"
 #include "schedule.hpp"
 
 namespace parsy {

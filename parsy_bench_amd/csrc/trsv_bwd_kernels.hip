@@ -160,9 +160,8 @@ __global__ __launch_bounds__(kThreads) void k_bsolve_block(const SnDesc* __restr
                     }
                     // x of block I: every lane polls its own row's values (the data is the flag); bounded, and
                     // one timeout (status word) ends every wait of the solve
-                    const unsigned long long t0 = wall_clock64();
+                    BoundedWait wait;
                     bool ok = true;
-                    int spins = 0;
                     double xk[NQ];
                     for (;;) {
                         bool in = true;
@@ -177,16 +176,14 @@ __global__ __launch_bounds__(kThreads) void k_bsolve_block(const SnDesc* __restr
                             xk[q] = __longlong_as_double(b);
                         }
                         if (__all(in && wait_bias == 0)) break;
-                        if ((++spins & 15) == 0 &&
-                            (wall_clock64() - t0 > kSolveSpinTicks ||
-                             __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                        if (wait.expired(info)) {
                             ok = false;
                             break;
                         }
                         __builtin_amdgcn_s_sleep(1);
                     }
                     if (!ok) {
-                        if (lane == 0) atomicMin(info, -1);
+                        if (lane == 0) wait_failed(info);
                         break;  // (the result is wrong and reported; nobody may hang)
                     }
                     {
@@ -472,8 +469,7 @@ __global__ __launch_bounds__(kThreads, QG == 4 ? 1 : 2) void k_bsolve_block_mrhs
                         av[st][g] = (kk[st] < w && aok[g]) ? a : 0.0;
                     }
                 }
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;   // (of the watch and the full poll together)
                 // Only the block right above this one is on the critical path of the chain.  A workgroup further up
                 // would poll for a long time, with 16 loads per lane and round, next to hundreds of others on the
                 // same lines (the top separator: 313 workgroups): it first watches ONE value of the block lazily
@@ -485,16 +481,14 @@ __global__ __launch_bounds__(kThreads, QG == 4 ? 1 : 2) void k_bsolve_block_mrhs
                         reinterpret_cast<const long long*>(xscratch + (int64_t)q0 * ldx + D.c0 + kw);
                     while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed ||
                            wait_bias != 0) {
-                        if ((++spins & 15) == 0 &&
-                            (wall_clock64() - t0 > kSolveSpinTicks ||
-                             __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                        if (wait.expired(info)) {
                             ok = false;
                             break;
                         }
                         __builtin_amdgcn_s_sleep(48);
                     }
                     if (!ok) {
-                        if (lane == 0) atomicMin(info, -1);
+                        if (lane == 0) wait_failed(info);
                         break;
                     }
                 }
@@ -513,16 +507,14 @@ __global__ __launch_bounds__(kThreads, QG == 4 ? 1 : 2) void k_bsolve_block_mrhs
                             bv[st][g] = __longlong_as_double(b);
                         }
                     if (__all(in && wait_bias == 0)) break;
-                    if ((++spins & 15) == 0 &&
-                        (wall_clock64() - t0 > kSolveSpinTicks ||
-                         __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                    if (wait.expired(info)) {
                         ok = false;
                         break;
                     }
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (!ok) {
-                    if (lane == 0) atomicMin(info, -1);
+                    if (lane == 0) wait_failed(info);
                     break;   // (the result is wrong and reported; nobody may hang)
                 }
 #pragma unroll
@@ -798,8 +790,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                         av[st][g] = (kk[st] < w && aok[g]) ? a : 0.0;
                     }
                 }
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;   // (of the watch and the full poll together)
                 // Only the block right above this one is on the critical path of the chain.  A workgroup further up
                 // would poll for a long time, with 16 loads per lane and round, next to hundreds of others on the
                 // same lines (the top separator: 313 workgroups): it first watches ONE value of the block lazily
@@ -811,16 +802,14 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                         reinterpret_cast<const long long*>(xscratch + (int64_t)q0 * ldx + D.c0 + kw);
                     while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed ||
                            wait_bias != 0) {
-                        if ((++spins & 15) == 0 &&
-                            (wall_clock64() - t0 > kSolveSpinTicks ||
-                             __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                        if (wait.expired(info)) {
                             ok = false;
                             break;
                         }
                         __builtin_amdgcn_s_sleep(48);
                     }
                     if (!ok) {
-                        if (lane == 0) atomicMin(info, -1);
+                        if (lane == 0) wait_failed(info);
                         break;
                     }
                 }
@@ -839,16 +828,14 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                             bv[st][g] = __longlong_as_double(b);
                         }
                     if (__all(in && wait_bias == 0)) break;
-                    if ((++spins & 15) == 0 &&
-                        (wall_clock64() - t0 > kSolveSpinTicks ||
-                         __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
+                    if (wait.expired(info)) {
                         ok = false;
                         break;
                     }
                     __builtin_amdgcn_s_sleep(1);
                 }
                 if (!ok) {
-                    if (lane == 0) atomicMin(info, -1);
+                    if (lane == 0) wait_failed(info);
                     break;   // (the result is wrong and reported; nobody may hang)
                 }
 #pragma unroll
@@ -903,16 +890,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                 const double* __restrict__ xq = xscratch + qoff;
                 bool ok = true;
                 auto take_x = [&](int I, bool lazy, double (&bv)[16]) __attribute__((always_inline)) {
-                    const unsigned long long t0 = wall_clock64();
-                    int spins = 0;
-                    auto give_up = [&]() {
-                        return (++spins & 15) == 0 && (wall_clock64() - t0 > kSolveSpinTicks ||
-                                                       __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0);
-                    };
+                    BoundedWait wait;   // (of the watch and the full poll together)
                     if (lazy) {   // (a block further up: watch ONE value first -- the top separator has 313 workgroups polling)
                         const long long* __restrict__ watch = reinterpret_cast<const long long*>(xq + min(I * kTile + 63, w - 1));
                         while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed || wait_bias != 0) {
-                            if (give_up()) {
+                            if (wait.expired(info)) {
                                 ok = false;
                                 break;
                             }
@@ -931,7 +913,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                             bv[st] = __longlong_as_double(b);
                         }
                         if (__all(in && wait_bias == 0)) break;
-                        if (give_up()) ok = false;
+                        if (wait.expired(info)) ok = false;
                         else __builtin_amdgcn_s_sleep(1);
                     }
                 };
@@ -958,7 +940,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_bsolve_chain_mrhs(const SnDesc*
                     BLK_STAMP(6);
                     take_x(pd.jb + 1, false, bv);
                     if (!ok) {
-                        if (lane == 0) atomicMin(info, -1);
+                        if (lane == 0) wait_failed(info);
                         return;
                     }
                     BLK_STAMP(0);
@@ -1320,20 +1302,6 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_bsolve_chain_w(const SnDes
     const int nbc = (w + kTile - 1) / kTile;
     const double* __restrict__ G = L + D.px;
     const int32_t* __restrict__ ri = rows + D.pi;
-    auto gave_up = [&](unsigned long long t0, int& spins) {
-        if ((++spins & 15) != 0) return false;
-        return wall_clock64() - t0 > kSolveSpinTicks ||
-               __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0;
-    };
-    auto wait_lds = [&](int* flag, int want) {
-        const unsigned long long t0 = wall_clock64();
-        int spins = 0;
-        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want || wait_bias != 0) {
-            if (gave_up(t0, spins)) return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        return true;
-    };
     auto inv_at = [&](int c) { return lane >= c ? c * kTile - c * (c - 1) / 2 + (lane - c) : kInvPacked; };
     if (qw == 0) {
         // inverse diagonal block -> LDS: lane = row, column c of the inverse from row c on
@@ -1394,21 +1362,20 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_bsolve_chain_w(const SnDes
             double xk = 0.0;
             if (I <= pd.jb) {
                 // a higher block of this workgroup: LDS
-                if (!wait_lds(&s_ready[pd.jb - I], 1)) {
-                    if (lane == 0) atomicMin(info, -1);   // (the result is wrong and reported; nobody may hang)
+                if (!wait_lds_counter(&s_ready[pd.jb - I], 1, wait_bias, info)) {
+                    if (lane == 0) wait_failed(info);   // (the result is wrong and reported; nobody may hang)
                     return;
                 }
                 xk = s_pub[pd.jb - I][lane];
             } else {
                 const long long* __restrict__ src = reinterpret_cast<const long long*>(xscratch + D.c0) + k;
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;
                 long long bits = 0;
                 for (;;) {
                     bits = k < w ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
                     if (__all(bits != kXArmed && wait_bias == 0)) break;
-                    if (gave_up(t0, spins)) {
-                        if (lane == 0) atomicMin(info, -1);
+                    if (wait.expired(info)) {
+                        if (lane == 0) wait_failed(info);
                         return;
                     }
                     if (I <= pd.jb + 2) __builtin_amdgcn_s_sleep(1);   // (the blocks right above: the critical path)
@@ -1447,8 +1414,8 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_bsolve_chain_w(const SnDes
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) __hip_atomic_fetch_add(&s_sums_in[b], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (qw != 0) return;
-    if (!wait_lds(&s_sums_in[b], kTile / kBackCols)) {
-        if (lane == 0) atomicMin(info, -1);
+    if (!wait_lds_counter(&s_sums_in[b], kTile / kBackCols, wait_bias, info)) {
+        if (lane == 0) wait_failed(info);
         return;
     }
     // ---- x_blk = inv(L_bb)' (y - t): x_c = sum_{k >= c} inv(L_bb)[k][c] (y_k - t_k); lane c walks its column of

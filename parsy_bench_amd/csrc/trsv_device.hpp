@@ -9,7 +9,6 @@
 namespace parsy {
 
 static constexpr int kThreads = 256;
-static constexpr unsigned long long kSolveSpinTicks = 200000000ull;  // 2 s of the 100 MHz wall clock (as the factorization's waits)
 static constexpr int kRhsM = 64;        // right-hand sides per pass
 static constexpr int kLdXm = kRhsM + 16;  // row stride of the staged x_jb / t_jb (doubles): conflict-free operand reads
 

@@ -694,20 +694,6 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
         }
     };
     auto inv_at = [&](int c) { return lane >= c ? c * kTile - c * (c - 1) / 2 + (lane - c) : kInvPacked; };
-    auto gave_up = [&](unsigned long long t0, int& spins) {   // bounded waits: one timeout ends every wait of the solve
-        if ((++spins & 15) != 0) return false;
-        return wall_clock64() - t0 > kSolveSpinTicks ||
-               __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0;
-    };
-    auto wait_lds = [&](int* flag, int want) {   // a counter of this workgroup's LDS
-        const unsigned long long t0 = wall_clock64();
-        int spins = 0;
-        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want || wait_bias != 0) {
-            if (gave_up(t0, spins)) return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        return true;
-    };
     if (is_diag && p == 0) {
         // inverse diagonal block -> LDS (off the critical path: the wave starts well before its turn)
         const double* __restrict__ src = dinv + (int64_t)(D.dslot + row0 / kTile) * (kTile * kTile);
@@ -725,8 +711,8 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
         const double* __restrict__ xb = xs;
         if (jb >= jb_wg) {
             // ---- x_jb comes from a wave of this workgroup: LDS
-            if (!wait_lds(&s_ready[jb - jb_wg], 1)) {
-                if (lane == 0) atomicMin(info, -1);   // (the result is wrong and reported; nobody may hang)
+            if (!wait_lds_counter(&s_ready[jb - jb_wg], 1, wait_bias, info)) {
+                if (lane == 0) wait_failed(info);   // (the result is wrong and reported; nobody may hang)
                 return;
             }
             xb = s_pub[jb - jb_wg];
@@ -734,13 +720,12 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
             // ---- x_jb comes from another workgroup: lane c polls value c of the armed buffer
             const long long* __restrict__ src = reinterpret_cast<const long long*>(xscratch + D.c0 + cb) + lane;
             long long bits = 0;
-            const unsigned long long t0 = wall_clock64();
-            int spins = 0;
+            BoundedWait wait;
             for (;;) {
                 bits = lane < wbk ? __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
                 if (__all(bits != kXArmed && wait_bias == 0)) break;
-                if (gave_up(t0, spins)) {
-                    if (lane == 0) atomicMin(info, -1);
+                if (wait.expired(info)) {
+                    if (lane == 0) wait_failed(info);
                     return;
                 }
                 // the rows right below the diagonal wait for the newest x: the critical path; the rows further
@@ -772,8 +757,8 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_solve_chain_w(const SnDesc
             __builtin_amdgcn_wave_barrier();
             if (lane == 0) __hip_atomic_fetch_add(&s_parts_in[rb], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         } else {
-            if (!wait_lds(&s_parts_in[rb], G - 1)) {
-                if (lane == 0) atomicMin(info, -1);
+            if (!wait_lds_counter(&s_parts_in[rb], G - 1, wait_bias, info)) {
+                if (lane == 0) wait_failed(info);
                 return;
             }
             double others = 0.0;
@@ -870,11 +855,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
     const int r = D.r, w = D.w;
     const int nbc = (w + kTile - 1) / kTile;
     const double* __restrict__ G = L + D.px;
-    // all lanes of a wave: true when every value of `vals` differs from the armed pattern
-    auto give_up = [&](unsigned long long t0, int& spins) {
-        return (++spins & 15) == 0 && (wall_clock64() - t0 > kSolveSpinTicks ||
-                                       __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0);
-    };
+    // the status word as the waits below read it.  (A local of the kernel, which the take_x lambdas capture by reference
+    // as they captured the former give_up lambda: with `info` captured directly the compiler numbers the registers
+    // of this kernel differently -- tools/asm_cmp.sh, profiles/wait_evidence.md.)
+    const int* const status = info;
 
     if (pd.row0 < 0) {
         // ================= a block column of the triangle =================
@@ -960,12 +944,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                 }
                 bool ok = true;
                 auto take_x = [&](int k, bool lazy, double (&bv)[16]) __attribute__((always_inline)) {
-                    const unsigned long long t0 = wall_clock64();
-                    int spins = 0;
+                    BoundedWait wait;
                     if (lazy) {
                         const long long* __restrict__ watch = reinterpret_cast<const long long*>(xq + (k * kTile + 63) * sr);
                         while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed || wait_bias != 0) {
-                            if (give_up(t0, spins)) {
+                            if (wait.expired(status)) {
                                 ok = false;
                                 break;
                             }
@@ -982,7 +965,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                             bv[st] = qok ? __longlong_as_double(b) : 0.0;
                         }
                         if (__all((in || !qok) && wait_bias == 0)) break;
-                        if (give_up(t0, spins)) ok = false;
+                        if (wait.expired(status)) ok = false;
                         else __builtin_amdgcn_s_sleep(1);
                     }
                 };
@@ -1005,7 +988,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                 }
                 // (a hand-off that timed out is reported; the waves leave TOGETHER, behind the barrier)
                 if (!ok) {
-                    if (lane == 0) atomicMin(info, -1);
+                    if (lane == 0) wait_failed(info);
                     s_ok = 0;
                 }
                 // T' = B - sums -> LDS as [row][q] (every wave reads the rows up to its own)
@@ -1023,7 +1006,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                     double bv[16];
                     take_x(jb - 1, false, bv);
                     if (!ok) {
-                        if (lane == 0) atomicMin(info, -1);
+                        if (lane == 0) wait_failed(info);
                         s_ok = 0;
                     }
                     double4_t m0 = {0, 0, 0, 0}, m1 = {0, 0, 0, 0};
@@ -1069,12 +1052,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
             // X_k (this wave's 16 right-hand sides, rows 4 st + kq) as soon as it is there; lazy: a block that is not the
             // one right before this one first watches ONE value, then goes on to the full poll (normally satisfied at once)
             auto take_x = [&](int k, bool lazy, double (&bv)[16]) __attribute__((always_inline)) {
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;
                 if (lazy) {
                     const long long* __restrict__ watch = reinterpret_cast<const long long*>(xq + (k * kTile + 63) * sr);
                     while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed || wait_bias != 0) {
-                        if (give_up(t0, spins)) {
+                        if (wait.expired(status)) {
                             ok = false;
                             break;
                         }
@@ -1091,7 +1073,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                         bv[st] = qok ? __longlong_as_double(b) : 0.0;
                     }
                     if (__all((in || !qok) && wait_bias == 0)) break;
-                    if (give_up(t0, spins)) ok = false;
+                    if (wait.expired(status)) ok = false;
                     else __builtin_amdgcn_s_sleep(1);
                 }
             };
@@ -1117,7 +1099,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                         acc[rg] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[st][rg], bv[st], acc[rg], 0, 0, 0);
             }
             if (!ok) {   // a hand-off timed out: reported; this block's x stays armed, its waiters give up on the status word
-                if (lane == 0) atomicMin(info, -1);
+                if (lane == 0) wait_failed(info);
                 return;
             }
             // T' = B - sum: k step st = 4 rg + v of the product with the inverse block
@@ -1145,7 +1127,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                 double bv[16];
                 take_x(jb - 1, false, bv);
                 if (!ok) {
-                    if (lane == 0) atomicMin(info, -1);
+                    if (lane == 0) wait_failed(info);
                     return;
                 }
                 BLK_STAMP(0);
@@ -1230,8 +1212,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
             const int cb = jb * kTile, wbk = min(kTile, w - cb);
             __syncthreads();  // ts of the previous block column is free
             {   // thread (c, q) = (tid & 63, (tid >> 6) + 4 u) -- or, X row-major, ((tid >> 6) + 4 u, tid & 63): 16 values each
-                const unsigned long long t0 = wall_clock64();
-                int spins = 0;
+                BoundedWait wait;
                 const int lo = tid & 63, hi = tid >> 6;
                 double xv[kRhsM / 4];
                 bool ok = true;
@@ -1242,7 +1223,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                     const long long* __restrict__ watch =
                         reinterpret_cast<const long long*>(xscratch + (D.c0 + cb + cw) * sr + (q0 + qw) * sq);
                     while (__hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kXArmed || wait_bias != 0) {
-                        if (give_up(t0, spins)) {
+                        if (wait.expired(status)) {
                             ok = false;
                             break;
                         }
@@ -1262,7 +1243,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                             xv[u] = __longlong_as_double(b);
                         }
                         if (in) break;
-                        if (give_up(t0, spins)) ok = false;
+                        if (wait.expired(status)) ok = false;
                         else __builtin_amdgcn_s_sleep(1);
                     }
                 } else {
@@ -1270,7 +1251,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_solve_blocks_mrhs(const SnDesc*
                     for (int u = 0; u < kRhsM / 4; ++u) xv[u] = 0.0;
                 }
                 if (!ok) {
-                    atomicMin(info, -1);
+                    wait_failed(info);
                     s_ok = 0;
                 }
 #pragma unroll
@@ -1428,18 +1409,16 @@ void launch_solve_chain(const DevicePattern& P, WitnessKernel k, int first, int 
 // launches' (2 s, status -1, nobody hangs).
 __device__ __forceinline__ double one_poll(const double* p, int* info, int wait_bias, bool& ok) {
     const long long* src = reinterpret_cast<const long long*>(p);
-    const unsigned long long t0 = wall_clock64();
-    int spins = 0;
+    BoundedWait wait;
     for (;;) {
         const long long b = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (b != kXArmed && wait_bias == 0) return __longlong_as_double(b);
-        if ((++spins & 15) == 0 && (wall_clock64() - t0 > kSolveSpinTicks ||
-                                    __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0)) {
-            atomicMin(info, -1);   // (the result is wrong and reported)
+        if (wait.expired(info)) {
+            wait_failed(info);   // (the result is wrong and reported)
             ok = false;
             return 0.0;
         }
-        if (spins < 8) __builtin_amdgcn_s_sleep(1);
+        if (wait.spins < 8) __builtin_amdgcn_s_sleep(1);
         else __builtin_amdgcn_s_sleep(8);   // (the late ones poll at leisure)
     }
 }

@@ -11,7 +11,8 @@ numbers of .Ltmp labels.  Lines with the source-text hash (__hip_cuid_), .file a
 symbol) over the whole tree: one that moves between files counts as unchanged, as a kernel does.  Where two files of a
 tree define the same kernel (a template of a shared header), the first definition stands for it.
 Exit status 0 only if no kernel is in one tree alone, none differs (between the trees, or between two files of one tree
-that both define it) and those sets are equal."""
+that both define it) and those sets are equal.  A kernel whose body alone differs and holds the same normalised lines in
+another order is marked as such (it still counts as different)."""
 import difflib
 import os
 import re
@@ -143,9 +144,11 @@ def main():
             same += 1
         if ka[k]["file"] != kb[k]["file"]:
             moved.setdefault((ka[k]["file"], kb[k]["file"]), []).append(k)
-    print(f"kernels that differ: {len(differ)}")
+    # (a body that differs alone, with the same lines in another order: nothing added or removed, labels included)
+    reordered = [k for k, bad in differ if bad == ["body"] and sorted(ka[k]["body"]) == sorted(kb[k]["body"])]
+    print(f"kernels that differ: {len(differ)}, of them same instructions in another order: {len(reordered)}")
     for k, bad in differ:
-        print(f"  {k} ({ka[k]['file']} -> {kb[k]['file']}): {', '.join(bad)}")
+        print(f"  {k} ({ka[k]['file']} -> {kb[k]['file']}): {', '.join(bad)}" + (" (same lines, other order)" if k in reordered else ""))
         for p in bad:
             d = list(difflib.unified_diff(ka[k][p], kb[k][p], "A", "B", lineterm="", n=1))
             print("".join(f"\n    {x}" for x in d[:20])[1:])
